@@ -2,7 +2,7 @@
 """Headline benchmark: Gibbs iterations/sec of BNMF on a synthetic I=J=8192, K=64 matrix
 with a 10 % missing mask (BASELINE.json metric / configs[2]; it fits one GPU).
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--repeats R]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--repeats R] [--dump-outputs DIR]
 
 One process per GPU.  For N > 1 the ranks are either started by a launcher that sets RANK / WORLD_SIZE /
 LOCAL_RANK / MASTER_ADDR / MASTER_PORT (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`: used
@@ -18,6 +18,11 @@ handed to page-locked host arrays included; `device_resident` i
 on the device.  `mse_trajectory` holds the masked MSE of the first iterations of this very run (up to 200), and
 `cpu_baseline.mse_vs_iter_small` the same chain (same Philox seed) run by the CPU oracle and by the device at a size
 the oracle finishes.  Rank 0 prints ONE JSON line.
+
+--steps K is the number of timed iterations, and `ms_per_step` the time one of them took (the timed seconds over K).
+--dump-outputs DIR writes what the timed path computed in its last iteration -- the state a caller of run() holds after it
+and that iteration's metrics -- as DIR/<name>.npy; the inputs and the initial state are seeded, so that two builds can be
+compared output for output.
 """
 import argparse
 import hashlib
@@ -67,6 +72,35 @@ WORKLOADS = {
 }
 PRI2 = dict(alpha=1.0, beta=1.0, lambdaU=0.1, lambdaV=0.1)
 PRI3 = dict(alpha=1.0, beta=1.0, lambdaF=0.1, lambdaS=0.1, lambdaG=0.1)
+REGION_SAMPLE_BYTES = 512 << 20     # page-locked sample arrays of one timed region, at most (they are re-used by every region)
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+STATE = {"bnmf": ("U", "V", "tau"), "bnmtf": ("F", "S", "G", "tau")}     # (the variational models: their _NAMES)
+
+
+def _regions(steps, repeats, sample_bytes_per_step=0):
+    """The --steps timed iterations as consecutive timed regions: --repeats of them, more when one region's samples would not
+    fit REGION_SAMPLE_BYTES; sizes differ by at most one, the first is the largest."""
+    cap = max(1, REGION_SAMPLE_BYTES // sample_bytes_per_step) if sample_bytes_per_step else steps
+    r = max(min(max(1, repeats), steps), -(-steps // cap))
+    return [steps // r + (i < steps % r) for i in range(r)]
+
+
+def model_outputs(model, kind, metrics):
+    """What run() leaves a caller after the last timed iteration: the model's state (the last sample of the Gibbs samplers,
+    the q-parameters of the variational ones) and that iteration's MSE, R^2, Rp."""
+    model._pull()
+    out = {n: getattr(model, n) for n in STATE.get(kind, getattr(model, "_NAMES", ()))}
+    out["metrics"] = metrics
+    return out
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: d/<name>.npy in float64 (64 MB in all at most: every workload's outputs fit whole)."""
+    arrays = {n: np.asarray(a, dtype=np.float64) for n, a in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES, {n: a.shape for n, a in arrays.items()}
+    os.makedirs(d, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(d, n + ".npy"), a)
 
 
 def _blas_cores():
@@ -352,11 +386,14 @@ def main_small(a, w):
             m.close()
     m.run(max(a.warmup, 1))
     # one model, the reference's call: run(iterations) with every sample handed to the host and the three metrics per iteration
+    sizes = _regions(steps, a.repeats)
     dts = []
-    for _ in range(max(1, a.repeats)):
-        t0 = time.perf_counter(); m.run(steps); dts.append(time.perf_counter() - t0)
+    for n in sizes:
+        t0 = time.perf_counter(); m.run(n); dts.append(time.perf_counter() - t0)
     mse = list(m.all_performances["MSE"])
-    dt = float(np.median(dts))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, model_outputs(m, w["kind"], [m.all_performances[q][-1] for q in ("MSE", "R^2", "Rp")]))
+    dt = float(sum(dts))
     dev_s = float(m.all_times[-1])           # the device's own clock over the last call (HIP events around the iterations)
     t0 = time.perf_counter(); m.run(steps, store_samples=False); t_nos = time.perf_counter() - t0
     desc = m.describe()
@@ -385,11 +422,16 @@ def main_small(a, w):
            "config": {"workload": "%s Gibbs, synthetic R %dx%d K=%d%s, %.0f %% missing, priors alpha=beta=1 lambda=0.1, init random; one model through the class API: run(%d) incl. the sample hand-off and the per-iteration metrics" % (
                "BNMF" if kind == "bnmf" else "BNMTF", w["I"], w["J"], w["K"], " L=%d" % w["L"] if "L" in w else "", 100 * w["missing"], steps)},
            "published": {"value": w["published"], "unit": "iterations/s", "hardware": "unstated CPU, Python 2.7 (BASELINE.md section 1)", "source": w["source"]},
-           "repeats": {"n": len(dts), "values": [steps / d for d in dts]},
-           "device_clock_it_s": steps / dev_s if dev_s > 0 else None, "no_samples_it_s": steps / t_nos,
+           "repeats": {"n": len(dts), "values": [n / d for n, d in zip(sizes, dts)]},
+           "device_clock_it_s": sizes[-1] / dev_s if dev_s > 0 else None, "no_samples_it_s": steps / t_nos,
            "create_ms_per_model": {"median": 1e3 * float(np.median(t_build[1:])), "first": 1e3 * t_build[0], "what": "class constructor + initialise + bnmtf_create + state upload"},
            "batch": batch, "mse_first_last": [mse[0], mse[-1]], "describe": desc, "roofline": None, "cpu_baseline": None}
     print(json.dumps(out)); sys.stdout.flush()
+
+
+def heldout_outputs(cv):
+    """The model-selection jobs' result (of the last slot setting): every fold's held-out performance, per measure."""
+    return {"heldout_" + q.replace("^", ""): v for q, v in cv.performances.items()}
 
 
 def main_cv(a, w):
@@ -417,6 +459,8 @@ def main_cv(a, w):
         nmodels = w["folds"] * len(w["values_K"]) + w["folds"]
         res[str(s)] = {"slots": s, "seconds": dt, "models": nmodels, "model_iterations_per_s": nmodels * its / dt,
                        "heldout_MSE": cv.average_performance["MSE"], "heldout_R2": cv.average_performance["R^2"]}
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, heldout_outputs(cv))
     best = max(res.values(), key=lambda r: r["model_iterations_per_s"])
     out = {"metric": "model-iterations/sec of the GDSC-shaped 10-fold line-search cross-validation (BNMF %s 622x138, K in {15,20,25,30}, %d iterations)" % ("VB" if vb else "Gibbs", its),
            "value": best["model_iterations_per_s"], "unit": "model-iterations/s", "n_gpus": 1, "steps": its, "warmup": 0, "ms_per_step": 1e3 * best["seconds"] / its,
@@ -462,6 +506,8 @@ def main_cv3(a, w):
         pool.close()
         res[str(s) + ("b" if batched else "")] = {"slots": s, "batched": batched, "seconds": dt, "models": fits[0], "model_iterations_per_s": fits[0] * its / dt,
                                                   "heldout_MSE": cv.average_performance["MSE"], "heldout_R2": cv.average_performance["R^2"]}
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, heldout_outputs(cv))
     best = max(res.values(), key=lambda r: r["model_iterations_per_s"])
     out = {"metric": "model-iterations/sec of the GDSC-shaped 10-fold greedy-search cross-validation (BNMTF Gibbs 622x138, K, L in 5..10, %d iterations)" % its,
            "value": best["model_iterations_per_s"], "unit": "model-iterations/s", "n_gpus": 1, "steps": its, "warmup": 0, "ms_per_step": 1e3 * best["seconds"] / its,
@@ -483,10 +529,9 @@ def _warm(job, shared):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None)
+    ap.add_argument("--steps", type=int, default=None, help="timed iterations (default 100; the small workloads: their own count)")
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps iterations each (at least this many); value = median")
-    ap.add_argument("--min-timed-s", type=float, default=1.0, help="keep adding timed regions until they total this many seconds (at most 400 regions)")
+    ap.add_argument("--repeats", type=int, default=1, help="timed regions the --steps iterations are split into; value = steps / timed seconds")
     ap.add_argument("--workload", default="bnmf_8192_k64", choices=sorted(WORKLOADS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-whole-iteration", action="store_true",
@@ -497,7 +542,10 @@ def main():
     ap.add_argument("--batch", type=int, nargs="*", default=[16, 256], help="small workloads: models per batched call")
     ap.add_argument("--slots", type=int, nargs="*", default=[1, 4], help="cv_gdsc: replica slots on the GPU")
     ap.add_argument("--cv-batched", action="store_true", help="cv_gdsc: the pool fits its jobs in batched launches")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last iteration as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
     a.steps_given = a.steps is not None
     if a.steps is None:
         a.steps = 100
@@ -545,19 +593,20 @@ def main():
             _lib.check(L.bnmf_vb_run(h, n, None, _lib.ptr(perf), None, None))
 
     # the reference's run() hands every sample to the host (all_U[it], all_V[it]): the timed loop does too -- page-locked
-    # arrays of --steps samples (re-used by every timed region), asynchronous copies behind the compute stream
+    # arrays of one region's samples (re-used by every timed region), asynchronous copies behind the compute stream
+    with_samples = kind not in ("vb", "trivb") and not a.no_samples
+    sizes = _regions(a.steps, a.repeats, 4 * (I * K + J * w.get("L", K) + (K * w["L"] if kind == "bnmtf" else 0)) if with_samples else 0)
     tri_orders = None
     if kind == "trivb":           # the three shuffles of every iteration, drawn the reference's way (bnmtf_vb_optimised.py:171-186): reused by every region
         import random as _random
         _random.seed(1)
-        tri_orders = np.ascontiguousarray(model._draw_orders(max(a.steps, a.warmup, 50)))
-    with_samples = kind not in ("vb", "trivb") and not a.no_samples
+        tri_orders = np.ascontiguousarray(model._draw_orders(max(sizes[0], a.warmup, 50)))
     bufs = None
     if with_samples:
         if kind == "bnmf":
-            bufs = (_lib.sample_buffer((a.steps, I, K)), _lib.sample_buffer((a.steps, J, K)), None)
+            bufs = (_lib.sample_buffer((sizes[0], I, K)), _lib.sample_buffer((sizes[0], J, K)), None)
         else:
-            bufs = (_lib.sample_buffer((a.steps, I, K)), _lib.sample_buffer((a.steps, J, w["L"])), _lib.sample_buffer((a.steps, K, w["L"])))
+            bufs = (_lib.sample_buffer((sizes[0], I, K)), _lib.sample_buffer((sizes[0], J, w["L"])), _lib.sample_buffer((sizes[0], K, w["L"])))
     trajectory = []
     perf_w = np.zeros((max(a.warmup, 1), 3))
     if a.warmup > 0:
@@ -566,8 +615,8 @@ def main():
     # one untimed pass over the page-locked sample arrays: the device's first write to a fresh pinned page is slow (the first
     # timed region ran at 600-1 700 instead of 2 400 it/s), and the arrays are re-used by every timed region
     if with_samples:
-        perf_t = np.zeros((a.steps, 3))
-        run(a.steps, perf_t, samples=bufs)
+        perf_t = np.zeros((sizes[0], 3))
+        run(sizes[0], perf_t, samples=bufs)
         trajectory += [float(x) for x in perf_t[:, 0]]
     # timed regions: HIP events bracket the roofline kernel only, on its own stream, in every fourth iteration (an event
     # record drains the queue for ~4 us: two per iteration were 2 % of the headline iteration)
@@ -578,22 +627,23 @@ def main():
     model.set_profiling(True, kernel=ROOF, every=4)
     perf_first = None
     dts = []
-    # (every region is EXACTLY --steps iterations between two barriers; regions are added until they total --min-timed-s, so that
-    # the timed work is seconds, not milliseconds -- the count is the same on every rank: it follows the max-reduced times)
-    while len(dts) < max(1, a.repeats) or (sum(dts) < a.min_timed_s and len(dts) < 400):
-        perf = np.zeros((a.steps, 3))
+    # (the regions together are EXACTLY --steps iterations, each between two barriers; a region's time is the max over the ranks)
+    for n in sizes:
+        perf = np.zeros((n, 3))
         sync()
         t0 = time.perf_counter()
-        run(a.steps, perf, samples=bufs)
+        run(n, perf, samples=bufs)
         sync()
         dts.append(cp.allreduce_max(time.perf_counter() - t0))
         if len(trajectory) < 400:
             trajectory += [float(x) for x in perf[:, 0]]
         if perf_first is None:
             perf_first = perf
-    dt = float(np.median(dts))
+    dt = float(sum(dts))
     if with_samples:
-        assert np.isfinite(bufs[0][-1]).all() and float(np.abs(bufs[0][-1]).max()) > 0.0
+        assert np.isfinite(bufs[0][sizes[-1] - 1]).all() and float(np.abs(bufs[0][sizes[-1] - 1]).max()) > 0.0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model_outputs(model, kind, perf[-1]))
 
     names = {_lib.KERNEL_GEMM_ROWS: "gemm_rows(R~.V)", _lib.KERNEL_GEMM_COLS: "gemm_cols((R~^T.F).S from the S step's slabs)" if kind == "bnmtf" else "gemm_cols(R~^T.U)",
              _lib.KERNEL_SWEEP_ROWS: "sweep_rows", _lib.KERNEL_SWEEP_COLS: "sweep_cols"}
@@ -618,13 +668,13 @@ def main():
     if with_samples:
         run(2)
         sync(); t1 = time.perf_counter()
-        run(a.steps)
-        sync(); resident = a.steps / cp.allreduce_max(time.perf_counter() - t1)
+        run(sizes[0])
+        sync(); resident = sizes[0] / cp.allreduce_max(time.perf_counter() - t1)
 
     # what the box sustains under this loop: the pool's boxes differ by +-5 % in rate, and that spread is the shader clock
     # (~861 k cycles per iteration of the headline on either kind) -- rocm-smi read a few times beside ~2 s of the
     # device-resident loop, after everything that is timed; None when rocm-smi is not there or says nothing
-    clock = _clock_beside(clock_helper, lambda: run(max(a.steps, 50) if kind != "trivb" else min(max(a.steps, 50), len(tri_orders))), sync) if clock_helper is not None else None
+    clock = _clock_beside(clock_helper, lambda: run(max(sizes[0], 50) if kind != "trivb" else min(max(sizes[0], 50), len(tri_orders))), sync) if clock_helper is not None else None
 
     import ctypes as C_
     ck, cr = C_.c_int(), C_.c_int()
@@ -639,6 +689,7 @@ def main():
     if rank == 0:
         Wc = w.get("L", K)                 # width of the cols-direction contraction's factor operand is K (F or U)
         ms_step = 1e3 * dt / a.steps
+        rates = [n / d for n, d in zip(sizes, dts)]
         # dominant HBM kernel, "the U^T.R step" (SURVEY.md 8(d)): algorithmic 4*I*J bytes (R~ read once) and 2*I*J*K flop
         # per launch (per rank: its column shard); fp32-exact products on the bf16 matrix cores (3-term splits), so a
         # stream of R~ from HBM
@@ -703,7 +754,7 @@ def main():
                        "samples": ("handed to the host every iteration (all_U/all_V: %.1f MiB per iteration, page-locked arrays, copy stream)" % (
                                        4.0 * (I * K + J * Wc + (K * Wc if kind == "bnmtf" else 0)) / 2 ** 20)) if with_samples else
                                   ("none (the variational run() stores no samples)" if kind in ("vb", "trivb") else "device-resident (--no-samples)")},
-            "repeats": {"n": len(dts), "timed_seconds": float(sum(dts)), "values": [a.steps / d for d in dts[:40]], "min": a.steps / max(dts), "median": a.steps / dt, "max": a.steps / min(dts)},
+            "repeats": {"n": len(dts), "timed_seconds": dt, "values": [n / d for n, d in zip(sizes[:40], dts)], "min": min(rates), "median": float(np.median(rates)), "max": max(rates)},
             "device_resident": None if resident is None else {"value": resident, "unit": "iterations/s", "what": "same loop, samples left on the device"},
             "clock": clock,
             "roofline": roof,

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ by IMPORTING THE REFERENCE.
 
-Runs only in the build container (needs /root/reference).  The reference is
-Python-2 source, so a throw-away copy is converted with lib2to3 under
-/tmp/oracle (never inside this repo, never shipped to the GPU box) and
-imported from there -- recipe of SURVEY.md Appendix B.  What is committed is
-DATA ONLY: inputs and the reference's outputs for them.
+Needs a checkout of the reference BNMTF project, named by BNMTF_REFERENCE.  The
+reference is Python-2 source, so a throw-away copy is converted with lib2to3
+in a temporary directory (never inside this repo) and imported from there --
+recipe of SURVEY.md Appendix B.  What is committed is DATA ONLY: inputs and the
+reference's outputs for them.
 
-    python tests/golden/make_golden.py            # writes tests/golden/*.npz
+    BNMTF_REFERENCE=<checkout> python tests/golden/make_golden.py   # writes tests/golden/*.npz
 """
 import contextlib
 import io
@@ -15,15 +15,17 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference"
-TMP = "/tmp/oracle"
+REF = os.environ.get("BNMTF_REFERENCE", "")
+TMP = os.path.join(tempfile.gettempdir(), "bnmtf_oracle")
 
 
 def import_reference():
+    assert os.path.isdir(os.path.join(REF, "code")), "BNMTF_REFERENCE must name a checkout of the reference project"
     if not os.path.isdir(os.path.join(TMP, "BNMTF")):
         os.makedirs(TMP, exist_ok=True)
         shutil.copytree(REF, os.path.join(TMP, "BNMTF"))
@@ -502,7 +504,8 @@ def make_kmeans():
 def make_gdsc():
     """data_drug_sensitivity/gdsc/load_data.py:15-54 on the reference's own ic50 file: what load_gdsc returns for the
     first 12 cell lines (the excerpt travels as a fixture: header + 12 lines of the data file) and summary numbers of the
-    whole file (checked where /root/reference is present)."""
+    whole file (which travels gzipped as gdsc_ic50.txt.gz)."""
+    import gzip
     sys.path.insert(0, TMP + "/BNMTF/data_drug_sensitivity/gdsc")
     import load_data as ref_load
     src = REF + "/data_drug_sensitivity/gdsc/ic50_excl_empty_filtered_cell_lines_drugs.txt"
@@ -510,6 +513,9 @@ def make_gdsc():
     excerpt = os.path.join(HERE, "gdsc_excerpt.txt")
     with open(excerpt, "w") as f:
         f.writelines(lines[:13])
+    with open(src, "rb") as fi, open(os.path.join(HERE, "gdsc_ic50.txt.gz"), "wb") as fo, \
+            gzip.GzipFile(filename="", mode="wb", compresslevel=9, fileobj=fo, mtime=0) as gz:
+        gz.write(fi.read())
     out = {}
     X, X_min, M, drugs, cells, cancers, tissues = ref_load.load_gdsc(location=excerpt)
     out["ex/X"], out["ex/X_min"], out["ex/M"] = X, X_min, M

@@ -226,6 +226,25 @@ def test_bench_clock_reading_is_optional():
     assert got is None or (got["sclk_mhz_median"] > 0 and got["readings"] >= 1)
 
 
+def test_bench_times_exactly_the_steps_asked_for(tmp_path):
+    """bench.py --steps K: the timed regions add up to K iterations whatever --repeats asks, with more regions when one region's
+    page-locked sample arrays would pass REGION_SAMPLE_BYTES; --dump-outputs writes every array as float64 .npy."""
+    import importlib.util, os
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    for steps, repeats, per_step in [(1, 1, 0), (100, 1, 0), (100, 5, 0), (7, 3, 0), (3, 10, 0), (5, 0, 0),
+                                     (100, 1, 4 << 20), (1000, 1, 4 << 20), (12345, 4, 1 << 20), (2, 1, 1 << 30)]:
+        sizes = bench._regions(steps, repeats, per_step)
+        assert sum(sizes) == steps and min(sizes) >= 1 and sizes[0] == max(sizes) and max(sizes) - min(sizes) <= 1, (steps, repeats, sizes)
+        assert len(sizes) >= min(max(1, repeats), steps)
+        assert per_step == 0 or sizes[0] == 1 or sizes[0] * per_step <= bench.REGION_SAMPLE_BYTES
+    assert bench._regions(100, 1, 4 << 20) == [100]
+    bench.dump_outputs(str(tmp_path / "out"), {"U": np.arange(6, dtype=np.float32).reshape(3, 2), "metrics": [1.0, 0.5, 0.25]})
+    U, m = np.load(str(tmp_path / "out" / "U.npy")), np.load(str(tmp_path / "out" / "metrics.npy"))
+    assert U.dtype == m.dtype == np.float64 and np.array_equal(U, np.arange(6).reshape(3, 2)) and np.array_equal(m, [1.0, 0.5, 0.25])
+
+
 def test_run_many_takes_gibbs_models_only():
     """The batch entry point fits a model as bnmf_gibbs_optimised.run would: a subclass with its own run() (nmf_icm: another
     update rule, minimum_TN, the Gamma mode) is refused before anything reaches the device, and the replica pool's batching asks

@@ -4,7 +4,8 @@
     run empty ('singleton' refill and the reference's centroid-is-a-view-of-X behaviour), an unobserved column, the toy
     BNMTF matrix by rows and by columns (what initialise(init_FG='kmeans') clusters);
   * bnmtf_amd.data.load_gdsc / negate_gdsc == data_drug_sensitivity/gdsc/load_data.py:15-70 on the first 12 cell lines of the
-    reference's own ic50 file (the excerpt is a fixture), and on the whole file where /root/reference is present."""
+    reference's own ic50 file (the excerpt is a fixture), and on the whole file (a gzipped fixture)."""
+import gzip
 import os
 
 import numpy as np
@@ -39,15 +40,15 @@ def test_kmeans_golden_cases_cover_the_empty_cluster_rule():
     assert len(set(g[-1])) == int(KM["empties/K"])          # all six clusters are populated although the data has three groups
 
 
-def test_gdsc_loader_matches_the_reference_on_its_own_file():
+def test_gdsc_loader_matches_the_reference_on_its_own_file(tmp_path):
     g = np.load(os.path.join(HERE, "golden", "gdsc.npz"))
     X, X_min, M, drugs, cells, cancers, tissues = data.load_gdsc(os.path.join(HERE, "golden", "gdsc_excerpt.txt"))
     assert np.array_equal(X, g["ex/X"]) and np.array_equal(X_min, g["ex/X_min"]) and np.array_equal(M, g["ex/M"])
     assert len(drugs) == int(g["ex/n_drugs"]) and len(cells) == int(g["ex/n_cells"]) == len(cancers) == len(tissues)
     assert np.array_equal(data.negate_gdsc(X, M), g["ex/negated"])
-    full = "/root/reference/data_drug_sensitivity/gdsc/ic50_excl_empty_filtered_cell_lines_drugs.txt"
-    if not os.path.exists(full):
-        pytest.skip("the whole file is only in the build container")
+    full = str(tmp_path / "ic50_excl_empty_filtered_cell_lines_drugs.txt")
+    with gzip.open(os.path.join(HERE, "golden", "gdsc_ic50.txt.gz"), "rb") as fi, open(full, "wb") as fo:
+        fo.write(fi.read())
     X, X_min, M, drugs, cells, cancers, tissues = data.load_gdsc(full)
     assert tuple(X.shape) == tuple(g["full/shape"]) and M.sum() == float(g["full/M_sum"])
     assert X.sum() == float(g["full/X_sum"]) and X.min() == float(g["full/minimum"])
