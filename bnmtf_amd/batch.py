@@ -7,8 +7,9 @@ The reference fits the candidates of a model search -- folds x ranks x restarts 
 (parallel_matrix_cross_validation.py:40-74).  Small BNMF and BNMTF Gibbs models run on the device as ONE block each
 (csrc/kernel_small.hip), so a list of them is one launch per kind; models that do not qualify are run in turn.  Variational models
 (bnmf_vb_optimised, any size its 8-wave kernels serve) walk their iterations in lock-step: every kernel of an iteration is ONE
-launch for all of them (csrc/many.h, api_many.inc: bnmf_vb_run_many), each model ending with the bits of its own run().  ICM models
-(nmf_icm: their own run(), update rule and minimum_TN) are not taken: ReplicaPool runs them one by one."""
+launch for all of them (csrc/many.h, api_many.inc: bnmf_vb_run_many), each model ending with the bits of its own run().  Models
+wider than 64 columns (column blocks, _blocked.py: several handles per model) of any of these kinds are run by their own run().
+ICM models (nmf_icm: their own run(), update rule and minimum_TN) are not taken: ReplicaPool runs them one by one."""
 import ctypes as C
 import time
 
@@ -39,7 +40,8 @@ def run_many(models, iterations, update='draw', store_samples=True, expectation=
     """run(iterations, update, store_samples, expectation) of every model in `models` (bnmf_gibbs_optimised and / or
     bnmtf_gibbs_optimised instances), with the models of the one-launch path that share a device and a kind sharing a single
     launch; bnmf_vb_optimised instances (their run(iterations)): the models of a device walk their iterations in lock-step, one
-    launch per kernel for all of them (csrc/api_many.inc).  Returns the list of the runs' results, in the order of `models`."""
+    launch per kernel for all of them (csrc/api_many.inc).  A Gibbs model wider than 64 columns (column blocks) is run by its own
+    run(iterations, update, store_samples, expectation).  Returns the list of the runs' results, in the order of `models`."""
     models = list(models)
     if not models:
         return []
@@ -53,8 +55,11 @@ def run_many(models, iterations, update='draw', store_samples=True, expectation=
     out = [None] * len(models)
     upd = _lib.UPDATE_MODE if update == 'mode' else _lib.UPDATE_DRAW
     _run_many_vb([m for m in models if _kind(m) == "vb"], int(iterations))
+    for i, m in enumerate(models):
+        if _kind(m) in ("bnmf", "bnmtf") and m._blocks is not None:
+            out[i] = m.run(iterations, update, store_samples, expectation)
     for kind in ("bnmf", "bnmtf"):
-        idx = [i for i, m in enumerate(models) if _kind(m) == kind]
+        idx = [i for i, m in enumerate(models) if _kind(m) == kind and m._blocks is None]
         if not idx:
             continue
         ms = [models[i] for i in idx]

@@ -126,6 +126,7 @@ class bnmf_gibbs_optimised(DeviceModel):
         all_U = np.zeros((it, self.I, self.K), dtype=np.float32) if store_samples else None
         all_V = np.zeros((it, self.J, self.K), dtype=np.float32) if store_samples else None
         self._dev_expect = None
+        self._host_expect = None              # (a run without expectation= leaves no means of an earlier chain behind)
         acc = None
         if expectation is not None:
             burn_in, thinning = int(expectation[0]), int(expectation[1])

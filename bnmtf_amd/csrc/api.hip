@@ -1219,6 +1219,13 @@ static void describe_model(bnmtf_model* h) {
     h->description += buf;
   }
 }
+
+// the metric kernel's per-tile partial sums (launch_metric_sums): one buffer per handle, sized by its I x J
+static int metric_partials(bnmtf_model* h, double** out) {
+  if (!h->metric_part) CHK(dalloc(&h->metric_part, metric_tiles(h->I, h->J) * 8, false));
+  *out = h->metric_part;
+  return BNMTF_OK;
+}
 }  // namespace bnmtf
 extern "C" {
 
@@ -1234,7 +1241,7 @@ int bnmtf_destroy(bnmtf_handle h) try {
   dfree(h->muS); dfree(h->tauS); dfree(h->varS); dfree(h->mv_rows); dfree(h->mv_cols); dfree(h->tri_order); dfree(h->tri_sums); dfree(h->tri_third); dfree(h->ss_Aperm);
   dfree(h->ss_Wc); dfree(h->ss_Gc); dfree(h->ss_cands); dfree(h->ss_slabs); dfree(h->ss_AB); dfree(h->ss_r); dfree(h->ss_bpart); dfree(h->ss_tinv); dfree(h->ss_rec);
   dfree(h->Rfull); h->Mtrain = nullptr; h->out6 = nullptr; h->tau_d = nullptr; h->tau_f = nullptr; h->acc = nullptr;   // (one allocation: bnmtf_create)
-  dfree(h->Mscratch); dfree(h->Ad); dfree(h->Bd); dfree(h->AdW); dfree(h->BdW);
+  dfree(h->Mscratch); dfree(h->Ad); dfree(h->Bd); dfree(h->AdW); dfree(h->BdW); dfree(h->metric_part);
   dfree(h->A2d); dfree(h->B2d); dfree(h->vb_rec); dfree(h->vbred);
   dfree(h->rec); dfree(h->gunit); dfree(h->S);
   for (auto& pe : h->pending_events) { (void)hipEventDestroy(pe.second.first); (void)hipEventDestroy(pe.second.second); }
@@ -1704,6 +1711,7 @@ static int metric_sums_impl(bnmtf_handle h, const uint8_t* Mp, const double* A, 
   }
   MetricArgs m;
   m.R = h->Rfull; m.Mp = mask; m.I = I; m.J = J; m.A = Ad; m.B = Bd; m.K = Kc; m.out6 = h->out6; m.A2 = nullptr; m.B2 = nullptr;
+  CHK(metric_partials(h, &m.part));
   launch_metric_sums(m, h->stream);
   HIPCHK(hipMemcpyAsync(sums_out, h->out6, 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));

@@ -599,6 +599,7 @@ static int vb_esd_direct(bnmtf_model* h, double* out, double* terms = nullptr) {
   HIPCHK(hipMemcpyAsync(h->B2d, b2.data(), b2.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   MetricArgs m;
   m.R = h->Rfull; m.Mp = h->Mtrain; m.I = I; m.J = J; m.A = h->Ad; m.B = h->Bd; m.K = K; m.A2 = h->A2d; m.B2 = h->B2d; m.out6 = h->out6;
+  CHK(metric_partials(h, &m.part));
   launch_metric_sums(m, h->stream);
   double s[8];
   HIPCHK(hipMemcpyAsync(s, h->out6, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));

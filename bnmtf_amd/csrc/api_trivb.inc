@@ -178,6 +178,7 @@ static int enqueue_tri_sums(bnmtf_model* h) {
     MetricArgs m;
     m.R = h->Rfull; m.Mp = h->Mtrain; m.I = h->I; m.J = h->J; m.A = h->Ad; m.B = h->Bd; m.K = width; m.A2 = nullptr; m.B2 = nullptr;
     m.out6 = h->tri_sums + 8 * which;
+    CHK(metric_partials(h, &m.part));
     launch_metric_sums(m, h->stream);
   }
   return BNMTF_OK;

@@ -255,12 +255,28 @@ __global__ __launch_bounds__(256) void metric_kernel(MetricArgs a) {
     if (tid < w) for (int m = 0; m < 7; ++m) red[m][tid] += red[m][tid + w];
     __syncthreads();
   }
-  if (tid < 7) atomicAdd(a.out6 + tid, red[tid][0]);
+  if (tid < 7) a.part[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 8 + tid] = red[tid][0];
+}
+// the tiles' partial sums in a fixed order: the same operands give the same bits on every call (a column-blocked model's tau
+// comes from these sums, so a chain would otherwise depend on the order in which the tiles finished)
+__global__ __launch_bounds__(256) void metric_reduce_kernel(const double* part, int ntiles, double* out) {
+  __shared__ double red[7][256];
+  const int tid = threadIdx.x;
+  double s[7] = {0, 0, 0, 0, 0, 0, 0};
+  for (int t = tid; t < ntiles; t += 256)
+    for (int m = 0; m < 7; ++m) s[m] += part[(size_t)t * 8 + m];
+  for (int m = 0; m < 7; ++m) red[m][tid] = s[m];
+  __syncthreads();
+  for (int w = 128; w >= 1; w >>= 1) {
+    if (tid < w) for (int m = 0; m < 7; ++m) red[m][tid] += red[m][tid + w];
+    __syncthreads();
+  }
+  if (tid < 8) out[tid] = tid < 7 ? red[tid][0] : 0.0;
 }
 void launch_metric_sums(const MetricArgs& a, hipStream_t st) {
-  (void)hipMemsetAsync(a.out6, 0, 8 * sizeof(double), st);
   dim3 grid((a.J + 31) / 32, (a.I + 31) / 32), block(32, 8);
   hipLaunchKernelGGL(metric_kernel, grid, block, 0, st, a);
+  hipLaunchKernelGGL(metric_reduce_kernel, dim3(1), dim3(256), 0, st, (const double*)a.part, (int)(grid.x * grid.y), a.out6);
 }
 
 __global__ __launch_bounds__(256) void sum_stats_kernel(const double* stats, int nblocks, double* acc) {

@@ -257,7 +257,9 @@ struct MetricArgs {
   const double* A; const double* B; int K;     // A [I][K], B [J][K]
   const double* A2; const double* B2;          // optional (VB): second-moment factors; out[6] = sum_mask (A2_i.B2_j - sum_k A_ik^2 B_jk^2)
   double* out6;                                // 8 doubles
+  double* part;                                // metric_tiles(I, J) x 8 doubles: the tiles' partial sums
 };
+inline size_t metric_tiles(int I, int J) { return (size_t)((I + 31) / 32) * (size_t)((J + 31) / 32); }
 void launch_metric_sums(const MetricArgs& a, hipStream_t st);
 
 // ---------------------------------------------------------------------------

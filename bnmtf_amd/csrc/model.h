@@ -172,6 +172,7 @@ struct bnmtf_model {
   float *mv_rows = nullptr, *mv_cols = nullptr;             // masked variance sums mvG [I_loc][32], mvF [J_loc][32]
   int* tri_order = nullptr; size_t tri_order_cap = 0;        // per iteration: K L entries of S, K columns of F, L columns of G
   double* tri_sums = nullptr;                                // 3 x 8 masked sums (metric_kernel passes)
+  double* metric_part = nullptr;                             // metric_kernel's per-tile partial sums (metric_partials)
   uint32_t s_word0 = 0; int s_ldword = 0;                    // a block of a wider S (bnmtf_set_s_block): the Philox column word of its entry (k, l) is s_word0 + k s_ldword + l (0: k L + l)
   bool tri_w_current = false;                                // ss_Wc holds the masked column Grams of the current q(F) (formed behind its sweep)
   bool tri_mv_cols_current = false;                          // mv_cols holds the masked variance sums of the current q(F) (formed in the G step)
