@@ -94,6 +94,16 @@ _SIGS = {
     "bnmtf_set_sweep_path": ([_P, C.c_int], C.c_int),
     "bnmtf_kernel_stats": ([_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)], C.c_int),
     "bnmtf_describe": ([_P, C.c_char_p, C.c_size_t], C.c_int),
+    "bnmtf_np_create": ([_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)], C.c_int),
+    "bnmf_np_set_state": ([_P, _P, _P], C.c_int),
+    "bnmf_np_get_state": ([_P, _P, _P], C.c_int),
+    "bnmf_np_update": ([_P, C.c_int, C.c_int], C.c_int),
+    "bnmf_np_run": ([_P, C.c_int, _P, _P, _P], C.c_int),
+    "bnmtf_np_set_state": ([_P, _P, _P, _P], C.c_int),
+    "bnmtf_np_get_state": ([_P, _P, _P, _P], C.c_int),
+    "bnmtf_np_update": ([_P, C.c_int, C.c_int, C.c_int], C.c_int),
+    "bnmtf_np_run": ([_P, C.c_int, _P, _P, _P], C.c_int),
+    "bnmtf_np_metrics": ([_P, _P, _P], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 

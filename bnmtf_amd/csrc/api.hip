@@ -42,6 +42,7 @@ static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
   catch (...) { bnmtf::set_error("host exception"); return BNMTF_EINVAL; }
 extern "C" int bnmtf_shard_range(int64_t n, int rank, int world, int64_t* first, int64_t* count);
 namespace bnmtf {
+static void np_free(bnmtf_model* h);   // api_np.inc
 
 template <typename T>
 static int dalloc(T** p, size_t count, bool zero = true) {
@@ -1234,6 +1235,7 @@ int bnmtf_destroy(bnmtf_handle h) try {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->comm) comm_destroy(h->comm);
+  np_free(h);
   small_free(h);            // (first: a small model's arena also holds Rfull, the posterior sums, Ad / Bd -- their pointers are cleared)
   free_dir(h->rows); free_dir(h->cols); free_dir(h->reff); free_dir(h->ceff);
   dfree(h->slabsS); dfree(h->CfS); dfree(h->deltaS); dfree(h->s_partial); dfree(h->s_w); dfree(h->s_omp); dfree(h->lambdaS); dfree(h->s_numer); dfree(h->s_taup);
@@ -1770,3 +1772,4 @@ int bnmtf_gamma_sample(double alpha, double beta, uint64_t seed, uint64_t it, in
 #include "api_models.inc"
 #include "api_trivb.inc"
 #include "api_many.inc"
+#include "api_np.inc"

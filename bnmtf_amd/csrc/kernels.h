@@ -480,4 +480,34 @@ void launch_tn_sample(const double* mu, const double* tau, size_t n, uint64_t se
 void launch_tn_moments(const double* mu, const double* tau, size_t n, double* e, double* v, hipStream_t st);
 void launch_gamma_sample(double alpha, double beta, uint64_t seed, uint32_t it, double* out, hipStream_t st);
 
+// ---------------------------------------------------------------------------
+// Non-probabilistic NMF / NMTF (kernel_np.hip): multiplicative updates
+// ---------------------------------------------------------------------------
+struct NpSweepArgs {
+  const float* Rn; int n, m;         // [n][m] the data of the n units (NaN where unobserved)
+  float* Xt;                         // [K][n] this direction's factor, column major (updated in columns k0 .. k1-1)
+  const float* Yt;                   // [K][m] the other factor, column major
+  int K, k0, k1;
+  double* stats;                     // null, or [blocks][8]: the eight training-mask sums of the final P (np_entry_stats)
+};
+struct NpSPassArgs {
+  const float* Rn; float* P;         // [I][J] (P only on the observed entries)
+  const float* Ft; const float* Gt;  // [K][I], [L][J]
+  const float* S_in; float* S_out;   // [K][L]
+  const double* part_prev;           // [blocks][2] numerator / denominator partials of entry prev (the previous pass's part_cur)
+  double* part_cur;                  // [blocks][2] ... of entry cur
+  int I, J, K, L;
+  int prev, cur;                     // entries (k L + l) this pass finishes / accumulates; -1: none
+};
+void launch_np_prepare(const float* R, const uint8_t* M, int I, int J, float* Rn, float* RnT, hipStream_t st);
+bool np_sweep_supported(int m, int K);
+int np_sweep_blocks(int n, int m);
+void launch_np_sweep(const NpSweepArgs& a, hipStream_t st);
+void launch_np_stats_finish(const double* part, int nb, double* out, hipStream_t st);   // out[8] = column sums of part[nb][8]
+void launch_np_small_product(const float* S, int sc, int sa, const float* in, int A, int C, int n, float* out, hipStream_t st);
+void launch_np_build_p(const float* Rn, const float* Ut, const float* Yt, int I, int J, int K, float* P, hipStream_t st);
+int np_s_blocks(int I);
+void launch_np_s_pass(const NpSPassArgs& a, hipStream_t st);
+void launch_np_metrics(const float* R, const uint8_t* M, const float* Ut, const float* Yt, int I, int J, int K, double* part, hipStream_t st);
+
 }  // namespace bnmtf

@@ -104,6 +104,7 @@ struct Dir {
 };
 
 struct Comm;   // RCCL wrapper (comm.cpp)
+struct NpState;   // the non-probabilistic models' buffers (api_np.inc)
 
 // A model small enough for the one-launch path (kernel_small.hip, api_small.inc): ONE device allocation holds its static tables
 // (both masked operands, slot / segment / permutation tables, prior rates) and its state (factors, q of the missing entries,
@@ -206,4 +207,5 @@ struct bnmtf_model {
   float* snap_host = nullptr; size_t snap_host_cap = 0;     // pinned ring, used when the caller's buffers are pageable
   hipEvent_t snap_ready[8] = {nullptr}, copy_done[8] = {nullptr};
   double create_ms = 0.0;                                   // wall time of bnmtf_create (host layout + uploads)
+  bnmtf::NpState* np = nullptr;                             // a handle of bnmtf_np_create (nmf_np / nmtf_np): its buffers
 };

@@ -333,6 +333,32 @@ BNMTF_API int bnmtf_kernel_stats(bnmtf_handle h, int kernel, double* total_ms, u
 /* geometry of the last create: padded shapes, split factor, slot counts (for DESIGN/bench) */
 BNMTF_API int bnmtf_describe(bnmtf_handle h, char* buf, size_t buflen);
 
+/* ---- non-probabilistic NMF / NMTF (nmf_np.py, nmtf_np.py: multiplicative updates) ---------------------
+ * A handle of its own kind: R ([I][J] fp32) and the 0/1 mask M ([I][J]) go to the device, nothing of the samplers' layouts is
+ * built, so K and L are not tied to wave lanes (1 <= K, L <= BNMTF_NP_MAX_RANK; rows and columns of at most 16 384 entries).
+ * L = 0: NMF (R ~ U V^T), L > 0: NMTF (R ~ F S G^T).  One GPU.  Such a handle takes the calls below, bnmtf_sync,
+ * bnmtf_describe and bnmtf_destroy; the sampler and variational calls refuse it.  Factors cross as double, live as fp32. */
+#define BNMTF_NP_MAX_RANK 256
+BNMTF_API int bnmtf_np_create(const float* R, const uint8_t* M, int I, int J, int K, int L, int device, bnmtf_handle* out);
+/* U [I][K], V [J][K] */
+BNMTF_API int bnmf_np_set_state(bnmtf_handle h, const double* U, const double* V);
+BNMTF_API int bnmf_np_get_state(bnmtf_handle h, double* U, double* V);
+/* update_U(k) (which = 0) or update_V(k) (which = 1): nmf_np.py:117-121 */
+BNMTF_API int bnmf_np_update(bnmtf_handle h, int which, int k);
+/* run(n_iter), nmf_np.py:84-107: per iteration the K columns of U, then the K columns of V.  perf_out [n][3] (MSE, R^2, Rp on the
+ * training mask), idiv_out [n] (compute_I_div), times_out [n] (seconds since the call began, device clock); any may be null */
+BNMTF_API int bnmf_np_run(bnmtf_handle h, int n_iter, double* perf_out, double* idiv_out, double* times_out);
+/* F [I][K], S [K][L], G [J][L] */
+BNMTF_API int bnmtf_np_set_state(bnmtf_handle h, const double* F, const double* S, const double* G);
+BNMTF_API int bnmtf_np_get_state(bnmtf_handle h, double* F, double* S, double* G);
+/* update_F(k) (which = 0), update_S(k, l) (which = 1), update_G(l) (which = 2): nmtf_np.py:152-174 */
+BNMTF_API int bnmtf_np_update(bnmtf_handle h, int which, int k, int l);
+/* run(n_iter), nmtf_np.py:116-144: per iteration the K L entries of S row by row, the K columns of F, the L columns of G */
+BNMTF_API int bnmtf_np_run(bnmtf_handle h, int n_iter, double* perf_out, double* idiv_out, double* times_out);
+/* the current point's sums over the entries of Mp ([I][J] 0/1; null: the training mask), fp64: out[8] = n, sum R, sum R^2,
+ * sum P, sum P^2, sum R P, the I-divergence sum R log(R / P) - R + P (nmf_np.py:146-148), sum (R - P)^2 */
+BNMTF_API int bnmtf_np_metrics(bnmtf_handle h, const uint8_t* Mp, double* out);
+
 #ifdef __cplusplus
 }
 #endif
