@@ -110,3 +110,29 @@ def test_run_many_still_refuses_the_np_models():
     R, M = np.ones((3, 4)), np.ones((3, 4))
     with pytest.raises(TypeError):
         run_many([NMF(R, M, 2)], 1)
+
+
+@pytest.mark.parametrize("I,J", [(16385, 3), (3, 16385)])
+def test_rows_and_columns_longer_than_16384_are_refused(I, J):
+    """bnmtf_np_create refuses before any device call, so the refusal reads the same with or without a GPU."""
+    R = np.ones((I, J)); M = np.ones((I, J))
+    for m in (NMF(R, M, 2, verbose=False), NMTF(R, M, 2, 3, verbose=False)):
+        m.U, m.V = np.ones((I, 2)), np.ones((J, 2))
+        m.F, m.S, m.G = np.ones((I, 2)), np.ones((2, 3)), np.ones((J, 3))
+        with pytest.raises(BnmtfError) as e:
+            m.run(1)
+        assert "at most 16384" in str(e.value)
+        m.close()
+
+
+@pytest.mark.parametrize("I,J", [(16384, 3), (3, 16384)])
+def test_rows_and_columns_of_16384_pass_the_limit(I, J):
+    """The limit's own value is accepted: without a GPU the call fails at the device, not at the shape check."""
+    R = np.ones((I, J)); M = np.ones((I, J))
+    n = NMF(R, M, 2, verbose=False)
+    n.U, n.V = np.ones((I, 2)), np.ones((J, 2))
+    try:
+        n.run(1)
+    except BnmtfError as e:
+        assert "at most" not in str(e)
+    n.close()

@@ -1,6 +1,7 @@
 """The non-probabilistic models on the device (csrc/kernel_np.hip): the reference's trajectories (tests/golden/np.npz), its single
 updates, whole iterations at large shapes against a fp64 NumPy restatement written here, long rows and columns, a wide rank,
-the same bits on two runs, and MatrixCrossValidation(method=NMF) against the reference's fold table."""
+the same bits on two runs, and MatrixCrossValidation(method=NMF) against the reference's fold table.  The restatement
+(tests/_np_restatement.py) is pinned to the reference's numbers by tests/test_np_restatement_cpu.py."""
 import os
 import random
 
@@ -9,6 +10,7 @@ import pytest
 
 from bnmtf_amd.nmf_np import NMF
 from bnmtf_amd.nmtf_np import NMTF
+from _np_restatement import ref_nmf_iteration, ref_nmtf_iteration
 
 pytestmark = pytest.mark.gpu
 
@@ -107,24 +109,6 @@ def test_nmtf_update_hooks(name):
 
 
 # ---------------------------------------------------------------- large shapes against a fp64 restatement
-def ref_half(R, M, U, V):
-    """U's columns in order, P moved by each column's change (fp64)."""
-    U = U.copy()
-    P = U @ V.T
-    for k in range(U.shape[1]):
-        Q = np.where(M, R / np.where(M, P, 1.0), 0.0)
-        new = U[:, k] * (Q @ V[:, k]) / (M @ V[:, k])
-        P += np.outer(new - U[:, k], V[:, k])
-        U[:, k] = new
-    return U
-
-
-def ref_nmf_iteration(R, M, U, V):
-    U = ref_half(R, M, U, V)
-    V = ref_half(R.T, M.T, V, U)
-    return U, V
-
-
 def problem(I, J, K, seed, frac=0.5):
     rs = np.random.RandomState(seed)
     U0, V0 = rs.rand(I, K), rs.rand(J, K)
@@ -148,23 +132,6 @@ def test_nmf_iteration_against_restatement(I, J, K):
     close_to_scale(n.U, U); close_to_scale(n.V, V)
     np.testing.assert_allclose(n.all_performances["MSE"][0], masked_mse(R, M, U @ V.T), rtol=1e-4)
     n.close()
-
-
-def ref_nmtf_iteration(R, M, F, S, G):
-    F, S, G = F.copy(), S.copy(), G.copy()
-    P = F @ S @ G.T
-    Mb = M.astype(bool)
-    Q = lambda: np.where(Mb, R / np.where(Mb, P, 1.0), 0.0)      # noqa: E731
-    for k in range(S.shape[0]):
-        for l in range(S.shape[1]):
-            num = F[:, k] @ Q() @ G[:, l]
-            den = F[:, k] @ M @ G[:, l]
-            new = S[k, l] * num / den
-            P += (new - S[k, l]) * np.outer(F[:, k], G[:, l])
-            S[k, l] = new
-    F = ref_half(R, Mb, F, G @ S.T)
-    G = ref_half(R.T, Mb.T, G, F @ S)
-    return F, S, G
 
 
 def test_nmtf_iteration_against_restatement():
