@@ -104,6 +104,7 @@ _SIGS = {
     "bnmtf_np_update": ([_P, C.c_int, C.c_int, C.c_int], C.c_int),
     "bnmtf_np_run": ([_P, C.c_int, _P, _P, _P], C.c_int),
     "bnmtf_np_metrics": ([_P, _P, _P], C.c_int),
+    "bnmtf_np_run_many": ([_P, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -9,7 +9,9 @@ The reference fits the candidates of a model search -- folds x ranks x restarts 
 (bnmf_vb_optimised, any size its 8-wave kernels serve) walk their iterations in lock-step: every kernel of an iteration is ONE
 launch for all of them (csrc/many.h, api_many.inc: bnmf_vb_run_many), each model ending with the bits of its own run().  Models
 wider than 64 columns (column blocks, _blocked.py: several handles per model) of any of these kinds are run by their own run().
-ICM models (nmf_icm: their own run(), update rule and minimum_TN) are not taken: ReplicaPool runs them one by one."""
+The non-probabilistic models (nmf_np.NMF, nmtf_np.NMTF: their run(iterations)) walk their iterations in lock-step too, NMF and
+NMTF of any shapes and ranks together: every launch site of an iteration is ONE launch for all of them (csrc/api_np_many.inc:
+bnmtf_np_run_many).  ICM models (nmf_icm: their own run(), update rule and minimum_TN) are not taken: ReplicaPool runs them one by one."""
 import ctypes as C
 import time
 
@@ -33,6 +35,13 @@ def _kind(model):
     from .bnmf_vb import bnmf_vb_optimised
     if isinstance(model, bnmf_vb_optimised) and type(model).run is bnmf_vb_optimised.run:
         return "vb"
+    from .nmf_np import NMF
+    from .nmtf_np import NMTF
+    # (taken once initialise() has given it its factors: run() of a model without them fails its assertion, run_many refuses it)
+    if isinstance(model, NMF) and type(model).run is NMF.run and all(hasattr(model, f) for f in "UV"):
+        return "np"
+    if isinstance(model, NMTF) and type(model).run is NMTF.run and all(hasattr(model, f) for f in "FSG"):
+        return "np"
     return None
 
 
@@ -41,20 +50,24 @@ def run_many(models, iterations, update='draw', store_samples=True, expectation=
     bnmtf_gibbs_optimised instances), with the models of the one-launch path that share a device and a kind sharing a single
     launch; bnmf_vb_optimised instances (their run(iterations)): the models of a device walk their iterations in lock-step, one
     launch per kernel for all of them (csrc/api_many.inc).  A Gibbs model wider than 64 columns (column blocks) is run by its own
-    run(iterations, update, store_samples, expectation).  Returns the list of the runs' results, in the order of `models`."""
+    run(iterations, update, store_samples, expectation).  NMF / NMTF instances (their run(iterations); update, store_samples and
+    expectation do not apply): the models of a device walk their iterations in lock-step, one launch per launch site for all of
+    them (csrc/api_np_many.inc).  Returns the list of the runs' results, in the order of `models`."""
     models = list(models)
     if not models:
         return []
     if not all(takes(m) for m in models):
         # (nmf_icm inherits the Gibbs class and overrides run(): its update rule, minimum_TN and Gamma mode are not what the
         # batched entry point runs -- it would come back fitted by Gibbs draws)
-        raise TypeError("run_many takes models whose run() is bnmf_gibbs_optimised.run or bnmtf_gibbs_optimised.run (got %s)"
+        raise TypeError("run_many takes models whose run() is bnmf_gibbs_optimised.run, bnmtf_gibbs_optimised.run, "
+                        "bnmf_vb_optimised.run, NMF.run or NMTF.run, the last two initialised (got %s)"
                         % sorted({type(m).__name__ for m in models if not takes(m)}))
     if int(iterations) == 0:                  # run(0) changes nothing (the C entry points return before they fill the final states)
         return [None for _ in models]
     out = [None] * len(models)
     upd = _lib.UPDATE_MODE if update == 'mode' else _lib.UPDATE_DRAW
     _run_many_vb([m for m in models if _kind(m) == "vb"], int(iterations))
+    _run_many_np([m for m in models if _kind(m) == "np"], int(iterations))
     for i, m in enumerate(models):
         if _kind(m) in ("bnmf", "bnmtf") and m._blocks is not None:
             out[i] = m.run(iterations, update, store_samples, expectation)
@@ -105,4 +118,25 @@ def _run_many_vb(ms, it):
         dt = time.perf_counter() - t0
         for i, m in enumerate(group):
             m._run_finish(it, exptau[i], perf[i], terms[i], times[i])
+            m._many_info = (int(info[0]), int(info[1]), dt)     # models that shared launches, argument-list uploads, seconds of the device call
+
+
+def _run_many_np(ms, it):
+    """NMF.run(it) / NMTF.run(it) of every model of `ms` (nmf_np.py:87-107, nmtf_np.py:116-144): per device one bnmtf_np_run_many
+    call, NMF and NMTF together."""
+    by_device = {}
+    for m in ms:
+        by_device.setdefault(m._device, []).append(m)
+    for group in by_device.values():
+        n = len(group)
+        for m in group:
+            m._run_prepare(it)
+        hs = (C.c_void_p * n)(*[m._handle().value for m in group])
+        perf = np.zeros((n, it, 3)); idiv = np.zeros((n, it)); times = np.zeros((n, it))
+        info = np.zeros(2, dtype=np.int32)
+        t0 = time.perf_counter()
+        _lib.check(_lib.lib().bnmtf_np_run_many(hs, n, it, _lib.ptr(perf), _lib.ptr(idiv), _lib.ptr(times), _lib.ptr(info)))
+        dt = time.perf_counter() - t0
+        for i, m in enumerate(group):
+            m._run_finish(it, perf[i], idiv[i], times[i])
             m._many_info = (int(info[0]), int(info[1]), dt)     # models that shared launches, argument-list uploads, seconds of the device call

@@ -17,13 +17,71 @@ import json
 import numpy
 
 from . import mask
-from .replicas import ReplicaError, ReplicaPool, _accepts
+from .replicas import JobFailed, ReplicaError, ReplicaPool, _accepts
 
 attempts_generate_M = 1000
 
 
 def fold_job(job, shared):
     """One fold on the worker's GPU: `method(X, train, **parameters).train(**train_config).predict(test)` (:85-88)."""
+    model = _fold_model(job, shared)
+    try:
+        model.train(**job["train_config"])
+        return model.predict(job["test"])
+    finally:
+        if hasattr(model, "close"):
+            model.close()
+
+
+def _np_trains(method):
+    """Does `method` train as the non-probabilistic base class does (initialise, then its own run)?"""
+    from ..nmf_np import NMF
+    from ..nmtf_np import NMTF
+    return any(isinstance(method, type) and issubclass(method, c) and method.train is c.train and method.run is c.run for c in (NMF, NMTF))
+
+
+def fold_jobs(jobs, shared):
+    """fold_job of every job, results in job order (a batched ReplicaPool's form of it).  The folds of a method that trains as
+    nmf_np.NMF / nmtf_np.NMTF do are built and initialised in job order (train_config without `iterations`, each job's seeds set
+    first), then run as ONE bnmtf_amd.run_many per iteration count, and each is scored with predict(test); every other job runs
+    fold_job, in its place in the job order.  The global NumPy / `random` draws (initialise only) come in the serial order: the
+    results are fold_job's, bit for bit.  A job that raises comes back as a JobFailed in its place."""
+    from ..batch import run_many
+    out = [None] * len(jobs)
+    fits = {}                                    # iterations -> [(job index, model)]
+    for i, job in enumerate(jobs):
+        try:
+            if not _np_trains(job["method"]):
+                out[i] = fold_job(job, shared)
+                continue
+            cfg = dict(job["train_config"])
+            iterations = cfg.pop("iterations")
+            model = _fold_model(job, shared)
+            try:
+                model.initialise(**cfg)
+            except BaseException:
+                model.close()
+                raise
+            fits.setdefault(int(iterations), []).append((i, model))
+        except Exception as e:      # noqa: BLE001 -- reported in the job's place
+            out[i] = JobFailed(e)
+    for iterations, group in fits.items():
+        try:
+            run_many([m for _, m in group], iterations)
+            for i, m in group:
+                out[i] = m.predict(jobs[i]["test"])
+        except Exception as e:      # noqa: BLE001 -- every job of the call reports it
+            for i, _ in group:
+                if out[i] is None:
+                    out[i] = JobFailed(e)
+        finally:
+            for _, m in group:
+                m.close()
+    return out
+
+
+def _fold_model(job, shared):
+    """The model of one fold, constructed (the job's seeds set first)."""
     method = job["method"]
     kw = dict(job["parameters"])
     if job.get("seed") is not None:              # (an extension: the reference's folds draw from the process's global streams, :85-88)
@@ -35,13 +93,7 @@ def fold_job(job, shared):
         kw["device"] = job.get("device", 0)
     if _accepts(method.__init__, "verbose"):
         kw.setdefault("verbose", False)
-    model = method(shared["X"], job["train"], **kw)
-    try:
-        model.train(**job["train_config"])
-        return model.predict(job["test"])
-    finally:
-        if hasattr(model, "close"):
-            model.close()
+    return method(shared["X"], job["train"], **kw)
 
 
 class _Setting(object):
@@ -52,11 +104,14 @@ class _Setting(object):
 
 
 class MatrixCrossValidation(object):
-    def __init__(self, method, X, M, K, parameter_search, train_config, file_performance, *, devices=None, seed=None):
+    def __init__(self, method, X, M, K, parameter_search, train_config, file_performance, *, devices=None, seed=None, batched=False):
         """seed (not in the reference): every fold job seeds NumPy's and Python's global streams -- and the model's sampler -- with
-        seed + its index before it builds its model; the folds run in worker processes, whose streams are otherwise their own."""
+        seed + its index before it builds its model; the folds run in worker processes, whose streams are otherwise their own.
+        batched (not in the reference): a slot fits the folds it is dealt together (ReplicaPool(batched=True), fold_jobs: the
+        non-probabilistic models in one device call) -- the same results as one by one."""
         self.method = method
         self.seed = seed
+        self.batched = bool(batched)
         self.X = numpy.array(X, dtype=float)
         self.M = numpy.array(M)
         self.K = K
@@ -98,7 +153,7 @@ class MatrixCrossValidation(object):
                 owner.append(si)
         if not jobs:
             return
-        with ReplicaPool(devices=self.devices, shared={"X": self.X}) as pool:
+        with ReplicaPool(devices=self.devices, shared={"X": self.X}, batched=self.batched) as pool:
             out = pool.map(fold_job, jobs, errors="return")
         for setting in plan:
             setting.results = []

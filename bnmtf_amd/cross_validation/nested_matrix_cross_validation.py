@@ -17,8 +17,12 @@ attempts_generate_M = 1000
 
 
 class MatrixNestedCrossValidation(object):
-    def __init__(self, method, X, M, K, P, parameter_search, train_config, file_performance, files_nested_performances, *, devices=None):
+    def __init__(self, method, X, M, K, P, parameter_search, train_config, file_performance, files_nested_performances, *, devices=None,
+                 batched=False):
+        """batched (not in the reference): the inner searches and the outer models fit the folds of a slot together
+        (MatrixCrossValidation's batched) -- the same results as one by one."""
         self.method = method
+        self.batched = bool(batched)
         self.X = numpy.array(X, dtype=float)
         self.M = numpy.array(M)
         self.K = K
@@ -48,7 +52,7 @@ class MatrixNestedCrossValidation(object):
             print("Fold %s of nested cross-validation." % (i + 1))
             crossval = ParallelMatrixCrossValidation(method=self.method, X=self.X, M=train, K=self.K, parameter_search=self.parameter_search,
                                                      train_config=self.train_config, file_performance=self.files_nested_performances[i],
-                                                     P=self.P, devices=self.devices)
+                                                     P=self.P, devices=self.devices, batched=self.batched)
             crossval.run()
             try:
                 (best_parameters, _) = crossval.find_best_parameters(evaluation_criterion='MSE', low_better=True)
@@ -65,7 +69,7 @@ class MatrixNestedCrossValidation(object):
         if type(self).run_model is not MatrixNestedCrossValidation.run_model:
             results = [self.run_model(train, test, p) for p, train, test in zip(chosen, folds_training, folds_test)]
         else:
-            with ReplicaPool(devices=devices, shared={"X": self.X}) as pool:
+            with ReplicaPool(devices=devices, shared={"X": self.X}, batched=self.batched) as pool:
                 results = pool.map(fold_job, jobs)
         for i, performance_dict in enumerate(results):
             self.store_performances(performance_dict)

@@ -5,10 +5,11 @@ from .matrix_cross_validation import MatrixCrossValidation
 
 
 class ParallelMatrixCrossValidation(MatrixCrossValidation):
-    def __init__(self, method, X, M, K, parameter_search, train_config, file_performance, P, *, devices=None, seed=None):
+    def __init__(self, method, X, M, K, parameter_search, train_config, file_performance, P, *, devices=None, seed=None, batched=False):
         if devices is None:
             from .replicas import visible_devices
             n = max(visible_devices(), 1)
             devices = [p % n for p in range(P)]
-        MatrixCrossValidation.__init__(self, method, X, M, K, parameter_search, train_config, file_performance, devices=devices, seed=seed)
+        MatrixCrossValidation.__init__(self, method, X, M, K, parameter_search, train_config, file_performance, devices=devices, seed=seed,
+                                       batched=batched)
         self.P = P

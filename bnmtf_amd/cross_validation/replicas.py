@@ -60,7 +60,8 @@ class ReplicaPool(object):
         """devices: list of device ordinals, one worker each (repeat an ordinal to run several models on one GPU at
         once); default: every visible GPU once.  shared: dict handed to every worker once (e.g. the data matrix R),
         so that jobs only carry what differs between them.  batched: a slot fits ALL the model-fit jobs it is dealt in
-        one device call (bnmtf_amd.run_many: small models share a launch, one block each) instead of one after the other."""
+        one device call (bnmtf_amd.run_many: small models share a launch, one block each) instead of one after the other; the
+        cross-validation folds of map(fold_job, ...) go through fold_jobs, which fits the non-probabilistic models of a share so."""
         if devices is None:
             n = visible_devices()
             devices = list(range(max(n, 1)))
@@ -89,8 +90,10 @@ class ReplicaPool(object):
         any job is raised here (after all jobs have run) with the worker's traceback -- or, with errors="return", comes
         back in the job's place as a ReplicaError (a caller that logs a failed setting and carries on)."""
         jobs = list(jobs)
-        if self.batched and fn is fit_model and jobs:
-            out = self._map_batched(jobs)
+        from .matrix_cross_validation import fold_job, fold_jobs
+        batch_fn = {fit_model: fit_models, fold_job: fold_jobs}.get(fn) if self.batched and jobs else None
+        if batch_fn is not None:
+            out = self._map_batched(batch_fn, jobs)
         elif len(self.devices) <= 1:                    # single slot: in this process, like the reference's serial loops
             _worker_device[0] = self.devices[0] if self.devices else 0
             _worker_shared.clear(); _worker_shared.update(self.shared)
@@ -103,17 +106,17 @@ class ReplicaPool(object):
             raise RuntimeError("%d of %d replica jobs failed; first:\n%s" % (len(errs), len(jobs), errs[0]))
         return [ReplicaError(r[1]) if r[0] == "error" else r[1] for r in out]
 
-    def _map_batched(self, jobs):
-        """Every slot gets a contiguous share of the jobs and fits it as one batch."""
+    def _map_batched(self, batch_fn, jobs):
+        """Every slot gets a share of the jobs (every ns-th) and fits it as one batch: batch_fn(jobs, shared)."""
         ns = max(len(self.devices), 1)
         shares = [list(range(len(jobs)))[i::ns] for i in range(ns)]
         if ns == 1:
             _worker_device[0] = self.devices[0] if self.devices else 0
             _worker_shared.clear(); _worker_shared.update(self.shared)
-            parts = [_call_batch([jobs[i] for i in shares[0]])]
+            parts = [_call_batch((batch_fn, [jobs[i] for i in shares[0]]))]
         else:
             self._start()
-            parts = self._pool.map(_call_batch, [[jobs[i] for i in sh] for sh in shares], chunksize=1)
+            parts = self._pool.map(_call_batch, [(batch_fn, [jobs[i] for i in sh]) for sh in shares], chunksize=1)
         out = [None] * len(jobs)
         for sh, part in zip(shares, parts):
             for i, r in zip(sh, part):
@@ -190,9 +193,17 @@ class _Joint(object):
         pass
 
 
-def _call_batch(jobs):
+class JobFailed(object):
+    """In a batch function's results: the job raised (the worker reports it in the job's place, as _call does)."""
+    def __init__(self, e):
+        self.msg = "%s: %s\n%s" % (type(e).__name__, e, "".join(traceback.format_exception(type(e), e, e.__traceback__)))
+
+
+def _call_batch(args):
+    batch_fn, jobs = args
     try:
-        return [("ok", r) for r in fit_models([dict(j, device=_worker_device[0]) for j in jobs], _worker_shared)]
+        res = batch_fn([dict(j, device=_worker_device[0]) for j in jobs], _worker_shared)
+        return [("error", r.msg) if isinstance(r, JobFailed) else ("ok", r) for r in res]
     except Exception as e:      # noqa: BLE001 -- one failure fails the share: every job of it reports it
         msg = "%s: %s\n%s" % (type(e).__name__, e, traceback.format_exc())
         return [("error", msg) for _ in jobs]

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <mutex>
 #include <exception>
+#include <map>
 #include <new>
 #include <system_error>
 #include <thread>
@@ -603,6 +604,7 @@ static void enqueue_gemm(bnmtf_model* h, Dir& d, const Dir& other, int kid, int 
 // [other.n0, other.n0 + other.n): final the moment the rank's sweep ends, before any exchange); 2 the remaining slices
 static void enqueue_gemm(bnmtf_model* h, Dir& d, const Dir& other, int kid, int part) {
   GemmArgs g;
+  memset(&g, 0, sizeof(g));                              // (padding too: a recorded list compares argument bytes)
   g.big = d.big; g.ld = d.n_pad; g.X = other.X; g.slabs = d.slabs;
   g.n_pad = d.n_pad; g.split = d.split; g.inner_per_wave = d.ipw; g.tw = d.gemm_tw;
   const int rows_per_slice = 4 * d.ipw;
@@ -1773,3 +1775,4 @@ int bnmtf_gamma_sample(double alpha, double beta, uint64_t seed, uint64_t it, in
 #include "api_trivb.inc"
 #include "api_many.inc"
 #include "api_np.inc"
+#include "api_np_many.inc"

@@ -28,27 +28,31 @@ struct ManySite {
   ~ManySite() { if (dev) (void)hipFree(dev); }
 };
 
-// the records of one iteration, site by site: the models whose record of a site agrees in kernel, block and grid (grid.x too
-// unless the kernel leaves by its own block count) share a launch.  Argument lists live in device memory and are uploaded again
-// only when their bytes change (a variational iteration's arguments do not, after the first).
-int launch_recorded(std::vector<Recorder>& recs, std::vector<std::unique_ptr<ManySite>>& sites, int it, hipStream_t st, long* uploads) {
-  const size_t nm = recs.size(), ns = recs[0].recs.size();
-  for (size_t m = 1; m < nm; ++m)
-    if (recs[m].recs.size() != ns) { set_error("run_many: model %d enqueues %d launches an iteration, model 0 %d", (int)m, (int)recs[m].recs.size(), (int)ns); return BNMTF_ESTATE; }
+// The launch sites of one iteration: at[s] lists (model, record index) of the models that have a record at site s, in model
+// order.  Of a site, the models whose records agree in kernel, block and grid (grid.x too unless the kernel leaves by its own
+// block count) share a launch.  Argument lists live in device memory and are uploaded again only when their bytes change (a
+// variational iteration's arguments do not, after the first).
+typedef std::vector<std::vector<std::pair<int, int>>> SiteMembers;
+int launch_sites(std::vector<Recorder>& recs, const SiteMembers& at, std::vector<std::unique_ptr<ManySite>>& sites, int it, hipStream_t st,
+                 long* uploads) {
+  const size_t nm = recs.size(), ns = at.size();
   if (sites.size() < ns * nm) { const size_t old = sites.size(); sites.resize(ns * nm); for (size_t i = old; i < sites.size(); ++i) sites[i] = std::make_unique<ManySite>(); }
-  std::vector<char> done(nm);
+  std::vector<char> done;
   std::vector<int> members;
   for (size_t s = 0; s < ns; ++s) {
-    std::fill(done.begin(), done.end(), 0);
+    const auto& here = at[s];
+    auto rec = [&](size_t q) -> const LaunchRec& { return recs[here[q].first].recs[here[q].second]; };
+    auto args = [&](size_t q) { return recs[here[q].first].args(rec(q)); };
+    done.assign(here.size(), 0);
     int part = 0;
-    for (size_t m0 = 0; m0 < nm; ++m0) {
+    for (size_t m0 = 0; m0 < here.size(); ++m0) {
       if (done[m0]) continue;
-      const LaunchRec& r0 = recs[m0].recs[s];
+      const LaunchRec& r0 = rec(m0);
       unsigned gx = r0.grid.x; size_t lds = r0.lds;
       members.clear();
-      for (size_t m = m0; m < nm; ++m) {
+      for (size_t m = m0; m < here.size(); ++m) {
         if (done[m]) continue;
-        const LaunchRec& r = recs[m].recs[s];
+        const LaunchRec& r = rec(m);
         const bool same = r.fn == r0.fn && r.block.x == r0.block.x && r.block.y == r0.block.y && r.block.z == r0.block.z && r.grid.y == r0.grid.y &&
                           r.grid.z == 1 && r.size == r0.size && r.flex == r0.flex && (r.flex || r.grid.x == r0.grid.x);
         if (!same || members.size() == 65535) continue;
@@ -59,11 +63,11 @@ int launch_recorded(std::vector<Recorder>& recs, std::vector<std::unique_ptr<Man
       const size_t sz = r0.size, total = sz * members.size();
       bool changed = site.last.size() != total;
       for (size_t k = 0; k < members.size() && !changed; ++k)
-        changed = memcmp(site.last.data() + k * sz, recs[members[k]].args(recs[members[k]].recs[s]), sz) != 0;
+        changed = memcmp(site.last.data() + k * sz, args(members[k]), sz) != 0;
       if (changed) {
         if (getenv("BNMTF_MANY_DEBUG")) fprintf(stderr, "many: it %d site %d part %d: argument list of %zu models uploaded\n", it, (int)s, part - 1, members.size());
         site.last.resize(total);
-        for (size_t k = 0; k < members.size(); ++k) memcpy(site.last.data() + k * sz, recs[members[k]].args(recs[members[k]].recs[s]), sz);
+        for (size_t k = 0; k < members.size(); ++k) memcpy(site.last.data() + k * sz, args(members[k]), sz);
         HIPCHK(hipStreamSynchronize(st));              // (a launch in flight may still read the old list)
         if (site.cap < total) { if (site.dev) (void)hipFree(site.dev); site.dev = nullptr; site.cap = 0; HIPCHK(hipMalloc(&site.dev, total)); site.cap = total; }
         HIPCHK(hipMemcpy(site.dev, site.last.data(), total, hipMemcpyHostToDevice));
@@ -75,6 +79,17 @@ int launch_recorded(std::vector<Recorder>& recs, std::vector<std::unique_ptr<Man
     }
   }
   return BNMTF_OK;
+}
+
+// the records of one iteration, site by site: every model enqueues the same launches in the same order (the variational path)
+int launch_recorded(std::vector<Recorder>& recs, std::vector<std::unique_ptr<ManySite>>& sites, int it, hipStream_t st, long* uploads) {
+  const size_t nm = recs.size(), ns = recs[0].recs.size();
+  for (size_t m = 1; m < nm; ++m)
+    if (recs[m].recs.size() != ns) { set_error("run_many: model %d enqueues %d launches an iteration, model 0 %d", (int)m, (int)recs[m].recs.size(), (int)ns); return BNMTF_ESTATE; }
+  SiteMembers at(ns);
+  for (size_t s = 0; s < ns; ++s)
+    for (size_t m = 0; m < nm; ++m) at[s].push_back({(int)m, (int)s});
+  return launch_sites(recs, at, sites, it, st, uploads);
 }
 
 struct RecorderScope {

@@ -739,6 +739,7 @@ static int enqueue_vb_iteration(bnmtf_model* h, int it, bool recording) {
   int sweep_blocks = 0;
   { ScopedKernelTimer t(h, BNMTF_KERNEL_SWEEP_COLS); enqueue_vb_sweep(h, c, r, kStreamCols, true, h->comm ? nullptr : &sweep_blocks); }
   VbFinishArgs f;
+  memset(&f, 0, sizeof(f));                              // (padding too: a recorded list compares argument bytes)
   f.extra = nullptr; f.n_extra = 0;
   f.sweep_stats = sweep_blocks > 0 ? c.stats : nullptr; f.n_sweep_stats = sweep_blocks;
   f.acc = h->acc; f.stats_r = r.vb_stats; f.nr = r.vb_stat_rows; f.stats_c = c.vb_stats; f.nc = c.vb_stat_rows;

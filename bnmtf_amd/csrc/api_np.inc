@@ -69,7 +69,7 @@ static void np_perf(const double* s, double* perf) {
 // the half sweep of the rows (U / F: other factor Yt [W][J]) or of the columns (V / G: other factor Yt [W][I]), columns [k0, k1)
 static void np_enqueue_sweep(bnmtf_model* h, bool rows, float* Xt, const float* Yt, int W, int k0, int k1, double* stats_out) {
   NpState* s = h->np;
-  NpSweepArgs a;
+  NpSweepArgs a; memset(&a, 0, sizeof(a));                   // (padding too: a recorded list compares argument bytes)
   a.Rn = rows ? s->Rn : s->RnT; a.n = rows ? h->I : h->J; a.m = rows ? h->J : h->I;
   a.Xt = Xt; a.Yt = Yt; a.K = W; a.k0 = k0; a.k1 = k1;
   a.stats = stats_out ? s->part : nullptr;
@@ -81,15 +81,29 @@ static void np_enqueue_sweep(bnmtf_model* h, bool rows, float* Xt, const float* 
 static void np_gst(bnmtf_model* h) { NpState* s = h->np; launch_np_small_product(s->S, h->L, 1, s->Xc, h->L, h->K, h->J, s->Y, h->stream); }
 static void np_fs(bnmtf_model* h) { NpState* s = h->np; launch_np_small_product(s->S, 1, h->L, s->Xr, h->K, h->L, h->I, s->Y, h->stream); }
 
+// While a Recorder is installed (api_np_many.inc), the site key (phase, index) of every record: the records of the models of a
+// batch are aligned by key -- phase 0 before the S step, phase 1 its passes (index = pass), phase 2 after it -- not by position.
+struct NpSiteKeys {
+  std::vector<std::pair<int, int>> key;
+  static void mark(NpSiteKeys* k, int phase, int index) {
+    if (k && g_recorder) while (k->key.size() < g_recorder->recs.size()) k->key.push_back({phase, index++});
+  }
+};
+
 // S entries [e0, e1) in row-major order (nmtf_np.py:127-129 for the whole range), one pass per entry plus one that finishes
-// the last; S2 receives the new values and becomes S
-static int np_s_step(bnmtf_model* h, int e0, int e1) {
+// the last; S2 receives the new values and becomes S.  Recorded (the whole range only): no copy of S into S2 beforehand --
+// the passes finish every entry -- and S2 is copied back into S instead of the swap, so that the arguments of every
+// iteration are the same.
+static int np_s_step(bnmtf_model* h, int e0, int e1, NpSiteKeys* keys = nullptr) {
   NpState* s = h->np;
   const int nb = np_s_blocks(h->I);
+  const bool recording = g_recorder != nullptr;
+  if (recording && (e0 != 0 || e1 != h->K * h->L)) { set_error("np_s_step: a recorded S step covers all of S"); return BNMTF_ESTATE; }
   np_gst(h);
   launch_np_build_p(s->Rn, s->Xr, s->Y, h->I, h->J, h->K, s->P, h->stream);
-  HIPCHK(hipMemcpyAsync(s->S2, s->S, (size_t)h->K * h->L * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-  NpSPassArgs a;
+  NpSiteKeys::mark(keys, 0, 0);
+  if (!recording) HIPCHK(hipMemcpyAsync(s->S2, s->S, (size_t)h->K * h->L * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  NpSPassArgs a; memset(&a, 0, sizeof(a));
   a.Rn = s->Rn; a.P = s->P; a.Ft = s->Xr; a.Gt = s->Xc; a.S_in = s->S; a.S_out = s->S2;
   a.I = h->I; a.J = h->J; a.K = h->K; a.L = h->L;
   for (int e = e0; e <= e1; ++e) {
@@ -98,23 +112,31 @@ static int np_s_step(bnmtf_model* h, int e0, int e1) {
     a.part_prev = s->spart + (size_t)((e + 1) & 1) * nb * 2;
     a.part_cur = s->spart + (size_t)(e & 1) * nb * 2;
     launch_np_s_pass(a, h->stream);
+    NpSiteKeys::mark(keys, 1, e - e0);
   }
-  std::swap(s->S, s->S2);
+  if (recording) record_np_copy(s->S2, s->S, h->K * h->L);
+  else std::swap(s->S, s->S2);
+  NpSiteKeys::mark(keys, 2, 0);
   return BNMTF_OK;
 }
 
-static int np_iteration(bnmtf_model* h, double* stats_out) {
+// One iteration on h->stream -- or, while a Recorder is installed, into its records with their site keys (stats_out: then the
+// run's first record; the list-form end-of-iteration kernel finds the iteration's own).
+static int np_iteration(bnmtf_model* h, double* stats_out, NpSiteKeys* keys = nullptr) {
   NpState* s = h->np;
   if (h->L == 0) {                                            // nmf_np.py:95-98
     np_enqueue_sweep(h, true, s->Xr, s->Xc, h->K, 0, h->K, nullptr);
+    NpSiteKeys::mark(keys, 2, 2);                             // (the sites of NMTF's F and G sweeps)
     np_enqueue_sweep(h, false, s->Xc, s->Xr, h->K, 0, h->K, stats_out);
+    NpSiteKeys::mark(keys, 2, 4);
     return BNMTF_OK;
   }
-  CHK(np_s_step(h, 0, h->K * h->L));                          // nmtf_np.py:127-135
+  CHK(np_s_step(h, 0, h->K * h->L, keys));                    // nmtf_np.py:127-135
   np_gst(h);
   np_enqueue_sweep(h, true, s->Xr, s->Y, h->K, 0, h->K, nullptr);
   np_fs(h);
   np_enqueue_sweep(h, false, s->Xc, s->Y, h->L, 0, h->L, stats_out);
+  NpSiteKeys::mark(keys, 2, 1);
   return BNMTF_OK;
 }
 

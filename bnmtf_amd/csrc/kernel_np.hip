@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "kernels.h"
+#include "many.h"
 
 namespace bnmtf {
 
@@ -75,8 +76,9 @@ __device__ void np_block_stats(double* s, double* out) {
   }
 }
 
+// The half sweep of the RB rows from blockIdx.x * RB (np_sweep_kernel, and np_sweep_many for a model of a list).
 template <int E, int RB>
-__global__ __launch_bounds__(1024) void np_sweep_kernel(NpSweepArgs a) {
+__device__ __forceinline__ void np_sweep_body(const NpSweepArgs& a) {
   extern __shared__ float xs[];                               // [RB][K] the block's rows of X
   __shared__ float red[kNpMaxWaves][2 * RB];
   __shared__ float delta[RB];
@@ -160,6 +162,17 @@ __global__ __launch_bounds__(1024) void np_sweep_kernel(NpSweepArgs a) {
   }
 }
 
+template <int E, int RB>
+__global__ __launch_bounds__(1024) void np_sweep_kernel(NpSweepArgs a) { np_sweep_body<E, RB>(a); }
+
+// list form (many.h): blockIdx.z = model; grid.x is the largest block count of the launch, a model's surplus blocks leave
+template <int E, int RB>
+__global__ __launch_bounds__(1024) void np_sweep_many(const NpSweepArgs* list, int) {
+  const NpSweepArgs a = load_pack(list, blockIdx.z);
+  if ((int)blockIdx.x * RB >= a.n) return;
+  np_sweep_body<E, RB>(a);
+}
+
 // Configuration of a half sweep over n units of inner extent m: E entries per thread and row, T threads, RB rows per block
 // (E RB = 32 values of R and of P per thread; 16 for the longest rows, whose 1 024-thread blocks leave 128 registers a lane).
 static void np_sweep_shape(int m, int* E, int* T, int* RB) {
@@ -187,6 +200,12 @@ void launch_np_sweep(const NpSweepArgs& a, hipStream_t st) {
   np_sweep_shape(a.m, &E, &T, &RB);
   const int nb = (a.n + RB - 1) / RB;
   const size_t lds = (size_t)RB * a.K * sizeof(float);
+  if (g_recorder) {
+    const void* fn = E == 2 ? (const void*)np_sweep_many<2, 16> : E == 4 ? (const void*)np_sweep_many<4, 8>
+                   : E == 8 ? (const void*)np_sweep_many<8, 4> : (const void*)np_sweep_many<16, 1>;
+    record_launch(fn, dim3(nb), dim3(T), lds, a, true);
+    return;
+  }
   switch (E) {
     case 2: np_sweep_kernel<2, 16><<<nb, T, lds, st>>>(a); break;
     case 4: np_sweep_kernel<4, 8><<<nb, T, lds, st>>>(a); break;
@@ -201,7 +220,7 @@ void launch_np_prepare(const float* R, const uint8_t* M, int I, int J, float* Rn
 }
 
 // out[8] = sums over the nb rows of part[nb][8], each in a fixed order (one block).
-__global__ __launch_bounds__(256) void np_stats_finish_kernel(const double* __restrict__ part, int nb, double* __restrict__ out) {
+__device__ __forceinline__ void np_stats_finish_body(const double* __restrict__ part, int nb, double* __restrict__ out) {
   __shared__ double red[256];
   for (int v = 0; v < 8; ++v) {
     double s = 0.0;
@@ -216,15 +235,30 @@ __global__ __launch_bounds__(256) void np_stats_finish_kernel(const double* __re
     __syncthreads();
   }
 }
+__global__ __launch_bounds__(256) void np_stats_finish_kernel(const double* __restrict__ part, int nb, double* __restrict__ out) {
+  np_stats_finish_body(part, nb, out);
+}
+// list form: out = the run's FIRST record, the iteration's one is `it` records behind it (the argument list stays the same)
+struct NpStatsFinishPack { const double* part; double* out; int nb, pad; };
+__global__ __launch_bounds__(256) void np_stats_finish_many(const NpStatsFinishPack* list, int it) {
+  const NpStatsFinishPack p = load_pack(list, blockIdx.z);
+  np_stats_finish_body(p.part, p.nb, p.out + (size_t)it * 8);
+}
 
 void launch_np_stats_finish(const double* part, int nb, double* out, hipStream_t st) {
+  if (g_recorder) {                                           // (recording: the caller passes the run's first record)
+    NpStatsFinishPack p; memset(&p, 0, sizeof(p));
+    p.part = part; p.out = out; p.nb = nb;
+    record_launch((const void*)np_stats_finish_many, dim3(1), dim3(256), 0, p);
+    return;
+  }
   np_stats_finish_kernel<<<1, 256, 0, st>>>(part, nb, out);
 }
 
 // out[c][x] = sum_a S[c sc + a sa] in[a][x]  (c < C, a < A, x < n): G S^T as [K][J] (sc = L, sa = 1) or (F S)^T as [L][I]
 // (sc = 1, sa = L).  S is [K][L] row major.
-__global__ __launch_bounds__(256) void np_small_product_kernel(const float* __restrict__ S, int sc, int sa, const float* __restrict__ in,
-                                                               int A, int C, int n, float* __restrict__ out) {
+__device__ __forceinline__ void np_small_product_body(const float* __restrict__ S, int sc, int sa, const float* __restrict__ in,
+                                                      int A, int C, int n, float* __restrict__ out) {
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (size_t)C * n) return;
   const int c = (int)(idx / n), x = (int)(idx - (size_t)c * n);
@@ -232,16 +266,30 @@ __global__ __launch_bounds__(256) void np_small_product_kernel(const float* __re
   for (int q = 0; q < A; ++q) s = fmaf(S[c * sc + q * sa], in[(size_t)q * n + x], s);
   out[idx] = s;
 }
+__global__ __launch_bounds__(256) void np_small_product_kernel(const float* __restrict__ S, int sc, int sa, const float* __restrict__ in,
+                                                               int A, int C, int n, float* __restrict__ out) {
+  np_small_product_body(S, sc, sa, in, A, C, n, out);
+}
+struct NpProductPack { const float* S; const float* in; float* out; int sc, sa, A, C, n, pad; };
+__global__ __launch_bounds__(256) void np_small_product_many(const NpProductPack* list, int) {      // (surplus blocks: idx >= C n)
+  const NpProductPack p = load_pack(list, blockIdx.z);
+  np_small_product_body(p.S, p.sc, p.sa, p.in, p.A, p.C, p.n, p.out);
+}
 
 void launch_np_small_product(const float* S, int sc, int sa, const float* in, int A, int C, int n, float* out, hipStream_t st) {
   const size_t tot = (size_t)C * n;
+  if (g_recorder) {
+    NpProductPack p; memset(&p, 0, sizeof(p));
+    p.S = S; p.in = in; p.out = out; p.sc = sc; p.sa = sa; p.A = A; p.C = C; p.n = n;
+    record_launch((const void*)np_small_product_many, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, p, true);
+    return;
+  }
   np_small_product_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(S, sc, sa, in, A, C, n, out);
 }
 
 // P[i][j] = sum_k Ut[k][i] Yt[k][j] on the observed entries (NMTF's S step keeps P in memory).
-__global__ __launch_bounds__(256) void np_build_p_kernel(const float* __restrict__ Rn, const float* __restrict__ Ut, const float* __restrict__ Yt,
-                                                         int I, int J, int K, float* __restrict__ P) {
-  const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+__device__ __forceinline__ void np_build_p_body(const float* __restrict__ Rn, const float* __restrict__ Ut, const float* __restrict__ Yt,
+                                                int I, int J, int K, float* __restrict__ P, int i, int j) {
   if (j >= J) return;
   const size_t o = (size_t)i * J + j;
   const float r = Rn[o];
@@ -250,8 +298,27 @@ __global__ __launch_bounds__(256) void np_build_p_kernel(const float* __restrict
   for (int k = 0; k < K; ++k) s = fmaf(Ut[(size_t)k * I + i], Yt[(size_t)k * J + j], s);
   P[o] = s;
 }
+__global__ __launch_bounds__(256) void np_build_p_kernel(const float* __restrict__ Rn, const float* __restrict__ Ut, const float* __restrict__ Yt,
+                                                         int I, int J, int K, float* __restrict__ P) {
+  np_build_p_body(Rn, Ut, Yt, I, J, K, P, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
+}
+// list form: a one-dimensional grid of I row groups of (J + 255) / 256 blocks each (the models of a launch differ in I and J)
+struct NpBuildPPack { const float* Rn; const float* Ut; const float* Yt; float* P; int I, J, K, pad; };
+__global__ __launch_bounds__(256) void np_build_p_many(const NpBuildPPack* list, int) {
+  const NpBuildPPack p = load_pack(list, blockIdx.z);
+  const int bj = (p.J + 255) / 256;
+  if ((int)blockIdx.x >= p.I * bj) return;
+  const int i = (int)blockIdx.x / bj, jb = (int)blockIdx.x - i * bj;
+  np_build_p_body(p.Rn, p.Ut, p.Yt, p.I, p.J, p.K, p.P, i, jb * 256 + threadIdx.x);
+}
 
 void launch_np_build_p(const float* Rn, const float* Ut, const float* Yt, int I, int J, int K, float* P, hipStream_t st) {
+  if (g_recorder) {
+    NpBuildPPack p; memset(&p, 0, sizeof(p));
+    p.Rn = Rn; p.Ut = Ut; p.Yt = Yt; p.P = P; p.I = I; p.J = J; p.K = K;
+    record_launch((const void*)np_build_p_many, dim3((unsigned)(I * ((J + 255) / 256))), dim3(256), 0, p, true);
+    return;
+  }
   dim3 g((J + 255) / 256, I);
   np_build_p_kernel<<<g, 256, 0, st>>>(Rn, Ut, Yt, I, J, K, P);
 }
@@ -260,10 +327,11 @@ void launch_np_build_p(const float* Rn, const float* Ut, const float* Yt, int I,
 // pass's block partials in the same order, so all agree on its new value -- and moves P by dS F[:, k'] G[:, l']^T, then
 // accumulates entry `cur`'s (if >= 0) numerator sum F_ik G_jl R_ij / P_ij and denominator sum F_ik G_jl over the observed entries.
 // S_in holds the values at the start of the step (read only); S_out receives each entry as it is finished.
-__global__ __launch_bounds__(256) void np_s_pass_kernel(NpSPassArgs a) {
+// (nb: the pass's block count -- the stride of the rows and the number of partials -- gridDim.x of the single-model launch)
+__device__ __forceinline__ void np_s_pass_body(const NpSPassArgs& a, int nb) {
   __shared__ double red[256][2];
   __shared__ float s_delta;
-  const int t = threadIdx.x, nb = gridDim.x;
+  const int t = threadIdx.x;
   const int I = a.I, J = a.J;
   const int kp = a.prev >= 0 ? a.prev / a.L : 0, lp = a.prev >= 0 ? a.prev % a.L : 0;
   if (a.prev >= 0) {
@@ -322,8 +390,32 @@ __global__ __launch_bounds__(256) void np_s_pass_kernel(NpSPassArgs a) {
 
 int np_s_blocks(int I) { return I < 1024 ? I : 1024; }
 
+__global__ __launch_bounds__(256) void np_s_pass_kernel(NpSPassArgs a) { np_s_pass_body(a, gridDim.x); }
+// list form: the model's own block count np_s_blocks(I), its surplus blocks leave
+__global__ __launch_bounds__(256) void np_s_pass_many(const NpSPassArgs* list, int) {
+  const NpSPassArgs a = load_pack(list, blockIdx.z);
+  const int nb = a.I < 1024 ? a.I : 1024;                     // np_s_blocks(I)
+  if ((int)blockIdx.x >= nb) return;
+  np_s_pass_body(a, nb);
+}
+
 void launch_np_s_pass(const NpSPassArgs& a, hipStream_t st) {
+  if (record_launch((const void*)np_s_pass_many, dim3(np_s_blocks(a.I)), dim3(256), 0, a, true)) return;
   np_s_pass_kernel<<<np_s_blocks(a.I), 256, 0, st>>>(a);
+}
+
+// dst[0 .. n) = src[0 .. n): the list form of the S step's device-to-device copy (a copy cannot be recorded)
+struct NpCopyPack { const float* src; float* dst; int n, pad; };
+__global__ __launch_bounds__(256) void np_copy_many(const NpCopyPack* list, int) {
+  const NpCopyPack p = load_pack(list, blockIdx.z);
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q < p.n) p.dst[q] = p.src[q];
+}
+
+void record_np_copy(const float* src, float* dst, int n) {
+  NpCopyPack p; memset(&p, 0, sizeof(p));
+  p.src = src; p.dst = dst; p.n = n;
+  record_launch((const void*)np_copy_many, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, p, true);
 }
 
 // The eight sums of predict() / compute_I_div() for P = Ut^T Yt on the entries of a mask (fp64 per entry; one block per row).

@@ -508,6 +508,7 @@ void launch_np_small_product(const float* S, int sc, int sa, const float* in, in
 void launch_np_build_p(const float* Rn, const float* Ut, const float* Yt, int I, int J, int K, float* P, hipStream_t st);
 int np_s_blocks(int I);
 void launch_np_s_pass(const NpSPassArgs& a, hipStream_t st);
+void record_np_copy(const float* src, float* dst, int n);   // (many.h: a list-form record only) dst[0 .. n) = src[0 .. n)
 void launch_np_metrics(const float* R, const uint8_t* M, const float* Ut, const float* Yt, int I, int J, int K, double* part, hipStream_t st);
 
 }  // namespace bnmtf

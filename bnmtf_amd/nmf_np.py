@@ -97,9 +97,18 @@ class NPDevice(object):
 
     def _run_device(self, fn, iterations):
         it = int(iterations)
-        self._push()
-        perf = np.zeros((it, 3)); idiv = np.zeros(it); times = np.zeros(it)
+        perf, idiv, times = self._run_prepare(it)
         _lib.check(fn(self._handle(), it, _lib.ptr(perf), _lib.ptr(idiv), _lib.ptr(times)))
+        return self._run_finish(it, perf, idiv, times)
+
+    def _run_prepare(self, it):
+        """What run() does before the device call (batch.run_many: before the call that runs this model among others): the
+        factors to the device, the output arrays."""
+        self._push()
+        return np.zeros((it, 3)), np.zeros(it), np.zeros(it)
+
+    def _run_finish(self, it, perf, idiv, times):
+        """What run() does behind the device call."""
         self._pull()
         self.all_times = list(times)
         self.all_performances = {'MSE': list(perf[:, 0]), 'R^2': list(perf[:, 1]), 'Rp': list(perf[:, 2])}
@@ -160,8 +169,11 @@ class NMF(NPDevice):
 
     def run(self, iterations):
         """:87-107.  One device call runs all iterations."""
-        assert hasattr(self, 'U') and hasattr(self, 'V'), "U and V have not been initialised - please run NMF.initialise() first."
+        self._check_initialised()
         self._run_device(_lib.lib().bnmf_np_run, iterations)
+
+    def _check_initialised(self):
+        assert hasattr(self, 'U') and hasattr(self, 'V'), "U and V have not been initialised - please run NMF.initialise() first."
 
     def train(self, iterations, init_UV='random', expo_prior=1.):
         """:111-113."""

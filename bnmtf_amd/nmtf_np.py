@@ -73,9 +73,12 @@ class NMTF(NPDevice):
 
     def run(self, iterations):
         """:116-144.  One device call runs all iterations."""
+        self._check_initialised()
+        self._run_device(_lib.lib().bnmtf_np_run, iterations)
+
+    def _check_initialised(self):
         assert hasattr(self, 'F') and hasattr(self, 'S') and hasattr(self, 'G'), \
             "F, S and G have not been initialised - please run NMTF.initialise() first."
-        self._run_device(_lib.lib().bnmtf_np_run, iterations)
 
     def train(self, iterations, init_S='random', init_FG='random', expo_prior=1.):
         """:148-150."""

@@ -355,6 +355,14 @@ BNMTF_API int bnmtf_np_get_state(bnmtf_handle h, double* F, double* S, double* G
 BNMTF_API int bnmtf_np_update(bnmtf_handle h, int which, int k, int l);
 /* run(n_iter), nmtf_np.py:116-144: per iteration the K L entries of S row by row, the K columns of F, the L columns of G */
 BNMTF_API int bnmtf_np_run(bnmtf_handle h, int n_iter, double* perf_out, double* idiv_out, double* times_out);
+/* run(n_iter) of n_models handles of bnmtf_np_create on one device (NMF and NMTF, any shapes and ranks), walked in lock-step: every
+ * launch site of an iteration -- before the S step, S pass t, after it -- is ONE launch for all of them (csrc/many.h,
+ * api_np_many.inc).  Every model ends with the bits of its own bnmf_np_run / bnmtf_np_run.  Outputs model-major: perf_out
+ * [n_models][n_iter][3], idiv_out [n_models][n_iter], times_out [n_models][n_iter] (the batch's clock); any may be null.
+ * launch_info (optional, 2 ints): the models that shared launches, the argument-list uploads.  Refuses a null handle, one given
+ * twice, handles of several devices and a handle without state. */
+BNMTF_API int bnmtf_np_run_many(bnmtf_handle* hs, int n_models, int n_iter, double* perf_out, double* idiv_out, double* times_out,
+                      int* launch_info);
 /* the current point's sums over the entries of Mp ([I][J] 0/1; null: the training mask), fp64: out[8] = n, sum R, sum R^2,
  * sum P, sum P^2, sum R P, the I-divergence sum R log(R / P) - R + P (nmf_np.py:146-148), sum (R - P)^2 */
 BNMTF_API int bnmtf_np_metrics(bnmtf_handle h, const uint8_t* Mp, double* out);
