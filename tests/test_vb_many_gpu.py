@@ -42,7 +42,8 @@ def _same(a, b):
     [(622, 138, 25, 0.19, s) for s in (2, 3, 4)],                                    # the folds of one rank: one launch per kernel
     [(622, 138, K, 0.19, 5 + i) for i, K in enumerate((15, 20, 25, 30, 15, 20, 25, 30))],      # the line search's ranks together (KP = 32 for all)
     [(300, 200, 8, 0.1, 1), (210, 150, 8, 0.3, 2), (300, 200, 40, 0.1, 3), (64, 500, 5, 0.5, 4)],      # shapes and a 64-wide model: launches split where grids / kernels differ
-], ids=["folds", "ranks", "shapes"])
+    [(2100, 300, 40, 0.1, 6), (700, 300, 40, 0.1, 7), (500, 300, 20, 0.1, 8)],       # the contraction's three list forms in one call: KP = 64 over more than 2048 units (tw = 4), KP = 64 with tw = 2, KP = 32
+], ids=["folds", "ranks", "shapes", "tw4"])
 def test_models_run_together_end_with_the_bits_of_their_own_runs(specs):
     alone = _models(specs); together = _models(specs)
     for m in alone:
