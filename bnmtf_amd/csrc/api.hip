@@ -1221,6 +1221,12 @@ static void describe_model(bnmtf_model* h) {
              h->small->dev.rows.em, h->small->dev.cols.em, h->small->lds_bytes, (int)h->std_built);
     h->description += buf;
   }
+  if (h->L > 0 && h->std_built) {
+    // the dense S system (kernel_ssys.hip): its GEMM's column ranges and the blocks of b -- or the per-row path (on=0)
+    if (h->ssys) snprintf(buf, sizeof(buf), " ssys[on=1 nsplit=%d range=%d bblocks=%d]", h->ss_nsplit, ssys_gemm_range(h->cols.n, h->ss_nsplit), ssys_b_blocks(h->cols.n));
+    else snprintf(buf, sizeof(buf), " ssys[on=0]");
+    h->description += buf;
+  }
 }
 
 // the metric kernel's per-tile partial sums (launch_metric_sums): one buffer per handle, sized by its I x J

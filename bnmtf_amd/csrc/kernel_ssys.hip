@@ -275,7 +275,6 @@ __global__ __launch_bounds__(256) void ssys_gemm_kernel(SSysGemmArgs a) {
 // of BOTH interleaved tiles) -- splits its four fragments (a0, a1, b0, b1) and issues the 24 products; the next step's rows are
 // on their way in a second register set meanwhile.  Ranges are cut at multiples of 16 columns; past a range's end the zero rows
 // behind the arrays are read.  Same tiles, same slab layout, same epilogue as ssys_gemm_kernel.
-__host__ __device__ inline int ssys_gemm_range(int n, int nsplit) { return ((n + nsplit - 1) / nsplit + 15) & ~15; }     // columns per range: a multiple of a step
 __global__ __launch_bounds__(256) void ssys_gemm_bf16_kernel(SSysGemmArgs a) {
   const int lane = threadIdx.x & 63, half = lane >> 5, c = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

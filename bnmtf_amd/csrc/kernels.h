@@ -353,6 +353,7 @@ struct SSysGemmArgs {       // slabs[s][p][r] = sum_{j in range s} Wc[j][p] Gc[j
   float* slabs;                        // [nsplit][tri_padded(K)][tri_padded(L)]
 };
 inline int ssys_gemm_wave_tiles(int K, int L) { return (tri_padded(K) / 64) * (tri_padded(L) / 64); }
+__host__ __device__ inline int ssys_gemm_range(int n, int nsplit) { return ((n + nsplit - 1) / nsplit + 15) & ~15; }     // columns per range of ssys_gemm_bf16_kernel: a multiple of a step
 void launch_ssys_gemm(const SSysGemmArgs& a, hipStream_t st);
 struct SSysBArgs { int n, n0, K, L; const float* slabs; int split, n_pad; const float* G; float* b; };   // b[block][K L]: per 64-column block partials of sum_j Pv_jk G_jl
 inline int ssys_b_blocks(int n) { return (n + 63) / 64 > 0 ? (n + 63) / 64 : 1; }
