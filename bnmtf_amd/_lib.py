@@ -71,6 +71,7 @@ _SIGS = {
     "bnmtf_vb_update": ([_P, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
     "bnmtf_vb_exp_square_diff": ([_P, C.POINTER(C.c_double), _P], C.c_int),
     "bnmtf_vb_run": ([_P, C.c_int, _P, _P, _P, _P, _P], C.c_int),
+    "bnmtf_vb_run_many": ([_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P], C.c_int),
     "bnmtf_kmeans_create": ([_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)], C.c_int),
     "bnmtf_kmeans_destroy": ([_P], C.c_int),
     "bnmtf_kmeans_assign": ([_P, _P, _P, _P, _P], C.c_int),

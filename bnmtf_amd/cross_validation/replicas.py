@@ -279,12 +279,20 @@ def fit_model(job, shared):
 
 
 def fit_models(jobs, shared):
-    """The same for a list of jobs at once: all models are built first, those that bnmtf_amd.run_many takes (BNMF Gibbs) and
-    that ask for the same run (iterations, expectation) go to the device as ONE call -- small models share a launch, one
-    block each --, then every model is scored.  Results in job order, each what fit_model(job) returns."""
+    """The same for a list of jobs at once: all models are built first, those that bnmtf_amd.run_many takes (BNMF / BNMTF Gibbs,
+    the variational models) and that ask for the same run (iterations, expectation) go to the device as ONE call -- small models
+    share a launch, one block each; variational models share every launch of an iteration --, then every model is scored.
+    Results in job order, each what fit_model(job) returns: a tri-factorisation's update orders (bnmtf_vb_optimised draws them
+    from Python's `random`) are drawn right after its model is built, where fit_model's run() would draw them -- after the job's
+    seeds, before the next job's."""
     from ..batch import run_many, takes
-    models = [_build(j, shared) for j in jobs]
-    kws = [_run_kw(j, m) for j, m in zip(jobs, models)]
+    from ..bnmtf_vb import bnmtf_vb_optimised
+    models, kws, orders = [], [], []
+    for j in jobs:
+        m = _build(j, shared)
+        kw = _run_kw(j, m)
+        models.append(m); kws.append(kw)
+        orders.append(m._draw_orders(int(kw[0]["iterations"])) if isinstance(m, bnmtf_vb_optimised) and takes(m) else None)
     groups = {}
     for i, (m, (kw, _)) in enumerate(zip(models, kws)):
         if takes(m) and "minimum_TN" not in kw:                     # (nmf_icm inherits _run_prepare but not the Gibbs run(): one by one)
@@ -292,5 +300,5 @@ def fit_models(jobs, shared):
         else:
             m.run(**kw)
     for (iterations, expectation, store), idx in groups.items():
-        run_many([models[i] for i in idx], iterations, store_samples=store, expectation=expectation)
+        run_many([models[i] for i in idx], iterations, store_samples=store, expectation=expectation, orders=[orders[i] for i in idx])
     return [_score(j, m, sampled) for j, m, (_, sampled) in zip(jobs, models, kws)]

@@ -1780,5 +1780,6 @@ int bnmtf_gamma_sample(double alpha, double beta, uint64_t seed, uint64_t it, in
 #include "api_models.inc"
 #include "api_trivb.inc"
 #include "api_many.inc"
+#include "api_trivb_many.inc"
 #include "api_np.inc"
 #include "api_np_many.inc"

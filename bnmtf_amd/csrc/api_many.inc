@@ -150,6 +150,7 @@ int bnmf_vb_run_many(bnmtf_handle* hs, int n_models, int n_iter, double* exptau_
       recs[i].clear();
       RecorderScope scope(&recs[i]);
       CHK(enqueue_vb_iteration(hs[batch[i]], it, true));
+      if (recs[i].missing) { set_error("run_many: a recorded variational iteration met a kernel without a list form (%s)", recs[i].missing); return BNMTF_ESTATE; }
     }
     CHK(launch_recorded(recs, sites, it, st, &uploads));
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], st));

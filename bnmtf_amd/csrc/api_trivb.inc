@@ -5,6 +5,26 @@
 
 namespace bnmtf {
 
+// While a Recorder is installed (api_trivb_many.inc), the site key (site, index within the site) of every record: the records of
+// the models of a batch are aligned by key, not by position -- a model's first iteration of a call forms R~^T E[F] and the column
+// Grams inside the S system (later ones take them from behind the F sweep), and only K L >= 64 permutes the system for the chain.
+enum TriSite {
+  kTsPv, kTsColGram, kTsGammaPack, kTsSysGemm, kTsSysReduce, kTsSysB, kTsResidual, kTsColsumRows, kTsGemmRows, kTsPermute, kTsChain,
+  kTsProductF, kTsSlabF, kTsSweepF, kTsPostF, kTsColGramsNext, kTsPvNext, kTsProductG, kTsSlabG, kTsSweepG, kTsPostG, kTsThird,
+  kTsFinish, kTsEnd
+};
+struct TriSiteKeys {
+  std::vector<std::pair<int, int>> key;
+  int site = -1, sub = 0;
+  void clear() { key.clear(); site = -1; sub = 0; }
+  // the records made since the last call belong to the site named then; the next ones to `s`
+  static void at(TriSiteKeys* k, int s) {
+    if (!k || !g_recorder) return;
+    while (k->key.size() < g_recorder->recs.size()) k->key.push_back({k->site, k->sub++});
+    k->site = s; k->sub = 0;
+  }
+};
+
 static int ensure_tri(bnmtf_model* h) {
   if (h->tri_ready) return BNMTF_OK;
   if (h->L == 0) { set_error("the tri-factorisation VB calls need a BNMTF handle (L > 0)"); return BNMTF_ESTATE; }
@@ -33,9 +53,11 @@ static int ensure_tri(bnmtf_model* h) {
 static void enqueue_tri_colgrams(bnmtf_model* h) {
   Dir& c = h->cols; Dir& r = h->rows;
   SColGramArgs w;
+  memset(&w, 0, sizeof(w));                              // (padding too: a recorded list compares argument bytes)
   w.n = c.n; w.K = h->K; w.F = r.X; w.varF = r.var; w.Cf64 = r.C64; w.cf_diag_extra = r.colsum2;
   w.slot_ptr = c.slot_ptr; w.idx = c.idx; w.Wc = h->ss_Wc; w.var_obs_out = h->mv_cols;
   GammaPackArgs gp;
+  memset(&gp, 0, sizeof(gp));
   gp.n = 0; gp.n0 = c.n0; gp.L = h->L; gp.G = c.X; gp.varG = c.var; gp.Gc = h->ss_Gc;
   launch_scol_gram(w, gp, h->stream);
   h->tri_w_current = h->tri_mv_cols_current = true;
@@ -43,22 +65,30 @@ static void enqueue_tri_colgrams(bnmtf_model* h) {
 static void enqueue_tri_pv(bnmtf_model* h) {        // slabsS = R~^T E[F]
   Dir& c = h->cols; Dir& r = h->rows;
   GemmArgs g;
+  memset(&g, 0, sizeof(g));
   g.big = c.big; g.ld = c.n_pad; g.X = r.X; g.slabs = h->slabsS; g.n_pad = c.n_pad; g.split = c.split; g.inner_per_wave = c.ipw; g.tw = c.gemm_tw;
   launch_gemm(g, r.KP, h->stream);
 }
-static int enqueue_tri_ssys(bnmtf_model* h, bool pv_current = false) {
+static int enqueue_tri_ssys(bnmtf_model* h, bool pv_current = false, TriSiteKeys* keys = nullptr) {
   Dir& c = h->cols; Dir& r = h->rows;
   const int K = h->K, L = h->L, n2 = K * L;
   if (!pv_current) {
+    TriSiteKeys::at(keys, kTsPv);
     GemmArgs g;
+    memset(&g, 0, sizeof(g));
     g.big = c.big; g.ld = c.n_pad; g.X = r.X; g.slabs = h->slabsS; g.n_pad = c.n_pad; g.split = c.split; g.inner_per_wave = c.ipw; g.tw = c.gemm_tw;
     launch_gemm(g, r.KP, h->stream);                       // Pv = R~^T E[F]
   }
   GammaPackArgs gp;                                         // E[G_jl G_jl'] = E[G_jl] E[G_jl'] + [l = l'] varG_jl
+  memset(&gp, 0, sizeof(gp));
   gp.n = c.n; gp.n0 = c.n0; gp.L = L; gp.G = c.X; gp.varG = c.var; gp.Gc = h->ss_Gc;
-  if (h->tri_w_current) launch_gamma_pack(gp, h->stream);    // (the column Grams of this q(F) were formed behind its sweep: enqueue_tri_colgrams)
-  else {
+  if (h->tri_w_current) {
+    TriSiteKeys::at(keys, kTsGammaPack);
+    launch_gamma_pack(gp, h->stream);    // (the column Grams of this q(F) were formed behind its sweep: enqueue_tri_colgrams)
+  } else {
+    TriSiteKeys::at(keys, kTsColGram);
     SColGramArgs w;
+    memset(&w, 0, sizeof(w));
     w.n = c.n; w.K = K; w.F = r.X; w.varF = r.var; w.Cf64 = r.C64;
     w.cf_diag_extra = r.colsum2;                            // C~f_kk = sum_i (E[F_ik]^2 + varF_ik): the column sums of the second moments
     w.slot_ptr = c.slot_ptr; w.idx = c.idx; w.Wc = h->ss_Wc;
@@ -66,31 +96,41 @@ static int enqueue_tri_ssys(bnmtf_model* h, bool pv_current = false) {
     launch_scol_gram(w, gp, h->stream);
   }
   SSysGemmArgs g;
+  memset(&g, 0, sizeof(g));
   g.n = c.n; g.K = K; g.L = L; g.nsplit = h->ss_nsplit; g.Wc = h->ss_Wc; g.Gc = h->ss_Gc; g.slabs = h->ss_slabs;
+  TriSiteKeys::at(keys, kTsSysGemm);
   launch_ssys_gemm(g, h->stream);
+  TriSiteKeys::at(keys, kTsSysReduce);
   launch_ssys_reduce(h->ss_slabs, h->ss_nsplit, K, L, h->ss_AB, h->stream);
   SSysBArgs b;
+  memset(&b, 0, sizeof(b));
   b.n = c.n; b.n0 = c.n0; b.K = K; b.L = L; b.slabs = h->slabsS; b.split = c.split; b.n_pad = c.n_pad; b.G = c.X; b.b = h->ss_bpart;
+  TriSiteKeys::at(keys, kTsSysB);
   launch_ssys_b(b, h->stream);
   if (h->comm) {
     // several GPUs: (A~, b) of the ranks' column ranges summed with ONE all-reduce (the "K x L Gram" exchange, as bnmtf_gibbs_run's S step)
     launch_ssys_sum_parts(h->ss_bpart, ssys_b_blocks(c.n), (size_t)n2, h->ss_AB + (size_t)n2 * n2, h->stream);
     CHK(comm_allreduce_sum_f32(h->comm, h->ss_AB, n2 * n2 + n2, h->stream));
   }
+  TriSiteKeys::at(keys, kTsResidual);
   launch_ssys_residual(h->ss_AB, h->ss_AB + (size_t)n2 * n2, h->comm ? nullptr : h->ss_bpart, ssys_b_blocks(c.n), h->S, n2, h->ss_r, h->stream);
   return BNMTF_OK;
 }
-static void enqueue_tri_chain(bnmtf_model* h, const int* order_dev, int n_order, int only_params) {
+// order_step (recording): order_dev is the order of the call's first iteration, the list forms add it x order_step
+static void enqueue_tri_chain(bnmtf_model* h, const int* order_dev, int n_order, int only_params, int order_step = 0, TriSiteKeys* keys = nullptr) {
   SSysChainVbArgs a;
+  memset(&a, 0, sizeof(a));
   a.K = h->K; a.L = h->L; a.n_order = n_order; a.only_params = only_params; a.order = order_dev;
   a.A = h->ss_AB; a.r0 = h->ss_r; a.lambdaS = h->lambdaS; a.tau = h->tau_f;
   a.E = h->S; a.var = h->varS; a.mu = h->muS; a.tauq = h->tauS;
   a.Aperm = nullptr;
   if (n_order == h->K * h->L && !only_params && n_order >= 64 && h->ss_Aperm) {      // a whole pass: the system in the pass's order
-    launch_ssys_permute(h->ss_AB, order_dev, n_order, h->ss_Aperm, h->stream);
+    TriSiteKeys::at(keys, kTsPermute);
+    launch_ssys_permute(h->ss_AB, order_dev, n_order, h->ss_Aperm, h->stream, order_step);
     a.Aperm = h->ss_Aperm;
   }
-  launch_ssys_chain_vb(a, h->stream);
+  TriSiteKeys::at(keys, kTsChain);
+  launch_ssys_chain_vb(a, h->stream, order_step);
 }
 
 // everything update_F (which = 0) / update_G (which = 2) needs before its sweep: effective factor (mean, second moment,
@@ -99,6 +139,7 @@ static void enqueue_tri_masked_colsum(bnmtf_model* h, int which, hipStream_t st)
   Dir& d = which == 0 ? h->rows : h->cols;
   Dir& o = which == 0 ? h->cols : h->rows;
   MaskedColsumArgs m;
+  memset(&m, 0, sizeof(m));
   m.n = d.n; m.slot_ptr = d.slot_ptr; m.idx = d.idx; m.V = o.var; m.colsum2 = o.colsum2; m.C64 = o.C64;
   m.out = which == 0 ? h->mv_rows : h->mv_cols;
   launch_masked_colsum(m, st);
@@ -110,6 +151,7 @@ static void enqueue_tri_side_prepare(bnmtf_model* h, int which, int pieces = 7) 
   Dir& e = which == 0 ? h->ceff : h->reff;      // effective factor built from o and S
   if (pieces & 1) {
     SmallProductVbArgs p;
+    memset(&p, 0, sizeof(p));
     p.X = o.X; p.varX = o.var; p.rows = o.nglob; p.S = h->S; p.varS = h->varS; p.K = h->K; p.L = h->L;
     p.transposeS = which == 0 ? 1 : 0; p.out = e.X; p.outS2 = e.S2;
     launch_small_product_vb(p, h->stream);
@@ -132,7 +174,9 @@ static SweepArgs tri_sweep_args(bnmtf_model* h, int which, const int* order_dev)
 // (d.vb_stats, d.vb_stat_rows rows).  Round 6: on the on-chip pair-panel kernel of the BNMF-VB sweep (kernel_sweep_vb.hip, COV)
 // when the direction's slot layout allows it -- the generic kernel (one wave per unit, q in global memory) was 484 us per half
 // sweep at 4096^2, K = L = 32.  want_acc: the three sums of the SSE identity -> h->acc (zeroed by the caller).
-static void enqueue_tri_sweep(bnmtf_model* h, int which, const int* order_dev, bool want_acc, bool one_slab = false, int* stats_blocks = nullptr) {
+// order_step (recording): order_dev is the column order of the call's first iteration, the list form adds it x order_step
+static void enqueue_tri_sweep(bnmtf_model* h, int which, const int* order_dev, bool want_acc, bool one_slab = false, int* stats_blocks = nullptr,
+                              int order_step = 0) {
   if (stats_blocks) *stats_blocks = 0;
   Dir& d = which == 0 ? h->rows : h->cols;
   Dir& e = which == 0 ? h->ceff : h->reff;
@@ -157,7 +201,7 @@ static void enqueue_tri_sweep(bnmtf_model* h, int which, const int* order_dev, b
   f.vb_asq = d.vb_asq; f.vb_vsq = d.vb_vsq;
   f.stats = want_acc ? d.stats : nullptr;
   f.nch = 1; f.ho_rows_total = (int)d.f_slots;      // (no q hand-over: S changes between the G sweep and the next F sweep)
-  launch_sweep_vb(s, f, h->stream);
+  launch_sweep_vb(s, f, h->stream, order_step);
   launch_vb_pieces(d.n, d.n0, d.KP, d.W, d.mu, d.tauq, d.X, d.var, d.lambda, d.vb_asq, d.vb_vsq, d.vb_stats, h->stream);
   d.vb_stat_rows = (d.n + 3) / 4;
   if (want_acc) {
@@ -181,6 +225,141 @@ static int enqueue_tri_sums(bnmtf_model* h) {
     CHK(metric_partials(h, &m.part));
     launch_metric_sums(m, h->stream);
   }
+  return BNMTF_OK;
+}
+
+// BNMTF_TRI_OVERLAP=0: the passes over R~ of an iteration in line instead of beside the S pass (A/B switch)
+static bool tri_overlap(const bnmtf_model* h) {
+  static const bool off = [] { const char* e = getenv("BNMTF_TRI_OVERLAP"); return e && atoi(e) == 0; }();
+  return !off && !h->comm;       // (several GPUs: every rank's passes cover its own rows / columns only; in line)
+}
+
+// One iteration of bnmtf_vb_run (update_S in the order's first K L entries, update_F in the next K, update_G in the last L; update_tau,
+// the metrics, the ELBO's pieces) on h->stream -- or, while a Recorder is installed (api_trivb_many.inc: the caller has checked
+// trivb_batchable), into its records, with the site key of every record in *keys.  Recording, the order and the record of the
+// iteration are the call's FIRST ones (the list forms add `it` steps), and the work that runs on the second stream otherwise
+// (the masked variance sums of G, R~ E[G]) is recorded in line: the same kernels on the same operands, the same bits.
+static int enqueue_trivb_iteration(bnmtf_model* h, int it, bool recording, TriSiteKeys* keys = nullptr) {
+  Dir& r = h->rows; Dir& c = h->cols;
+  const int K = h->K, L = h->L, per = K * L + K + L;
+  const bool overlap = tri_overlap(h);
+  if (recording && (!g_recorder || !overlap)) { set_error("a recorded tri-factorisation iteration needs a recorder and the overlapped passes"); return BNMTF_ESTATE; }
+  const int* ord = h->tri_order + (recording ? 0 : (size_t)it * per);
+  const int step = recording ? per : 0;
+  // Contractions of an iteration (round 6): R~ (E[G] E[S]^T) = (R~ E[G]) E[S]^T and R~^T (E[F] E[S]) = (R~^T E[F]) E[S] -- the passes over
+  // R~ do not wait for S.  R~ E[G] and the masked variance sums of G (E[G], varG: final since the last G sweep) run on a second
+  // stream BESIDE the S pass (one compute unit of 256 for ~160 us); R~^T E[F] is formed once behind the F sweep and serves the G
+  // step and the next iteration's S system.  Three passes over R~ on the critical path became one.  BNMTF_TRI_OVERLAP=0: in line.
+  // Several GPUs (round 6): rows of F and columns of G updated by their owners; the blocks of (E, var, S2) gathered behind each half
+  // sweep (the other side's effective factor, masked variance sums and column Grams read every row); the S system summed over the
+  // ranks' column ranges and walked by every rank; the iteration's sums exchanged as 21 doubles.
+  auto slab_product = [&](const float* slabs_in, int split, int n_pad, float* out, int n, int transposeS) {
+    SlabProductArgs sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.slabs = slabs_in; sp.split = split; sp.n_pad = n_pad; sp.KPin = 32; sp.S = h->S; sp.K = K; sp.L = L; sp.n = n; sp.out = out; sp.KPout = 32;
+    sp.transposeS = transposeS;
+    launch_slab_product(sp, h->stream);
+  };
+  auto gemm_rows = [&](hipStream_t st) {                            // r.slabs = R~ E[G]
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.big = r.big; g.ld = r.n_pad; g.X = c.X; g.slabs = r.slabs; g.n_pad = r.n_pad; g.split = r.split; g.inner_per_wave = r.ipw; g.tw = r.gemm_tw;
+    launch_gemm(g, r.KP, st);
+  };
+  {   // ---- S entries in shuffled order
+    ScopedKernelTimer t(h, BNMTF_KERNEL_SWEEP_S);
+    CHK(enqueue_tri_ssys(h, overlap && h->tri_pv_current, keys));
+    if (recording) {
+      TriSiteKeys::at(keys, kTsColsumRows);
+      enqueue_tri_masked_colsum(h, 0, h->stream);
+      TriSiteKeys::at(keys, kTsGemmRows);
+      gemm_rows(h->stream);
+    } else if (overlap) {
+      HIPCHK(hipEventRecord(h->ev_aux0, h->stream));
+      HIPCHK(hipStreamWaitEvent(h->aux_stream, h->ev_aux0, 0));
+      enqueue_tri_masked_colsum(h, 0, h->aux_stream);
+      gemm_rows(h->aux_stream);
+      HIPCHK(hipEventRecord(h->ev_aux1, h->aux_stream));
+    }
+    enqueue_tri_chain(h, ord, K * L, 0, step, keys);
+  }
+  // ---- F columns in their shuffled order
+  if (overlap) {
+    TriSiteKeys::at(keys, kTsProductF);
+    enqueue_tri_side_prepare(h, 0, 1);
+    if (!recording) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_aux1, 0));
+    TriSiteKeys::at(keys, kTsSlabF);
+    slab_product(r.slabs, r.split, r.n_pad, r.slabs, r.n, 1);       // (in place: a unit's half wave reads all of its row before it writes slab 0)
+  } else enqueue_tri_side_prepare(h, 0);
+  {
+    ScopedKernelTimer t(h, BNMTF_KERNEL_SWEEP_ROWS);
+    TriSiteKeys::at(keys, kTsSweepF);
+    enqueue_tri_sweep(h, 0, ord + K * L, false, overlap, nullptr, step);
+  }
+  if (h->comm)
+    for (float* X : {r.X, r.var, r.S2}) CHK(comm_allgather_factor(h->comm, X, r.KP, r.nglob, h->world, h->stream));
+  TriSiteKeys::at(keys, kTsPostF);
+  enqueue_post(h, r, true);
+  TriSiteKeys::at(keys, kTsColGramsNext);
+  enqueue_tri_colgrams(h);                 // (+ mv_cols for the G sweep below)
+  // ---- G columns
+  if (overlap) {
+    { ScopedKernelTimer t(h, BNMTF_KERNEL_GEMM_COLS); TriSiteKeys::at(keys, kTsPvNext); enqueue_tri_pv(h); }      // R~^T E[F] of the F just written
+    h->tri_pv_current = true;
+    TriSiteKeys::at(keys, kTsProductG);
+    enqueue_tri_side_prepare(h, 2, 1);
+    TriSiteKeys::at(keys, kTsSlabG);
+    slab_product(h->slabsS, c.split, c.n_pad, c.slabs, c.n, 0);
+  } else enqueue_tri_side_prepare(h, 2, 1 | 4);
+  int sweep_blocks = 0;
+  {
+    ScopedKernelTimer t(h, BNMTF_KERNEL_SWEEP_COLS);
+    TriSiteKeys::at(keys, kTsSweepG);
+    enqueue_tri_sweep(h, 2, ord + K * L + K, true, overlap, h->comm ? nullptr : &sweep_blocks, step);
+  }
+  if (h->comm)
+    for (float* X : {c.X, c.var, c.S2}) CHK(comm_allgather_factor(h->comm, X, c.KP, c.nglob, h->world, h->stream));
+  TriSiteKeys::at(keys, kTsPostG);
+  enqueue_post(h, c, true);
+  // ---- update_tau, update_exp_tau, predict(M).  Round 6: exp_square_diff (:235-239) without a pass over R -- it was three
+  // direct fp64 passes of 323 us each at 4096^2.  With m = E[F] E[S] (the G sweep's effective factor: mean m, second moment S2e):
+  //   first term + the metrics: the SSE identity on the G sweep's own sums (sum P.G, sum_miss q, sum_miss q^2) and the Grams;
+  //   second + fourth term  = sum_Omega sum_l (S2G_jl S2e_il - E[G_jl]^2 m_il^2)  -- the BNMF-VB second-moment term against the
+  //                           effective factor: column sums, Gram diagonals and the sweep's two masked sums per (j, l);
+  //   third term            = sum_jk mvF_jk ((E[S] E[G]^T)^2 - E[S]^2 (E[G]^2)^T)_kj  with the masked variance sums of the G step.
+  TriThirdArgs t3;
+  memset(&t3, 0, sizeof(t3));
+  t3.rows = c.n; t3.K = K; t3.L = L; t3.G = c.X + (size_t)c.n0 * 32; t3.S = h->S; t3.mv = h->mv_cols; t3.part = h->tri_third;
+  TriSiteKeys::at(keys, kTsThird);
+  launch_tri_third(t3, h->stream);
+  VbFinishArgs f;
+  memset(&f, 0, sizeof(f));
+  f.acc = h->acc; f.stats_r = r.vb_stats; f.nr = r.vb_stat_rows; f.stats_c = c.vb_stats; f.nc = c.vb_stat_rows;
+  f.Cr64 = h->reff.C64; f.Cc64 = c.C64; f.sr = h->reff.colsum; f.sc = c.colsum; f.s2r = h->reff.colsum2; f.s2c = c.colsum2; f.KP = c.KP;
+  f.n_obs = h->n_obs; f.sumR = h->sumR; f.sumR2 = h->sumR2; f.alpha = h->alpha; f.beta = h->beta;
+  f.tau_d = h->tau_d; f.tau_f = h->tau_f; f.rec = h->vb_rec + (recording ? 0 : (size_t)it * 16);      // (recording: the list form adds `it` records)
+  f.extra = h->tri_third; f.n_extra = tri_third_blocks(c.n);
+  f.sweep_stats = sweep_blocks > 0 ? c.stats : nullptr; f.n_sweep_stats = sweep_blocks;
+  if (h->comm) {
+    // [0..2] the SSE-identity sums, [4..9] the pieces of the rows, [12..17] of the columns, [20] the third term: one all-reduce
+    HIPCHK(hipMemsetAsync(h->vbred, 0, 24 * sizeof(double), h->stream));
+    launch_sum_cols(h->acc, 1, 4, 3, h->vbred, h->stream);
+    launch_sum_cols(r.vb_stats, r.vb_stat_rows, 8, 6, h->vbred + 4, h->stream);
+    launch_sum_cols(c.vb_stats, c.vb_stat_rows, 8, 6, h->vbred + 12, h->stream);
+    launch_sum_cols(h->tri_third, tri_third_blocks(c.n), 1, 1, h->vbred + 20, h->stream);
+    CHK(comm_allreduce_sum(h->comm, h->vbred, 21, h->stream));
+    f.acc = h->vbred; f.stats_r = h->vbred + 4; f.nr = 1; f.stats_c = h->vbred + 12; f.nc = 1;
+    f.extra = h->vbred + 20; f.n_extra = 1;
+  }
+  TriSiteKeys::at(keys, kTsFinish);
+  launch_vb_finish(f, h->stream);
+  TriSiteKeys::at(keys, kTsEnd);
+  if (recording && (sweep_blocks == 0 || g_recorder->missing)) {
+    set_error("a recorded tri-factorisation iteration met a kernel without a list form (%s)", g_recorder->missing ? g_recorder->missing : "the G sweep's sums");
+    return BNMTF_ESTATE;
+  }
+  if (sweep_blocks == 0) HIPCHK(hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));       // (acc was used: clean for the next iteration)
+  h->iteration++;
   return BNMTF_OK;
 }
 
@@ -292,103 +471,15 @@ int bnmtf_vb_run(bnmtf_handle h, int n_iter, const int32_t* orders, double* expt
   EventList ev;
   CHK(ev.create(times_out ? n_iter + 1 : 0));
   if (times_out) HIPCHK(hipEventRecord(ev[0], h->stream));
-  // Contractions of an iteration (round 6): R~ (E[G] E[S]^T) = (R~ E[G]) E[S]^T and R~^T (E[F] E[S]) = (R~^T E[F]) E[S] -- the passes over
-  // R~ do not wait for S.  R~ E[G] and the masked variance sums of G (E[G], varG: final since the last G sweep) run on a second
-  // stream BESIDE the S pass (one compute unit of 256 for ~160 us); R~^T E[F] is formed once behind the F sweep and serves the G
-  // step and the next iteration's S system.  Three passes over R~ on the critical path became one.  BNMTF_TRI_OVERLAP=0: in line.
-  static const bool overlap_off = [] { const char* e = getenv("BNMTF_TRI_OVERLAP"); return e && atoi(e) == 0; }();
-  const bool overlap = !overlap_off && !h->comm;       // (several GPUs: every rank's passes cover its own rows / columns only; in line)
-  // Several GPUs (round 6): rows of F and columns of G updated by their owners; the blocks of (E, var, S2) gathered behind each half
-  // sweep (the other side's effective factor, masked variance sums and column Grams read every row); the S system summed over the
-  // ranks' column ranges and walked by every rank; the iteration's sums exchanged as 21 doubles.
-  if (overlap) {
+  if (tri_overlap(h)) {                    // (the second stream of enqueue_trivb_iteration)
     if (!h->aux_stream) HIPCHK(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
     for (hipEvent_t* e : {&h->ev_aux0, &h->ev_aux1})
       if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
   }
-  auto slab_product = [&](const float* slabs_in, int split, int n_pad, float* out, int n, int transposeS) {
-    SlabProductArgs sp;
-    sp.slabs = slabs_in; sp.split = split; sp.n_pad = n_pad; sp.KPin = 32; sp.S = h->S; sp.K = K; sp.L = L; sp.n = n; sp.out = out; sp.KPout = 32;
-    sp.transposeS = transposeS;
-    launch_slab_product(sp, h->stream);
-  };
   HIPCHK(hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));
   for (int it = 0; it < n_iter; ++it) {
-    const int* ord = h->tri_order + (size_t)it * per;
-    {   // ---- S entries in shuffled order
-      ScopedKernelTimer t(h, BNMTF_KERNEL_SWEEP_S);
-      CHK(enqueue_tri_ssys(h, overlap && h->tri_pv_current));
-      if (overlap) {
-        HIPCHK(hipEventRecord(h->ev_aux0, h->stream));
-        HIPCHK(hipStreamWaitEvent(h->aux_stream, h->ev_aux0, 0));
-        enqueue_tri_masked_colsum(h, 0, h->aux_stream);
-        GemmArgs g;                                                  // r.slabs = R~ E[G]
-        g.big = r.big; g.ld = r.n_pad; g.X = c.X; g.slabs = r.slabs; g.n_pad = r.n_pad; g.split = r.split; g.inner_per_wave = r.ipw; g.tw = r.gemm_tw;
-        launch_gemm(g, r.KP, h->aux_stream);
-        HIPCHK(hipEventRecord(h->ev_aux1, h->aux_stream));
-      }
-      enqueue_tri_chain(h, ord, K * L, 0);
-    }
-    // ---- F columns in their shuffled order
-    if (overlap) {
-      enqueue_tri_side_prepare(h, 0, 1);
-      HIPCHK(hipStreamWaitEvent(h->stream, h->ev_aux1, 0));
-      slab_product(r.slabs, r.split, r.n_pad, r.slabs, r.n, 1);       // (in place: a unit's half wave reads all of its row before it writes slab 0)
-    } else enqueue_tri_side_prepare(h, 0);
-    {
-      ScopedKernelTimer t(h, BNMTF_KERNEL_SWEEP_ROWS);
-      enqueue_tri_sweep(h, 0, ord + K * L, false, overlap);
-    }
-    if (h->comm)
-      for (float* X : {r.X, r.var, r.S2}) CHK(comm_allgather_factor(h->comm, X, r.KP, r.nglob, h->world, h->stream));
-    enqueue_post(h, r, true);
-    enqueue_tri_colgrams(h);                 // (+ mv_cols for the G sweep below)
-    // ---- G columns
-    if (overlap) {
-      { ScopedKernelTimer t(h, BNMTF_KERNEL_GEMM_COLS); enqueue_tri_pv(h); }      // R~^T E[F] of the F just written
-      h->tri_pv_current = true;
-      enqueue_tri_side_prepare(h, 2, 1);
-      slab_product(h->slabsS, c.split, c.n_pad, c.slabs, c.n, 0);
-    } else enqueue_tri_side_prepare(h, 2, 1 | 4);
-    int sweep_blocks = 0;
-    {
-      ScopedKernelTimer t(h, BNMTF_KERNEL_SWEEP_COLS);
-      enqueue_tri_sweep(h, 2, ord + K * L + K, true, overlap, h->comm ? nullptr : &sweep_blocks);
-    }
-    if (h->comm)
-      for (float* X : {c.X, c.var, c.S2}) CHK(comm_allgather_factor(h->comm, X, c.KP, c.nglob, h->world, h->stream));
-    enqueue_post(h, c, true);
-    // ---- update_tau, update_exp_tau, predict(M).  Round 6: exp_square_diff (:235-239) without a pass over R -- it was three
-    // direct fp64 passes of 323 us each at 4096^2.  With m = E[F] E[S] (the G sweep's effective factor: mean m, second moment S2e):
-    //   first term + the metrics: the SSE identity on the G sweep's own sums (sum P.G, sum_miss q, sum_miss q^2) and the Grams;
-    //   second + fourth term  = sum_Omega sum_l (S2G_jl S2e_il - E[G_jl]^2 m_il^2)  -- the BNMF-VB second-moment term against the
-    //                           effective factor: column sums, Gram diagonals and the sweep's two masked sums per (j, l);
-    //   third term            = sum_jk mvF_jk ((E[S] E[G]^T)^2 - E[S]^2 (E[G]^2)^T)_kj  with the masked variance sums of the G step.
-    TriThirdArgs t3;
-    t3.rows = c.n; t3.K = K; t3.L = L; t3.G = c.X + (size_t)c.n0 * 32; t3.S = h->S; t3.mv = h->mv_cols; t3.part = h->tri_third;
-    launch_tri_third(t3, h->stream);
-    VbFinishArgs f;
-    f.acc = h->acc; f.stats_r = r.vb_stats; f.nr = r.vb_stat_rows; f.stats_c = c.vb_stats; f.nc = c.vb_stat_rows;
-    f.Cr64 = h->reff.C64; f.Cc64 = c.C64; f.sr = h->reff.colsum; f.sc = c.colsum; f.s2r = h->reff.colsum2; f.s2c = c.colsum2; f.KP = c.KP;
-    f.n_obs = h->n_obs; f.sumR = h->sumR; f.sumR2 = h->sumR2; f.alpha = h->alpha; f.beta = h->beta;
-    f.tau_d = h->tau_d; f.tau_f = h->tau_f; f.rec = h->vb_rec + (size_t)it * 16;
-    f.extra = h->tri_third; f.n_extra = tri_third_blocks(c.n);
-    f.sweep_stats = sweep_blocks > 0 ? c.stats : nullptr; f.n_sweep_stats = sweep_blocks;
-    if (h->comm) {
-      // [0..2] the SSE-identity sums, [4..9] the pieces of the rows, [12..17] of the columns, [20] the third term: one all-reduce
-      HIPCHK(hipMemsetAsync(h->vbred, 0, 24 * sizeof(double), h->stream));
-      launch_sum_cols(h->acc, 1, 4, 3, h->vbred, h->stream);
-      launch_sum_cols(r.vb_stats, r.vb_stat_rows, 8, 6, h->vbred + 4, h->stream);
-      launch_sum_cols(c.vb_stats, c.vb_stat_rows, 8, 6, h->vbred + 12, h->stream);
-      launch_sum_cols(h->tri_third, tri_third_blocks(c.n), 1, 1, h->vbred + 20, h->stream);
-      CHK(comm_allreduce_sum(h->comm, h->vbred, 21, h->stream));
-      f.acc = h->vbred; f.stats_r = h->vbred + 4; f.nr = 1; f.stats_c = h->vbred + 12; f.nc = 1;
-      f.extra = h->vbred + 20; f.n_extra = 1;
-    }
-    launch_vb_finish(f, h->stream);
-    if (sweep_blocks == 0) HIPCHK(hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));       // (acc was used: clean for the next iteration)
+    CHK(enqueue_trivb_iteration(h, it, false));
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], h->stream));
-    h->iteration++;
   }
   if (h->comm)      // the q parameters of the other ranks' rows / columns (bnmtf_vb_get_state returns whole matrices)
     for (Dir* d : {&r, &c})

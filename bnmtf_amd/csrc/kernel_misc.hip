@@ -295,6 +295,7 @@ __global__ __launch_bounds__(256) void sum_stats_kernel(const double* stats, int
   if (threadIdx.x < 3) acc[threadIdx.x] += (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 void launch_sum_stats(const double* stats, int nblocks, double* acc, hipStream_t st) {
+  if (record_missing("sum_stats")) return;             // (no list form)
   hipLaunchKernelGGL(sum_stats_kernel, dim3(1), dim3(256), 0, st, stats, nblocks, acc);
 }
 
@@ -317,6 +318,7 @@ __global__ __launch_bounds__(256) void sum_cols_kernel(const double* stats, int 
   if ((int)threadIdx.x < ncols) out[threadIdx.x] += (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 void launch_sum_cols(const double* stats, int nrows, int ld, int ncols, double* out, hipStream_t st) {
+  if (record_missing("sum_cols")) return;             // (no list form)
   hipLaunchKernelGGL(sum_cols_kernel, dim3(1), dim3(256), 0, st, stats, nrows, ld, ncols, out);
 }
 

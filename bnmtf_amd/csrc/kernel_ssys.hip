@@ -23,6 +23,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "many.h"
 #include "sweep_common.h"
 
 namespace bnmtf {
@@ -69,15 +70,16 @@ __device__ __forceinline__ void ssys_b_body(const SSysBArgs& a, int block);
 // BF = 1 (round 6): the outer products on the bf16 matrix cores, fp32-exact -- a half's eight rows of a 16-slot step ARE the A (and
 // B) operand of v_mfma_f32_32x32x16_bf16 (lane (c, g) holds k = 8 g .. 8 g + 7), so the loads stay as they are and a step is one
 // three-term split of eight registers (g_split3) and six products (6 x 32 cycles) instead of eight f32 products (8 x 64).
-template <int VB, int BF = 0>
-__global__ __launch_bounds__(256) void scol_gram_kernel(SColGramArgs a, GammaPackArgs gp, SSysBArgs sb) {
+// (LIST: the list form's own instantiation -- a body shared by two kernels is inlined differently into each)
+template <int VB, int BF, int LIST>
+__device__ __forceinline__ void scol_gram_body(SColGramArgs a, GammaPackArgs gp, SSysBArgs sb, unsigned block) {
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   const int gram_blocks = (a.n + 3) / 4, pack_blocks = (gp.n + 7) / 8;
   // (... and behind those, the blocks of b = sum_j Pv_j (x) G_j: a third independent piece of the S system's build in this launch)
-  if ((int)blockIdx.x >= gram_blocks + pack_blocks) { ssys_b_body(sb, (int)blockIdx.x - gram_blocks - pack_blocks); return; }
-  if ((int)blockIdx.x >= gram_blocks) { gamma_pack_body(gp, (int)blockIdx.x - gram_blocks); return; }
+  if ((int)block >= gram_blocks + pack_blocks) { ssys_b_body(sb, (int)block - gram_blocks - pack_blocks); return; }
+  if ((int)block >= gram_blocks) { gamma_pack_body(gp, (int)block - gram_blocks); return; }
   const int lane = threadIdx.x & 63, half = lane >> 5, c = lane & 31;
-  const int u = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int u = block * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (u >= a.n) return;
   const uint32_t s0 = __builtin_amdgcn_readfirstlane(a.slot_ptr[u]), s1 = __builtin_amdgcn_readfirstlane(a.slot_ptr[u + 1]);   // 64-wide slots, padded with the zero row
   const __amdgpu_buffer_rsrc_t rsI = panel_rsrc(reinterpret_cast<const float*>(a.idx), 0x7fffffffu);
@@ -159,13 +161,35 @@ __global__ __launch_bounds__(256) void scol_gram_kernel(SColGramArgs a, GammaPac
     if (row <= c && c < a.K) w[tri_pos(tri_index(row, c, a.K))] = cf - m;    // the upper triangle, packed: what the S-system GEMM reads
   }
 }
+template <int VB, int BF = 0>
+__global__ __launch_bounds__(256) void scol_gram_kernel(SColGramArgs a, GammaPackArgs gp, SSysBArgs sb) { scol_gram_body<VB, BF, 0>(a, gp, sb, blockIdx.x); }
+// list form (many.h): blockIdx.z = model; a model with fewer blocks than the launch leaves
+struct SColGramPack { SColGramArgs a; GammaPackArgs gp; SSysBArgs sb; };
+__host__ __device__ inline int scol_gram_blocks(const SColGramArgs& a, const GammaPackArgs& gp, const SSysBArgs* sb) {
+  return (a.n + 3) / 4 + (gp.n + 7) / 8 + (sb ? ((sb->n + 63) / 64 > 0 ? (sb->n + 63) / 64 : 1) : 0);      // (ssys_b_blocks)
+}
+template <int VB>
+__global__ __launch_bounds__(256) void scol_gram_many(const SColGramPack* list, int) {
+  const SColGramPack p = load_pack(list, blockIdx.z);
+  if ((int)blockIdx.x >= scol_gram_blocks(p.a, p.gp, p.sb.b ? &p.sb : nullptr)) return;
+  scol_gram_body<VB, 1, 1>(p.a, p.gp, p.sb, blockIdx.x);
+}
+// BNMTF_SCOL_GRAM=f32: the f32 matrix-core form (A/B switch; no list form)
+static bool scol_gram_f32() { static const bool f32 = [] { const char* e = getenv("BNMTF_SCOL_GRAM"); return e && !strcmp(e, "f32"); }(); return f32; }
 // gp: the packing of G's second moments rides along (gp.n == 0: none); sb (may be null): and the blocks of b
 void launch_scol_gram(const SColGramArgs& a, const GammaPackArgs& gp, hipStream_t st, const SSysBArgs* sb) {
   if (a.n <= 0) return;
   SSysBArgs b0 = {};
-  const int blocks = (a.n + 3) / 4 + (gp.n + 7) / 8 + (sb ? ssys_b_blocks(sb->n) : 0);
-  // BNMTF_SCOL_GRAM=f32: the f32 matrix-core form (A/B switch)
-  static const bool f32 = [] { const char* e = getenv("BNMTF_SCOL_GRAM"); return e && !strcmp(e, "f32"); }();
+  const int blocks = scol_gram_blocks(a, gp, sb);
+  const bool f32 = scol_gram_f32();
+  if (g_recorder) {
+    if (f32) { record_missing("scol_gram (BNMTF_SCOL_GRAM=f32)"); return; }
+    SColGramPack p; memset(&p, 0, sizeof(p));
+    p.a = a; p.gp = gp;
+    if (sb) p.sb = *sb;
+    record_launch(a.varF ? (const void*)scol_gram_many<1> : (const void*)scol_gram_many<0>, dim3(blocks), dim3(256), 0, p, true);
+    return;
+  }
   if (f32) {
     if (a.varF) hipLaunchKernelGGL((scol_gram_kernel<1, 0>), dim3(blocks), dim3(256), 0, st, a, gp, sb ? *sb : b0);
     else        hipLaunchKernelGGL((scol_gram_kernel<0, 0>), dim3(blocks), dim3(256), 0, st, a, gp, sb ? *sb : b0);
@@ -196,8 +220,15 @@ __device__ __forceinline__ void gamma_pack_body(const GammaPackArgs& a, int bloc
   }
 }
 __global__ __launch_bounds__(256) void gamma_pack_kernel(GammaPackArgs a) { gamma_pack_body(a, (int)blockIdx.x); }
+__global__ __launch_bounds__(256) void gamma_pack_many(const GammaPackArgs* list, int) {
+  const GammaPackArgs a = load_pack(list, blockIdx.z);
+  if ((int)blockIdx.x >= (a.n + 7) / 8) return;
+  gamma_pack_body(a, (int)blockIdx.x);
+}
 void launch_gamma_pack(const GammaPackArgs& a, hipStream_t st) {
-  if (a.n > 0) hipLaunchKernelGGL(gamma_pack_kernel, dim3((a.n + 7) / 8), dim3(256), 0, st, a);
+  if (a.n <= 0) return;
+  if (record_launch((const void*)gamma_pack_many, dim3((a.n + 7) / 8), dim3(256), 0, a, true)) return;
+  hipLaunchKernelGGL(gamma_pack_kernel, dim3((a.n + 7) / 8), dim3(256), 0, st, a);
 }
 
 // A on the packed pairs: slab[s][p][r] = sum_{j in range s} Wc[j][p] Gc[j][r], p = (k <= k'), r = (l <= l') -- with both
@@ -275,11 +306,12 @@ __global__ __launch_bounds__(256) void ssys_gemm_kernel(SSysGemmArgs a) {
 // of BOTH interleaved tiles) -- splits its four fragments (a0, a1, b0, b1) and issues the 24 products; the next step's rows are
 // on their way in a second register set meanwhile.  Ranges are cut at multiples of 16 columns; past a range's end the zero rows
 // behind the arrays are read.  Same tiles, same slab layout, same epilogue as ssys_gemm_kernel.
-__global__ __launch_bounds__(256) void ssys_gemm_bf16_kernel(SSysGemmArgs a) {
+template <int LIST>
+__device__ __forceinline__ void ssys_gemm_bf16_body(const SSysGemmArgs& a, unsigned block) {
   const int lane = threadIdx.x & 63, half = lane >> 5, c = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int PKp = tri_padded(a.K), PLp = tri_padded(a.L), TR = PLp / 64;
-  const int wt = blockIdx.x * 4 + wave, sp = blockIdx.y;
+  const int wt = block * 4 + wave, sp = blockIdx.y;
   if (wt >= (PKp / 64) * TR) return;
   const int tp = wt / TR, tr = wt % TR;
   const int per = ssys_gemm_range(a.n, a.nsplit);
@@ -345,25 +377,36 @@ __global__ __launch_bounds__(256) void ssys_gemm_bf16_kernel(SSysGemmArgs a) {
         slab[(size_t)row * PLp + tr * 64 + 32 * y + c] = acc[x][y][t];
       }
 }
+__global__ __launch_bounds__(256) void ssys_gemm_bf16_kernel(SSysGemmArgs a) { ssys_gemm_bf16_body<0>(a, blockIdx.x); }
+// list form: the launch's grid.y (the column ranges) is every model's own; a block past a model's tiles leaves in the body
+__global__ __launch_bounds__(256) void ssys_gemm_bf16_many(const SSysGemmArgs* list, int) { ssys_gemm_bf16_body<1>(load_pack(list, blockIdx.z), blockIdx.x); }
+static bool ssys_gemm_f32() { const char* e = getenv("BNMTF_SSYS_GEMM"); return e && !strcmp(e, "f32"); }
+bool ssys_ab_switch_set() { return scol_gram_f32() || ssys_gemm_f32(); }
 void launch_ssys_gemm(const SSysGemmArgs& a, hipStream_t st) {
   const dim3 grid((ssys_gemm_wave_tiles(a.K, a.L) + 3) / 4, a.nsplit);
-  const char* e = getenv("BNMTF_SSYS_GEMM");        // A/B switch: "f32" = the f32-MFMA form of rounds 2-5
-  if (e && !strcmp(e, "f32")) hipLaunchKernelGGL(ssys_gemm_kernel, grid, dim3(256), 0, st, a);
+  const bool f32 = ssys_gemm_f32();                 // A/B switch: "f32" = the f32-MFMA form of rounds 2-5 (no list form)
+  if (g_recorder) {
+    if (f32) record_missing("ssys_gemm (BNMTF_SSYS_GEMM=f32)");
+    else record_launch((const void*)ssys_gemm_bf16_many, grid, dim3(256), 0, a, true);
+    return;
+  }
+  if (f32) hipLaunchKernelGGL(ssys_gemm_kernel, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(ssys_gemm_bf16_kernel, grid, dim3(256), 0, st, a);
 }
 
 // A[(k,l)][(k',l')] = sum of the column-range slabs (in range order) at (p(k,k'), r(l,l')).  One block per packed pair p:
 // its row of the slabs is summed 16 bytes per thread, the two halves of the ranges by two threads (combined in a fixed
 // order), goes through LDS and comes out as the full L x L blocks (k,k') and (k',k), rows contiguous.
-__global__ __launch_bounds__(320) void ssys_reduce_kernel(const float* slabs, int nsplit, int K, int L, float* A) {
+template <int LIST>
+__device__ __forceinline__ void ssys_reduce_body(const float* slabs, int nsplit, int K, int L, float* A, unsigned block) {
   __shared__ __align__(16) float v[2][640];
-  int k, kp; tri_unindex(blockIdx.x, K, &k, &kp);
+  int k, kp; tri_unindex(block, K, &k, &kp);
   const int PLp = tri_padded(L), n2 = K * L, nq = PLp / 4;         // nq <= 144 float4 per row
   const size_t slab = (size_t)tri_padded(K) * PLp;
   const int q = threadIdx.x % 160, hs = threadIdx.x / 160;         // 2 x 160 threads
   if (q < nq) {
     const int t0 = hs ? (nsplit + 1) / 2 : 0, t1 = hs ? nsplit : (nsplit + 1) / 2;
-    const float4* sp = reinterpret_cast<const float4*>(slabs + (size_t)blockIdx.x * PLp) + q;
+    const float4* sp = reinterpret_cast<const float4*>(slabs + (size_t)block * PLp) + q;
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int t = t0; t < t1; ++t) { const float4 x = sp[(size_t)t * (slab / 4)]; s.x += x.x; s.y += x.y; s.z += x.z; s.w += x.w; }
     *reinterpret_cast<float4*>(&v[hs][4 * q]) = s;
@@ -376,7 +419,22 @@ __global__ __launch_bounds__(320) void ssys_reduce_kernel(const float* slabs, in
     if (k != kp) A[(size_t)(kp * L + l) * n2 + k * L + lp] = x;
   }
 }
+__global__ __launch_bounds__(320) void ssys_reduce_kernel(const float* slabs, int nsplit, int K, int L, float* A) {
+  ssys_reduce_body<0>(slabs, nsplit, K, L, A, blockIdx.x);
+}
+struct SSysReducePack { const float* slabs; float* A; int nsplit, K, L, pad_; };
+__global__ __launch_bounds__(320) void ssys_reduce_many(const SSysReducePack* list, int) {
+  const SSysReducePack p = load_pack(list, blockIdx.z);
+  if ((int)blockIdx.x >= tri_count(p.K)) return;
+  ssys_reduce_body<1>(p.slabs, p.nsplit, p.K, p.L, p.A, blockIdx.x);
+}
 void launch_ssys_reduce(const float* slabs, int nsplit, int K, int L, float* A, hipStream_t st) {
+  if (g_recorder) {
+    SSysReducePack p; memset(&p, 0, sizeof(p));
+    p.slabs = slabs; p.A = A; p.nsplit = nsplit; p.K = K; p.L = L;
+    record_launch((const void*)ssys_reduce_many, dim3(tri_count(K)), dim3(320), 0, p, true);
+    return;
+  }
   hipLaunchKernelGGL(ssys_reduce_kernel, dim3(tri_count(K)), dim3(320), 0, st, slabs, nsplit, K, L, A);
 }
 
@@ -416,7 +474,13 @@ __device__ __forceinline__ void ssys_b_body(const SSysBArgs& a, int block) {
     if (k0 + 8 * i < a.K && l < a.L) a.b[(size_t)block * a.K * a.L + (k0 + 8 * i) * a.L + l] = s[i];
 }
 __global__ __launch_bounds__(256) void ssys_b_kernel(SSysBArgs a) { ssys_b_body(a, (int)blockIdx.x); }
+__global__ __launch_bounds__(256) void ssys_b_many(const SSysBArgs* list, int) {
+  const SSysBArgs a = load_pack(list, blockIdx.z);
+  if ((int)blockIdx.x >= ((a.n + 63) / 64 > 0 ? (a.n + 63) / 64 : 1)) return;     // (ssys_b_blocks)
+  ssys_b_body(a, (int)blockIdx.x);
+}
 void launch_ssys_b(const SSysBArgs& a, hipStream_t st) {
+  if (record_launch((const void*)ssys_b_many, dim3(ssys_b_blocks(a.n)), dim3(256), 0, a, true)) return;
   hipLaunchKernelGGL(ssys_b_kernel, dim3(ssys_b_blocks(a.n)), dim3(256), 0, st, a);
 }
 
@@ -435,6 +499,7 @@ __global__ void ssys_sum_parts_kernel(const float* slabs, int nsplit, size_t n, 
   A[e] = s;
 }
 void launch_ssys_sum_parts(const float* slabs, int nsplit, size_t n, float* A, hipStream_t st) {
+  if (record_missing("ssys_sum_parts")) return;
   hipLaunchKernelGGL(ssys_sum_parts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, slabs, nsplit, n, A);
 }
 
@@ -476,20 +541,21 @@ __device__ __forceinline__ void ssys_tinv_body(const float* A, int K, int L, int
 // not on A) -- a Philox call each, hidden behind the dot product instead of standing at the head of the one-block chain kernel.
 // (bparts != nullptr: b is still in its nparts per-block parts -- summed here, in part order, as ssys_sum_parts_kernel would, and
 // written to b as well.)  K blocks behind the rows' make the chain's Ti (tinv != nullptr).
-__global__ __launch_bounds__(256) void ssys_residual_kernel(const float* A, float* b, const float* bparts, int nparts, const float* S, int n2, float* r,
-                                                            float4* cands, uint32_t it, uint32_t key0, uint32_t key1, float* tinv, int K, int L, const float* tau,
-                                                            float4* own8, float4* recT, float* Tn) {
+template <int LIST>
+__device__ __forceinline__ void ssys_residual_body(const float* A, float* b, const float* bparts, int nparts, const float* S, int n2, float* r,
+                                                   float4* cands, uint32_t it, uint32_t key0, uint32_t key1, float* tinv, int K, int L, const float* tau,
+                                                   float4* own8, float4* recT, float* Tn, int block) {
 #pragma clang fp contract(off)
   // the grid: K blocks for Ti (tinv != nullptr; FIRST: one wave of ~750 dependent fp64 instructions each, the longest blocks of
   // the launch), the rows' blocks, the warm-up blocks
   const int rblocks = (n2 + 3) / 4, kt = tinv ? K : 0;
-  if ((int)blockIdx.x < kt) { ssys_tinv_body(A, K, L, (int)blockIdx.x, *tau, tinv); return; }
-  if ((int)blockIdx.x >= rblocks + kt) {
+  if (block < kt) { ssys_tinv_body(A, K, L, block, *tau, tinv); return; }
+  if (block >= rblocks + kt) {
     // Warm-up for the chain kernel that follows: it is ONE block, which the dispatcher puts on XCD 0 (block i of a grid goes to
     // XCD i mod 8: tools/micro/xcc.hip), and its fold streams the upper block triangle of A (2 MB) through that one CU -- out
     // of the Infinity Cache at ~24 B/clk, out of its own XCD's L2 several times faster.  So the blocks of this range that sit on
     // XCD 0 read that triangle once (the rows dealt round kWarm blocks); the other seven of every eight leave at once.
-    const int ws = (rblocks + kt + 7) & ~7, wb = (int)blockIdx.x - ws;
+    const int ws = (rblocks + kt + 7) & ~7, wb = block - ws;
     if (wb < 0 || (wb & 7) != 0) return;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int a0 = wb >> 3; a0 < n2; a0 += kSsysWarmBlocks) {
@@ -500,7 +566,7 @@ __global__ __launch_bounds__(256) void ssys_residual_kernel(const float* A, floa
     if (acc.x + acc.y + acc.z + acc.w == 1.2345e38f) r[0] = acc.x;   // (never: keeps the loads)
     return;
   }
-  const int lane = threadIdx.x & 63, row = ((int)blockIdx.x - kt) * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63, row = (block - kt) * 4 + (threadIdx.x >> 6);
   if (row >= n2) return;
   if (cands && lane < 4) {
     const U4 rr = philox4x32_10(0u, (uint32_t)row, it, kStreamS + 16u * (uint32_t)lane, key0, key1);
@@ -567,8 +633,27 @@ __global__ __launch_bounds__(256) void ssys_residual_kernel(const float* A, floa
     r[row] = (float)((double)bv - s);
   }
 }
+__global__ __launch_bounds__(256) void ssys_residual_kernel(const float* A, float* b, const float* bparts, int nparts, const float* S, int n2, float* r,
+                                                            float4* cands, uint32_t it, uint32_t key0, uint32_t key1, float* tinv, int K, int L, const float* tau,
+                                                            float4* own8, float4* recT, float* Tn) {
+  ssys_residual_body<0>(A, b, bparts, nparts, S, n2, r, cands, it, key0, key1, tinv, K, L, tau, own8, recT, Tn, (int)blockIdx.x);
+}
+// list form of the variational system's residual (no candidates, no Ti, no warm-up blocks: (n2 + 3) / 4 blocks of rows)
+struct SSysResidualPack { const float* A; float* b; const float* bparts; const float* S; float* r; int nparts, n2; };
+__global__ __launch_bounds__(256) void ssys_residual_many(const SSysResidualPack* list, int) {
+  const SSysResidualPack p = load_pack(list, blockIdx.z);
+  if ((int)blockIdx.x >= (p.n2 + 3) / 4) return;
+  ssys_residual_body<1>(p.A, p.b, p.bparts, p.nparts, p.S, p.n2, p.r, nullptr, 0, 0, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, (int)blockIdx.x);
+}
 void launch_ssys_residual(const float* A, float* b, const float* bparts, int nparts, const float* S, int n2, float* r, hipStream_t st, float* cands, uint32_t it, uint32_t key0, uint32_t key1,
                           float* tinv, int K, int L, const float* tau, float* own8, float* recT, float* Tn) {
+  if (g_recorder) {
+    if (cands || tinv || own8 || recT || Tn) { record_missing("ssys_residual (the sampler's form)"); return; }
+    SSysResidualPack p; memset(&p, 0, sizeof(p));
+    p.A = A; p.b = b; p.bparts = bparts; p.S = S; p.r = r; p.nparts = nparts; p.n2 = n2;
+    record_launch((const void*)ssys_residual_many, dim3((n2 + 3) / 4), dim3(256), 0, p, true);
+    return;
+  }
   hipLaunchKernelGGL(ssys_residual_kernel, dim3((tinv && (L & 3) == 0 && n2 >= 256) ? (((n2 + 3) / 4 + K + 7) & ~7) + 8 * kSsysWarmBlocks : (n2 + 3) / 4 + (tinv ? K : 0)), dim3(256), 0, st, A, b, bparts, nparts, S, n2, r, reinterpret_cast<float4*>(cands), it, key0, key1, tinv, K, L, tau,
                      reinterpret_cast<float4*>(own8), reinterpret_cast<float4*>(recT), Tn);
 }

@@ -17,6 +17,7 @@
 // shapes of the benchmark configs.
 #include "kernels.h"
 #include "device_rng.h"
+#include "many.h"
 
 namespace bnmtf {
 
@@ -167,6 +168,7 @@ __global__ __launch_bounds__(256) void sweep_generic_kernel(SweepArgs a) {
 }
 
 void launch_sweep(const SweepArgs& a, hipStream_t st) {
+  if (record_missing("the generic sweep")) return;              // (no list form)
   dim3 grid((a.n + 3) / 4), block(256);
   switch (a.mode) {
     case kSweepDraw: hipLaunchKernelGGL(sweep_generic_kernel<kSweepDraw>, grid, block, 0, st, a); break;

@@ -379,11 +379,14 @@ __global__ __launch_bounds__((NW + NS) * 64, 1) void sweep_vb_kernel(SweepArgs a
   else sweep_vb_body<kWideMaxSlots, NX, NW, NS, COV>(a, f, lds);      // host guarantees e0 <= kWideMaxSlots
 }
 
-struct SweepVbPack { SweepArgs a; FastArgs f; };
+// order_step (the tri-factorisation's sweeps, COV): a.order is the column order of the run's FIRST iteration; iteration `it`'s is
+// it * order_step entries behind it
+struct SweepVbPack { SweepArgs a; FastArgs f; int order_step; int pad_; };
 template <int NX, int NW, int NS, int COV = 0>       // list form (many.h): blockIdx.z = model; a model with fewer blocks than the launch leaves
-__global__ __launch_bounds__((NW + NS) * 64, 1) void sweep_vb_many(const SweepVbPack* list, int) {
+__global__ __launch_bounds__((NW + NS) * 64, 1) void sweep_vb_many(const SweepVbPack* list, int it) {
   extern __shared__ float lds[];
-  const SweepVbPack p = load_pack(list, blockIdx.z);
+  SweepVbPack p = load_pack(list, blockIdx.z);
+  if constexpr (COV != 0) { if (p.a.order) p.a.order += (size_t)it * p.order_step; }
   if ((int)blockIdx.x >= (p.f.npairs + NW - 1) / NW) return;
   const int wv = (int)(threadIdx.x >> 6);
   const int pr = blockIdx.x * NW + wv;
@@ -402,31 +405,30 @@ bool sweep_vb_supported(int KP, int pw) { return sweep_vb_lds_bytes(KP, pw) <= 1
 bool sweep_vb_cov_supported(int KP, int pw) { return KP == 32 && sweep_vb_lds_bytes(KP, pw, true) <= 160 * 1024; }
 
 template <int NX, int NW, int NS, int COV = 0>
-static void launch_vb_inst(const SweepArgs& a, const FastArgs& f, hipStream_t st) {
+static void launch_vb_inst(const SweepArgs& a, const FastArgs& f, hipStream_t st, int order_step) {
   static std::atomic<uint64_t> lds_ok{0};
   const int nblocks = sweep_vb_blocks(f.npairs, NW);
   if (g_recorder) {
-    if constexpr (COV == 0) {            // (the tri-factorisation's sweeps have no list form)
     static std::atomic<uint64_t> lds_ok_many{0};
-    if (nblocks <= 0 || !allow_full_lds((const void*)sweep_vb_many<NX, NW, NS, COV>, lds_ok_many)) return;
-    SweepVbPack p; memset(&p, 0, sizeof(p)); p.a = a; p.f = f;
+    if (nblocks <= 0) return;
+    if (!allow_full_lds((const void*)sweep_vb_many<NX, NW, NS, COV>, lds_ok_many)) { record_missing("sweep_vb (LDS)"); return; }
+    SweepVbPack p; memset(&p, 0, sizeof(p)); p.a = a; p.f = f; p.order_step = order_step;
     record_launch((const void*)sweep_vb_many<NX, NW, NS, COV>, dim3(nblocks), dim3((NW + NS) * 64),
                   std::max(sweep_vb_lds_bytes(a.KP, f.pw, COV != 0), sizeof(float) * ((size_t)a.KP * a.KP + a.KP + 2 * 16 * 5 + (size_t)f.ho_lds_floats)), p, true);
-    }
     return;
   }
   if (nblocks > 0 && allow_full_lds((const void*)sweep_vb_kernel<NX, NW, NS, COV>, lds_ok)) hipLaunchKernelGGL((sweep_vb_kernel<NX, NW, NS, COV>), dim3(nblocks), dim3((NW + NS) * 64), std::max(sweep_vb_lds_bytes(a.KP, f.pw, COV != 0), sizeof(float) * ((size_t)a.KP * a.KP + a.KP + 2 * 16 * 5 + (size_t)f.ho_lds_floats)), st, a, f);
 }
 
 // f.nw = 16: 16 unit waves per block; anything else: 8 unit waves + 2 service waves
-void launch_sweep_vb(const SweepArgs& a, const FastArgs& f, hipStream_t st) {
+void launch_sweep_vb(const SweepArgs& a, const FastArgs& f, hipStream_t st, int order_step) {
   const int nx = a.KP / 32;
   if (a.cov_S) {        // the tri-factorisation's F / G sweeps (callers: sweep_vb_cov_supported)
-    if (f.nw == 16) launch_vb_inst<1, 16, 0, 1>(a, f, st); else launch_vb_inst<1, 8, 2, 1>(a, f, st);
+    if (f.nw == 16) launch_vb_inst<1, 16, 0, 1>(a, f, st, order_step); else launch_vb_inst<1, 8, 2, 1>(a, f, st, order_step);
     return;
   }
-  if (f.nw == 16) { if (nx == 1) launch_vb_inst<1, 16, 0>(a, f, st); else launch_vb_inst<2, 16, 0>(a, f, st); }
-  else            { if (nx == 1) launch_vb_inst<1, 8, 2>(a, f, st);  else launch_vb_inst<2, 8, 2>(a, f, st); }
+  if (f.nw == 16) { if (nx == 1) launch_vb_inst<1, 16, 0>(a, f, st, 0); else launch_vb_inst<2, 16, 0>(a, f, st, 0); }
+  else            { if (nx == 1) launch_vb_inst<1, 8, 2>(a, f, st, 0);  else launch_vb_inst<2, 8, 2>(a, f, st, 0); }
 }
 
 // ELBO / exp_square_diff pieces of one sweep (bnmf_vb_optimised.py:163-177, 185-187), one wave per unit, lane = column:

@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "sweep_common.h"
+#include "many.h"
 #include "tn_mean_table.h"
 
 namespace bnmtf {
@@ -22,7 +23,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // mean and second moment of the effective factor:  Xe[r][c] = sum_t X[r][t] S(t,c),
 // S2e[r][c] = sum_t (varX + X^2)[r][t] (varS + S^2)(t,c) - sum_t X^2[r][t] S^2(t,c) + Xe^2     (S(t,c) = S[t][c] or S[c][t])
-__global__ __launch_bounds__(256) void small_product_vb_kernel(SmallProductVbArgs a) {
+// (block of a grid of nblocks: the single-model kernel and its list form share the body)
+// (LIST: the list form's own instantiation -- a body shared by two kernels is inlined differently into each, and the single-model
+// kernel keeps the code it had)
+template <int LIST>
+__device__ __forceinline__ void small_product_vb_body(SmallProductVbArgs a, unsigned block, unsigned nblocks) {
   // S(t, c) at [t][c] in LDS whichever way it is read: consecutive lanes (c) on consecutive banks (round 6: the transposed read
   // c L + t was a 32-way bank conflict -- 16.8 us for the F side against 5 us for the G side)
   __shared__ float Ss[32 * 32], Vs[32 * 32];
@@ -33,7 +38,7 @@ __global__ __launch_bounds__(256) void small_product_vb_kernel(SmallProductVbArg
   }
   __syncthreads();
   const int inner = a.transposeS ? a.L : a.K, outw = a.transposeS ? a.K : a.L;
-  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < (size_t)a.rows * outw; e += (size_t)gridDim.x * 256) {
+  for (size_t e = (size_t)block * 256 + threadIdx.x; e < (size_t)a.rows * outw; e += (size_t)nblocks * 256) {
     const int r = (int)(e / outw), c = (int)(e % outw);
     const float* x = a.X + (size_t)r * 32;
     const float* vx = a.varX + (size_t)r * 32;
@@ -49,17 +54,32 @@ __global__ __launch_bounds__(256) void small_product_vb_kernel(SmallProductVbArg
     a.outS2[(size_t)r * 32 + c] = (s2 - sq) + m * m;
   }
 }
-void launch_small_product_vb(const SmallProductVbArgs& a, hipStream_t st) {
+__global__ __launch_bounds__(256) void small_product_vb_kernel(SmallProductVbArgs a) { small_product_vb_body<0>(a, blockIdx.x, gridDim.x); }
+__host__ __device__ inline int small_product_vb_blocks(const SmallProductVbArgs& a) {
   const int outw = a.transposeS ? a.K : a.L;
-  const int blocks = (int)std::min<size_t>(2048, ((size_t)a.rows * outw + 255) / 256);
+  const size_t need = ((size_t)a.rows * outw + 255) / 256;
+  return (int)(need < 2048 ? need : 2048);
+}
+// List forms (many.h): blockIdx.z = model; a model whose own grid is smaller than the launch's leaves with the surplus blocks --
+// and strides by its OWN grid, so that every element is formed by the thread that forms it in the model's own launch.
+__global__ __launch_bounds__(256) void small_product_vb_many(const SmallProductVbArgs* list, int) {
+  const SmallProductVbArgs a = load_pack(list, blockIdx.z);
+  const int nb = small_product_vb_blocks(a);
+  if ((int)blockIdx.x >= nb) return;
+  small_product_vb_body<1>(a, blockIdx.x, (unsigned)nb);
+}
+void launch_small_product_vb(const SmallProductVbArgs& a, hipStream_t st) {
+  const int blocks = small_product_vb_blocks(a);
+  if (record_launch((const void*)small_product_vb_many, dim3(blocks), dim3(256), 0, a, true)) return;
   hipLaunchKernelGGL(small_product_vb_kernel, dim3(blocks), dim3(256), 0, st, a);
 }
 
 // mv[u][c] = sum over the unit's OBSERVED inner indices of V[.][c] = colsum_c - sum_{e in miss(u)} V[idx_e][c]:
 // one wave per unit, a 32-lane half takes one missing entry per trip (a coalesced 128-byte row of V), eight in flight
-__global__ __launch_bounds__(256) void masked_colsum_kernel(MaskedColsumArgs a) {
+template <int LIST>
+__device__ __forceinline__ void masked_colsum_body(MaskedColsumArgs a, int block) {
   const int lane = threadIdx.x & 63, half = lane >> 5, c = lane & 31;
-  const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int u = block * 4 + (threadIdx.x >> 6);
   if (u >= a.n) return;
   const uint32_t s0 = a.slot_ptr[u], s1 = a.slot_ptr[u + 1];
   float acc = 0.f;
@@ -75,8 +95,16 @@ __global__ __launch_bounds__(256) void masked_colsum_kernel(MaskedColsumArgs a) 
   acc += __shfl_xor(acc, 32, 64);
   if (half == 0) a.out[(size_t)u * 32 + c] = (float)(a.colsum2[c] - a.C64[(size_t)c * 32 + c]) - acc;   // sum var = sum S2 - sum E^2
 }
+__global__ __launch_bounds__(256) void masked_colsum_kernel(MaskedColsumArgs a) { masked_colsum_body<0>(a, (int)blockIdx.x); }
+__global__ __launch_bounds__(256) void masked_colsum_many(const MaskedColsumArgs* list, int) {
+  const MaskedColsumArgs a = load_pack(list, blockIdx.z);
+  if ((int)blockIdx.x >= (a.n + 3) / 4) return;
+  masked_colsum_body<1>(a, (int)blockIdx.x);
+}
 void launch_masked_colsum(const MaskedColsumArgs& a, hipStream_t st) {
-  if (a.n > 0) hipLaunchKernelGGL(masked_colsum_kernel, dim3((a.n + 3) / 4), dim3(256), 0, st, a);
+  if (a.n <= 0) return;
+  if (record_launch((const void*)masked_colsum_many, dim3((a.n + 3) / 4), dim3(256), 0, a, true)) return;
+  hipLaunchKernelGGL(masked_colsum_kernel, dim3((a.n + 3) / 4), dim3(256), 0, st, a);
 }
 
 
@@ -91,7 +119,10 @@ void launch_masked_colsum(const MaskedColsumArgs& a, hipStream_t st) {
 // evaluated behind the last step by every thread for its own entry, from the (mu, tau) the step stored; the barrier of a step
 // waits for LDS traffic only, so the rows of A~ prefetched for later steps stay in flight.
 // only_params: write mu/tau of the ordered entries, leave the moments alone (update_S without update_exp_S).
-__global__ __launch_bounds__(1024) void ssys_chain_vb_kernel(SSysChainVbArgs a) {
+// (LIST: the list form's own instantiation -- a body shared by two kernels is inlined differently into each, and the single-model
+// kernel keeps the code it had)
+template <int LIST>
+__device__ __forceinline__ void ssys_chain_vb_body(SSysChainVbArgs a) {
   constexpr int PF = 12;                                           // rows of A~ prefetched ahead of their step
   __shared__ float dl[2];
   __shared__ int ordl[1024 + PF], posl[1024];
@@ -165,6 +196,15 @@ __global__ __launch_bounds__(1024) void ssys_chain_vb_kernel(SSysChainVbArgs a) 
     }
   }
 }
+__global__ __launch_bounds__(1024) void ssys_chain_vb_kernel(SSysChainVbArgs a) { ssys_chain_vb_body<0>(a); }
+// list forms of the chain and the permutation: a recorded pack holds the order of the run's FIRST iteration; iteration `it`'s is
+// it * order_step entries behind it (the orders of a run_many call lie iteration by iteration: bnmtf_vb_run's layout)
+struct SSysChainVbPack { SSysChainVbArgs a; int order_step; int pad_; };
+__global__ __launch_bounds__(1024) void ssys_chain_vb_many(const SSysChainVbPack* list, int it) {
+  SSysChainVbPack p = load_pack(list, blockIdx.z);
+  p.a.order += (size_t)it * p.order_step;
+  ssys_chain_vb_body<1>(p.a);
+}
 
 // The same chain for a whole pass (every step with its moments), walked in BLOCKS of 64 steps (round 6).  The kernel above pays a
 // block barrier and two LDS round trips per step (0.28 us a step, 285 us for 1 024 entries at K = L = 32: 40 % of an iteration
@@ -186,16 +226,32 @@ __global__ __launch_bounds__(1024) void ssys_chain_vb_kernel(SSysChainVbArgs a) 
 // step): out of A~ itself those were 64-lane gathers inside 4 KiB rows -- ~28 cache lines a load instruction, 27 000 line requests
 // per block of the chain from ONE compute unit, which is what its hand-overs waited for (round 6: 10 000 cycles each) -- here all
 // 256 units share the gathers once and the chain's loads are contiguous.
-__global__ __launch_bounds__(256) void ssys_permute_kernel(const float* __restrict__ A, const int* __restrict__ order, int n, float* __restrict__ out) {
-  const int s = blockIdx.x;
+template <int LIST>
+__device__ __forceinline__ void ssys_permute_body(const float* __restrict__ A, const int* __restrict__ order, int n, float* __restrict__ out, int s) {
   const float* row = A + (size_t)order[s] * n;
   for (int p = threadIdx.x; p < n; p += 256) out[(size_t)s * n + p] = row[order[p]];
 }
-void launch_ssys_permute(const float* A, const int* order, int n, float* out, hipStream_t st) {
+__global__ __launch_bounds__(256) void ssys_permute_kernel(const float* __restrict__ A, const int* __restrict__ order, int n, float* __restrict__ out) {
+  ssys_permute_body<0>(A, order, n, out, (int)blockIdx.x);
+}
+struct SSysPermutePack { const float* A; const int* order; float* out; int n, order_step; };
+__global__ __launch_bounds__(256) void ssys_permute_many(const SSysPermutePack* list, int it) {
+  const SSysPermutePack p = load_pack(list, blockIdx.z);
+  if ((int)blockIdx.x >= p.n) return;
+  ssys_permute_body<1>(p.A, p.order + (size_t)it * p.order_step, p.n, p.out, (int)blockIdx.x);
+}
+void launch_ssys_permute(const float* A, const int* order, int n, float* out, hipStream_t st, int order_step) {
+  if (g_recorder) {
+    SSysPermutePack p; memset(&p, 0, sizeof(p));
+    p.A = A; p.order = order; p.out = out; p.n = n; p.order_step = order_step;
+    record_launch((const void*)ssys_permute_many, dim3(n), dim3(256), 0, p, true);
+    return;
+  }
   hipLaunchKernelGGL(ssys_permute_kernel, dim3(n), dim3(256), 0, st, A, order, n, out);
 }
 
-__global__ __launch_bounds__(1024) void ssys_chain_vb_blocked_kernel(SSysChainVbArgs a) {
+template <int LIST>
+__device__ __forceinline__ void ssys_chain_vb_blocked_body(SSysChainVbArgs a) {
   __shared__ __align__(16) float dlt[1024];
   __shared__ float diag[3 * 64 * 64 + 8 * 64];
   const int n2 = a.K * a.L, p = threadIdx.x, lane = p & 63, n_order = a.n_order;      // (n_order == n2: a whole pass)
@@ -345,11 +401,28 @@ __global__ __launch_bounds__(1024) void ssys_chain_vb_blocked_kernel(SSysChainVb
   }
 #endif
 }
-void launch_ssys_chain_vb(const SSysChainVbArgs& a, hipStream_t st) {
-  // BNMTF_VB_CHAIN=steps: the barrier-per-step kernel for whole passes too (A/B switch)
-  static const bool steps = [] { const char* e = getenv("BNMTF_VB_CHAIN"); return e && !strcmp(e, "steps"); }();
-  if (a.only_params || a.n_order < 64 || a.n_order > 1024 || a.n_order != a.K * a.L || !a.Aperm || steps) { hipLaunchKernelGGL(ssys_chain_vb_kernel, dim3(1), dim3(1024), 0, st, a); return; }
-  hipLaunchKernelGGL(ssys_chain_vb_blocked_kernel, dim3(1), dim3(((a.n_order + 63) / 64) * 64), 0, st, a);
+__global__ __launch_bounds__(1024) void ssys_chain_vb_blocked_kernel(SSysChainVbArgs a) { ssys_chain_vb_blocked_body<0>(a); }
+__global__ __launch_bounds__(1024) void ssys_chain_vb_blocked_many(const SSysChainVbPack* list, int it) {
+  SSysChainVbPack p = load_pack(list, blockIdx.z);
+  p.a.order += (size_t)it * p.order_step;
+  ssys_chain_vb_blocked_body<1>(p.a);
+}
+// BNMTF_VB_CHAIN=steps: the barrier-per-step kernel for whole passes too (A/B switch; no list form)
+static bool vb_chain_steps() { static const bool steps = [] { const char* e = getenv("BNMTF_VB_CHAIN"); return e && !strcmp(e, "steps"); }(); return steps; }
+bool trivb_ab_switch_set() { return vb_chain_steps(); }
+void launch_ssys_chain_vb(const SSysChainVbArgs& a, hipStream_t st, int order_step) {
+  const bool steps = vb_chain_steps();
+  const bool blocked = !(a.only_params || a.n_order < 64 || a.n_order > 1024 || a.n_order != a.K * a.L || !a.Aperm || steps);
+  const dim3 block(blocked ? ((a.n_order + 63) / 64) * 64 : 1024);
+  if (g_recorder) {
+    if (steps) { record_missing("ssys_chain_vb (BNMTF_VB_CHAIN=steps)"); return; }
+    SSysChainVbPack p; memset(&p, 0, sizeof(p));
+    p.a = a; p.order_step = order_step;
+    record_launch(blocked ? (const void*)ssys_chain_vb_blocked_many : (const void*)ssys_chain_vb_many, dim3(1), block, 0, p);
+    return;
+  }
+  if (!blocked) { hipLaunchKernelGGL(ssys_chain_vb_kernel, dim3(1), block, 0, st, a); return; }
+  hipLaunchKernelGGL(ssys_chain_vb_blocked_kernel, dim3(1), block, 0, st, a);
 }
 
 // fp64 factor matrices of the masked bilinear sums of exp_square_diff (:235-239), for metric_kernel (sum over the mask of
@@ -406,12 +479,13 @@ void launch_tri_factors(const TriFactorArgs& a, hipStream_t st) {
 // exp_square_diff's third term, sum_Omega varF . ((E[S] E[G]^T)^2 - E[S]^2 (E[G]^2)^T) (:238), as a sum over (j, k): the masked
 // sums mv[j][k] = sum_{i in Omega_j} varF_ik are what the G step's covariance term has just used (masked_colsum_kernel), the
 // bracket is a function of row j of E[G] and row k of E[S].  One thread per (j, k), fp64 partial sum per block.
-__global__ __launch_bounds__(256) void tri_third_kernel(TriThirdArgs a) {
+template <int LIST>
+__device__ __forceinline__ void tri_third_body(TriThirdArgs a, unsigned block) {
   __shared__ float Ss[32 * 32];
   __shared__ double red[4];
   for (int t = threadIdx.x; t < a.K * a.L; t += 256) Ss[t] = a.S[t];
   __syncthreads();
-  const int j = blockIdx.x * 8 + (threadIdx.x >> 5), k = threadIdx.x & 31;
+  const int j = block * 8 + (threadIdx.x >> 5), k = threadIdx.x & 31;
   double v = 0.0;
   if (j < a.rows && k < a.K) {
     const float* g = a.G + (size_t)j * 32;
@@ -423,11 +497,19 @@ __global__ __launch_bounds__(256) void tri_third_kernel(TriThirdArgs a) {
   for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
-  if (threadIdx.x == 0) a.part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  if (threadIdx.x == 0) a.part[block] = (red[0] + red[1]) + (red[2] + red[3]);
 }
+__global__ __launch_bounds__(256) void tri_third_kernel(TriThirdArgs a) { tri_third_body<0>(a, blockIdx.x); }
 int tri_third_blocks(int rows) { return (rows + 7) / 8; }
+__global__ __launch_bounds__(256) void tri_third_many(const TriThirdArgs* list, int) {
+  const TriThirdArgs a = load_pack(list, blockIdx.z);
+  if ((int)blockIdx.x >= (a.rows + 7) / 8) return;                  // (tri_third_blocks)
+  tri_third_body<1>(a, blockIdx.x);
+}
 void launch_tri_third(const TriThirdArgs& a, hipStream_t st) {
-  if (a.rows > 0) hipLaunchKernelGGL(tri_third_kernel, dim3(tri_third_blocks(a.rows)), dim3(256), 0, st, a);
+  if (a.rows <= 0) return;
+  if (record_launch((const void*)tri_third_many, dim3(tri_third_blocks(a.rows)), dim3(256), 0, a, true)) return;
+  hipLaunchKernelGGL(tri_third_kernel, dim3(tri_third_blocks(a.rows)), dim3(256), 0, st, a);
 }
 
 }  // namespace bnmtf

@@ -161,7 +161,8 @@ void launch_sweep_turns(const SweepArgs& a, const FastArgs& f, hipStream_t st);
 bool sweep_vb_supported(int KP, int pw);
 bool sweep_vb_cov_supported(int KP, int pw);   // ... with SweepArgs::cov_S / order: the tri-factorisation's F / G sweeps (K, L <= 32)
 int sweep_vb_blocks(int npairs, int nw = 8);  // blocks (= rows of FastArgs::stats) of a VB sweep over npairs pairs with nw unit waves per block (16 or 8)
-void launch_sweep_vb(const SweepArgs& a, const FastArgs& f, hipStream_t st);
+// order_step (recording, many.h; the tri-factorisation's sweeps): entries between the column orders of consecutive iterations
+void launch_sweep_vb(const SweepArgs& a, const FastArgs& f, hipStream_t st, int order_step = 0);
 void launch_vb_pieces(int n, int n0, int KP, int K, const float* mu, const float* tauq, const float* ex, const float* var,
                       const float* lambda, const float* asq, const float* vsq, double* out, hipStream_t st);
 // the same pieces with the two masked sums taken from the slabs of kernel_maskgemm.hip (the on-chip VB sweep)
@@ -355,6 +356,7 @@ struct SSysGemmArgs {       // slabs[s][p][r] = sum_{j in range s} Wc[j][p] Gc[j
 inline int ssys_gemm_wave_tiles(int K, int L) { return (tri_padded(K) / 64) * (tri_padded(L) / 64); }
 __host__ __device__ inline int ssys_gemm_range(int n, int nsplit) { return ((n + nsplit - 1) / nsplit + 15) & ~15; }     // columns per range of ssys_gemm_bf16_kernel: a multiple of a step
 void launch_ssys_gemm(const SSysGemmArgs& a, hipStream_t st);
+bool ssys_ab_switch_set();          // an A/B switch of kernel_ssys.hip that has no list form is set (BNMTF_SCOL_GRAM=f32, BNMTF_SSYS_GEMM=f32)
 struct SSysBArgs { int n, n0, K, L; const float* slabs; int split, n_pad; const float* G; float* b; };   // b[block][K L]: per 64-column block partials of sum_j Pv_jk G_jl
 inline int ssys_b_blocks(int n) { return (n + 63) / 64 > 0 ? (n + 63) / 64 : 1; }
 void launch_ssys_b(const SSysBArgs& a, hipStream_t st);
@@ -397,8 +399,10 @@ struct SSysChainVbArgs {
   float* E; float* var; float* mu; float* tauq;     // q(S): expS (in/out), varS, muS, tauS  [K L]
   const float* Aperm;                  // whole passes: A~ in the pass's order (launch_ssys_permute), or null
 };
-void launch_ssys_chain_vb(const SSysChainVbArgs& a, hipStream_t st);
-void launch_ssys_permute(const float* A, const int* order, int n, float* out, hipStream_t st);   // out[s][p] = A[order[s]][order[p]]
+// order_step (recording, many.h): entries between the orders of consecutive iterations -- the list form adds it x order_step to order
+void launch_ssys_chain_vb(const SSysChainVbArgs& a, hipStream_t st, int order_step = 0);
+void launch_ssys_permute(const float* A, const int* order, int n, float* out, hipStream_t st, int order_step = 0);   // out[s][p] = A[order[s]][order[p]]
+bool trivb_ab_switch_set();         // an A/B switch of kernel_trivb.hip that has no list form is set (BNMTF_VB_CHAIN=steps)
 struct TriFactorArgs { int which, side, rows, K, L; const float* X; const float* varX; const float* S; const float* varS; double* out; };
 void launch_tri_factors(const TriFactorArgs& a, hipStream_t st);
 // exp_square_diff's third term (bnmtf_vb_optimised.py:238) from the masked variance sums the G step already holds:

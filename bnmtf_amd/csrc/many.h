@@ -36,7 +36,8 @@ struct LaunchRec {
 struct Recorder {                      // (cleared per iteration: the vectors keep their capacity, a record costs a memcpy)
   std::vector<LaunchRec> recs;
   std::vector<unsigned char> arena;
-  void clear() { recs.clear(); arena.clear(); }
+  const char* missing = nullptr;       // a launcher without a list form was called while recording (record_missing): its kernel
+  void clear() { recs.clear(); arena.clear(); missing = nullptr; }
   const unsigned char* args(const LaunchRec& r) const { return arena.data() + r.off; }
 };
 extern thread_local Recorder* g_recorder;
@@ -51,6 +52,15 @@ inline bool record_launch(const void* many_fn, dim3 grid, dim3 block, size_t lds
   rc->arena.resize(rc->arena.size() + sizeof(P));
   memcpy(rc->arena.data() + r.off, &p, sizeof(P));
   rc->recs.push_back(r);
+  return true;
+}
+
+// A launcher that has no list form, called while a Recorder is installed: it launches nothing and says so here -- the caller
+// turns the iteration into an error (a kernel launched on the side, out of the batch's order, or left out, would be wrong bits).
+inline bool record_missing(const char* what) {
+  Recorder* rc = g_recorder;
+  if (!rc) return false;
+  if (!rc->missing) rc->missing = what;
   return true;
 }
 

@@ -263,6 +263,15 @@ BNMTF_API int bnmtf_vb_exp_square_diff(bnmtf_handle h, double* esd_out, double s
  * sum log tau, sum lambda exp} -- the K L terms of S and the scalar algebra are the host's. */
 BNMTF_API int bnmtf_vb_run(bnmtf_handle h, int n_iter, const int32_t* orders, double* exptau_out, double* perf_out,
                  double* elbo_terms_out, double* times_out);
+/* run(iterations) of n_models tri-factorisations on one device, walked in lock-step: every launch site of an iteration is ONE launch
+ * for all of them (csrc/many.h, api_trivb_many.inc) -- the reference's model searches (experiments_gdsc/cross_validation/vb_nmtf/
+ * greedysearch_xval_vb.py: folds x a greedy walk over K, L) are dozens to hundreds of independent models of 622 x 138.  Models may
+ * differ in shape and in K, L; every model ends with the bits of its own bnmtf_vb_run.  orders[b]: model b's [n_iter][K L + K + L]
+ * update orders (bnmtf_vb_run's).  Outputs model-major ([n_models][n_iter]..., as bnmtf_vb_run's; times = the batch's clock); any
+ * may be null.  Models that cannot share launches (several GPUs, kernel timers on, the 16-wave sweeps of large problems, an A/B
+ * switch) run one after the other.  launch_info (optional, 2 ints): the models that shared launches, the argument-list uploads. */
+BNMTF_API int bnmtf_vb_run_many(bnmtf_handle* hs, int n_models, int n_iter, const int32_t* const* orders, double* exptau_out,
+                      double* perf_out, double* elbo_terms_out, double* times_out, int* launch_info);
 
 /* ---- metrics: predict()/predict_while_running()/quality('MSE')/log_likelihood
  *      (:191-223,247-251).  Six fp64 sums over mask Mp (I x J bytes; NULL = the
