@@ -637,7 +637,7 @@ static bool vb_chip_ok(const Dir& d, const Dir& o) {
   if (d.vb_path != 0) return d.vb_path == 1;
   return d.KP == 64 && d.use_wide;
 }
-static void enqueue_post(bnmtf_model* h, Dir& d, bool vb = false) {
+static void enqueue_post(bnmtf_model* h, Dir& d, bool vb = false, hipStream_t st = nullptr) {      // st: null = the compute stream
   PostArgs g;
   memset(&g, 0, sizeof(g));
   g.X = d.X; g.rows = d.nglob; g.KP = d.KP; g.XT = d.XT; g.ldT = d.ldT; g.XT2 = d.XT2; g.ld2 = d.ldT;
@@ -651,7 +651,7 @@ static void enqueue_post(bnmtf_model* h, Dir& d, bool vb = false) {
     d.xb_umax_posted = d.xb_mpart != nullptr;
   } else d.xb_umax_posted = false;
   g.snap = d.snap_dst; g.snapW = d.W; d.snap_dst = nullptr;
-  launch_post(g, h->stream);
+  launch_post(g, st ? st : h->stream);
 }
 // Several GPUs, after a half sweep: the block of X this rank has just drawn goes to the other ranks (all-gather on the
 // exchange stream) WHILE the rank forms the Gram partial and the column sums of its own rows; the partials -- one buffer,
@@ -707,6 +707,65 @@ static int exchange_factor(bnmtf_model* h, Dir& d, Dir* next = nullptr, int next
   if (next) { enqueue_gemm(h, *next, d, next_kid, 2); next->gemm_ahead = true; }
   return BNMTF_OK;
 }
+// One GPU, bnmf_gibbs_run: what follows a half sweep -- the relayout and the Gram of the factor it wrote (post_kernel,
+// gram_reduce_kernel) and, behind the V sweep, the end of the iteration (finish_kernel, the posterior sums, the sample slot's
+// event) -- is read by nothing on the compute stream before the NEXT sweep: the contraction in between reads the factor's X
+// alone.  So it goes to a second stream, beside that contraction, which is HBM-bound with one wave per SIMD and leaves the
+// tail kernels the registers and the LDS they need (launch_post's note):
+//   main:  gemm_rows | sweep_rows | fork(0) | gemm_cols ............ | join(0) | sweep_cols | fork(1) | gemm_rows(it+1) ........ | join(1) | sweep_rows
+//   tail:                           wait    | post(U) | gram(U) | done(0)                     wait    | post(V) | gram(V) | finish | done(1)
+// Every reader is behind its join: sweep_cols reads U's XT / XT2 / C32, finish (on the tail stream, in order behind both
+// relayouts) both Grams, the V sweep's statistics and acc; the next sweep_rows reads V's layouts and the tau that finish wrote.
+// Write after read: sweep_rows(it+1) overwrites the U.X that post(U)(it) and the posterior sums of iteration it read -- both
+// joined before it, at join(0) and join(1) of iteration it; sweep_cols(it) overwrites the V.X that post(V)(it-1) read, joined
+// at join(1) of it-1; the memset of acc ahead of sweep_cols(it) follows join(1) of it-1, behind the finish that read it.  The
+// sample slots are written, and their events recorded and waited for, on the tail stream (SampleSink::writer).
+// BNMTF_TAIL=serial (read at bnmtf_create), a communicator, a small problem (tail_overlap_wanted) or any other loop: everything
+// on the compute stream, as before.
+// By default only where the contraction is long enough to hide the tail and to pay for the four cross-stream edges of an
+// iteration (a few microseconds each on the compute stream): measured, same box, against the parent -- 8192 x 8192: K = 64
+// +5.6 %, K = 32 +2.9 %; 4096 x 4096, K = 32, where the contraction is 16-21 us: -5.4 %.  Sizes in between
+// have not been measured and keep the one-stream order.  BNMTF_TAIL=overlap / serial forces either.
+static bool tail_overlap_wanted(const bnmtf_model* h) {
+  if (h->comm || h->world > 1 || h->L != 0) return false;
+  if (h->tail_mode != 0) return h->tail_mode == 1;
+  return (int64_t)h->I * h->J >= (int64_t)8192 * 8192;
+}
+struct TailOverlap {
+  bnmtf_model* h = nullptr;
+  bool on = false, pending[2] = {false, false};
+  int begin(bnmtf_model* h_) {
+    h = h_; on = tail_overlap_wanted(h);
+    if (!on) return BNMTF_OK;
+    // The four events order kernels of this one device against each other and nothing else (the sample copies and the host
+    // have events of their own), so they are recorded without the system-scope fence: with it every record wrote back and
+    // invalidated the L2 in the middle of the loop -- 7-8 us between a sweep's end and the contraction's start in the trace,
+    // and the whole gain of the second stream (measured: DESIGN.md section 7).
+    if (!h->tail_stream) HIPCHK(hipStreamCreateWithFlags(&h->tail_stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : h->ev_tail)
+      if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence));
+    return BNMTF_OK;
+  }
+  hipStream_t stream() const { return on ? h->tail_stream : h->stream; }
+  // the sweep of direction dir (0 rows, 1 cols) has been enqueued: what follows on the tail stream starts behind it
+  int fork(int dir) {
+    HIPCHK(hipEventRecord(h->ev_tail[2 * dir], h->stream));
+    HIPCHK(hipStreamWaitEvent(h->tail_stream, h->ev_tail[2 * dir], 0));
+    return BNMTF_OK;
+  }
+  int done(int dir) {
+    HIPCHK(hipEventRecord(h->ev_tail[2 * dir + 1], h->tail_stream));
+    pending[dir] = true;
+    return BNMTF_OK;
+  }
+  // the compute stream is about to enqueue the first reader of what the tail of direction dir made
+  int join(int dir) {
+    if (pending[dir]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_tail[2 * dir + 1], 0)); pending[dir] = false; }
+    return BNMTF_OK;
+  }
+  // an error return out of the loop leaves nothing running on the tail stream behind the caller's back
+  ~TailOverlap() { if (on && (pending[0] || pending[1])) (void)hipStreamSynchronize(h->tail_stream); }
+};
 // the summed Gram of d (C32, C64, colsum) is about to be read on the compute stream
 static int await_gram(bnmtf_model* h, Dir& d) {
   if (d.gram_pending) { HIPCHK(hipStreamWaitEvent(h->stream, d.ev_gram_all, 0)); d.gram_pending = false; }
@@ -837,6 +896,7 @@ struct SampleSink {
   static constexpr int kGroup = BNMTF_SAMPLE_GROUP, kGroups = 2, kDepth = kGroup * kGroups;
   struct Mat { const float* src; int rows, W, KP; float* dst; size_t off; };
   bnmtf_model* h = nullptr;
+  hipStream_t writer = nullptr;   // the stream whose kernels fill the slots: the compute stream, or the tail stream of bnmf_gibbs_run (TailOverlap)
   Mat m[3]; int nmat = 0;
   size_t per_it = 0;            // floats per iteration over all matrices
   bool active = false, direct = true;
@@ -854,8 +914,8 @@ struct SampleSink {
     if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
     return at.type == hipMemoryTypeHost;
   }
-  int begin(bnmtf_model* h_, int n_iter_) {
-    h = h_; n_iter = n_iter_; next_copy = 0;
+  int begin(bnmtf_model* h_, int n_iter_, hipStream_t writer_ = nullptr) {
+    h = h_; n_iter = n_iter_; next_copy = 0; writer = writer_ ? writer_ : h_->stream;
     if (nmat == 0) return BNMTF_OK;
     active = true;
     for (int i = 0; i < nmat; ++i) direct = direct && pinned(m[i].dst) && pinned(m[i].dst + (size_t)n_iter * m[i].rows * m[i].W - 1);
@@ -893,11 +953,12 @@ struct SampleSink {
     return BNMTF_OK;
   }
   // before iteration `it` is enqueued: at the start of a group its slots must have been taken to the host (the group two back)
+  // (the wait goes to the stream that writes the slots)
   int open_slot(int it) {
     if (!active || it % kGroup != 0 || it < kDepth) return BNMTF_OK;
     const int g = (it / kGroup) % kGroups;
     if (!direct) CHK(drain_group(g));
-    HIPCHK(hipStreamWaitEvent(h->stream, h->copy_done[g], 0));
+    HIPCHK(hipStreamWaitEvent(writer, h->copy_done[g], 0));
     return BNMTF_OK;
   }
   // where matrix `src` goes in the slot of iteration `it` (the relayout kernel that follows its sweep writes it there), or null
@@ -907,11 +968,11 @@ struct SampleSink {
       if (m[i].src == src) return h->snap_dev + (size_t)(it % kDepth) * per_it + m[i].off;
     return nullptr;
   }
-  // matrix `src` is final for iteration `it`: pack it into the slot (compute stream)
+  // matrix `src` is final for iteration `it`: pack it into the slot (writer stream)
   void snapshot(int it, const float* src) {
     if (!active) return;
     for (int i = 0; i < nmat; ++i)
-      if (m[i].src == src) launch_compact_rows(src, m[i].rows, m[i].W, m[i].KP, h->snap_dev + (size_t)(it % kDepth) * per_it + m[i].off, h->stream);
+      if (m[i].src == src) launch_compact_rows(src, m[i].rows, m[i].W, m[i].KP, h->snap_dev + (size_t)(it % kDepth) * per_it + m[i].off, writer);
   }
   // every matrix of iteration `it` is in its slot; at the end of a group the group goes to the copy stream -- and in the LAST group
   // of the run every iteration on its own: what is still to be copied when the last sweep has finished is then one iteration, not
@@ -922,7 +983,7 @@ struct SampleSink {
     if (it % kGroup != kGroup - 1 && it != n_iter - 1 && !last_group) return BNMTF_OK;
     const int first = next_copy, g = (it / kGroup) % kGroups;
     next_copy = it + 1;
-    HIPCHK(hipEventRecord(h->snap_ready[g], h->stream));
+    HIPCHK(hipEventRecord(h->snap_ready[g], writer));
     HIPCHK(hipStreamWaitEvent(h->copy_stream, h->snap_ready[g], 0));
 #ifdef BNMTF_EXPERIMENT_SAMPLES_NOCOPY
     constexpr bool nocopy = true;      // measurement build only (wrong results): the hand-off without its copies
@@ -996,11 +1057,12 @@ static int expectation_begin(bnmtf_model* h) {
   h->exp_count = 0;
   return BNMTF_OK;
 }
-static void expectation_add(bnmtf_model* h, int it) {
+static void expectation_add(bnmtf_model* h, int it, hipStream_t st = nullptr) {      // st: the stream of the iteration's finish kernel (null = the compute stream)
   if (h->exp_burn < 0 || it < h->exp_burn || (it - h->exp_burn) % h->exp_thin != 0) return;
-  launch_accumulate(h->rows.X, (size_t)h->rows.nglob * h->rows.KP, h->exp_rows, h->tau_d, h->exp_tau, h->stream);
-  launch_accumulate(h->cols.X, (size_t)h->cols.nglob * h->cols.KP, h->exp_cols, nullptr, nullptr, h->stream);
-  if (h->L > 0) launch_accumulate(h->S, (size_t)h->K * h->L, h->exp_S, nullptr, nullptr, h->stream);
+  if (!st) st = h->stream;
+  launch_accumulate(h->rows.X, (size_t)h->rows.nglob * h->rows.KP, h->exp_rows, h->tau_d, h->exp_tau, st);
+  launch_accumulate(h->cols.X, (size_t)h->cols.nglob * h->cols.KP, h->exp_cols, nullptr, nullptr, st);
+  if (h->L > 0) launch_accumulate(h->S, (size_t)h->K * h->L, h->exp_S, nullptr, nullptr, st);
   h->exp_count++;
 }
 
@@ -1051,6 +1113,10 @@ int bnmtf_create(const bnmtf_problem* p, bnmtf_handle* out) try {
   h->I = p->I; h->J = p->J; h->K = p->K; h->L = p->L;
   h->alpha = p->alpha; h->beta = p->beta; h->seed = p->seed;
   h->device = p->device; h->rank = p->rank; h->world = p->world;
+  // BNMTF_TAIL=serial: bnmf_gibbs_run keeps every kernel on the compute stream, in program order (the A/B of TailOverlap, and what
+  // tests/test_tail_overlap_gpu.py compares the two-stream order against, bit for bit); =overlap: the second stream whatever the
+  // size.  Read once, here.
+  if (const char* e = getenv("BNMTF_TAIL")) h->tail_mode = !strcmp(e, "serial") ? 2 : !strcmp(e, "overlap") ? 1 : 0;
   const int I = p->I, J = p->J;
   const float* R = p->R; const uint8_t* M = p->M;
 
@@ -1216,6 +1282,9 @@ static void describe_model(bnmtf_model* h) {
   snprintf(buf, sizeof(buf), " unit_sweep[rows=%d/%d/%d cols=%d/%d/%d]", (int)(h->rows.uw_ok && (!h->ho_enabled || h->uw_force)), h->rows.u_nw, h->rows.u_emax,
            (int)(h->cols.uw_ok && (!h->ho_enabled || h->uw_force)), h->cols.u_nw, h->cols.u_emax);
   h->description += buf;
+  // bnmf_gibbs_run's relayout / Gram / finish kernels: beside the contractions on a second stream, or in program order (BNMTF_TAIL)
+  h->description += tail_overlap_wanted(h) ? " tail=overlap" : " tail=serial";
+  if (h->tail_mode == 0) h->description += "(auto)";
   if (h->small) {
     snprintf(buf, sizeof(buf), " small[block=%d entry_threads=%d/%d slots=%d/%d lds=%zu std_built=%d]", h->small->nt, h->small->dev.rows.nthreads, h->small->dev.cols.nthreads,
              h->small->dev.rows.em, h->small->dev.cols.em, h->small->lds_bytes, (int)h->std_built);
@@ -1264,6 +1333,8 @@ int bnmtf_destroy(bnmtf_handle h) try {
   dfree(h->snap_dev);
   if (h->snap_host) (void)hipHostFree(h->snap_host);
   if (h->xchg_stream) { (void)hipStreamSynchronize(h->xchg_stream); (void)hipStreamDestroy(h->xchg_stream); }
+  if (h->tail_stream) { (void)hipStreamSynchronize(h->tail_stream); (void)hipStreamDestroy(h->tail_stream); }
+  for (hipEvent_t e : h->ev_tail) if (e) (void)hipEventDestroy(e);
   if (h->aux_stream) { (void)hipStreamSynchronize(h->aux_stream); (void)hipStreamDestroy(h->aux_stream); }
   if (h->ev_aux0) (void)hipEventDestroy(h->ev_aux0);
   if (h->ev_aux1) (void)hipEventDestroy(h->ev_aux1);
@@ -1452,10 +1523,13 @@ int bnmf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* 
   HIPCHK(hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));
   EventList ev;
   CHK(ev.create(times_out ? n_iter + 1 : 0));
+  TailOverlap tail;
+  CHK(tail.begin(h));
+  hipStream_t const tst = tail.stream();         // where the relayouts, the Grams and the end of the iteration go (TailOverlap)
   SampleSink sink;
   sink.add(r.X, h->I, r.W, r.KP, U_out);
   sink.add(c.X, h->J, c.W, c.KP, V_out);
-  CHK(sink.begin(h, n_iter));
+  CHK(sink.begin(h, n_iter, tst));
   CHK(expectation_begin(h));
   if (times_out) HIPCHK(hipEventRecord(ev[0], h->stream));
 
@@ -1465,6 +1539,7 @@ int bnmf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* 
     if (!r.gemm_ahead) enqueue_gemm(h, r, c, BNMTF_KERNEL_GEMM_ROWS);      // (several GPUs: launched inside the previous iteration's exchange of V)
     r.gemm_ahead = false;
     CHK(await_gram(h, c));                       // V^T V of the previous iteration's exchange
+    CHK(tail.join(1));                           // V's layouts and Gram, tau: the previous iteration's tail, which ran beside the contraction above
     {
       ScopedKernelTimer t(h, BNMTF_KERNEL_SWEEP_ROWS);
       SweepArgs s = sweep_args(h, r, c, mode, kStreamRows);
@@ -1476,13 +1551,18 @@ int bnmf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* 
     constexpr bool snap_compact = false;
 #endif
     if (!snap_compact) r.snap_dst = sink.slot_for(it, r.X);         // the sample of U goes out with the relayout (no packing kernel of its own)
-    CHK(exchange_factor(h, r, &c, BNMTF_KERNEL_GEMM_COLS));        // one GPU: relayout + Gram; several: see exchange_factor
+    if (tail.on) {                                                 // one GPU: relayout + Gram beside the contraction below
+      CHK(tail.fork(0));
+      enqueue_post(h, r, false, tst);
+      CHK(tail.done(0));
+    } else CHK(exchange_factor(h, r, &c, BNMTF_KERNEL_GEMM_COLS)); // one GPU (BNMTF_TAIL=serial): relayout + Gram; several: see exchange_factor
     if (snap_compact) sink.snapshot(it, r.X);
     // ---- V columns: Pv = R~^T . U
     if (!c.gemm_ahead) enqueue_gemm(h, c, r, BNMTF_KERNEL_GEMM_COLS);
     c.gemm_ahead = false;
     if (acc_used && it > 0) HIPCHK(hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));
     CHK(await_gram(h, r));
+    CHK(tail.join(0));
     {
       ScopedKernelTimer t(h, BNMTF_KERNEL_SWEEP_COLS);
       SweepArgs s = sweep_args(h, c, r, mode, kStreamCols);
@@ -1492,7 +1572,10 @@ int bnmf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* 
     const bool fast_stats = h->last_sweep_fast;
     if (h->comm && fast_stats) launch_sum_stats(c.stats, c.stats_blocks, h->acc, h->stream);   // fold the slab before the exchange
     if (!snap_compact) c.snap_dst = sink.slot_for(it, c.X);
-    CHK(exchange_factor(h, c, it + 1 < n_iter ? &r : nullptr, BNMTF_KERNEL_GEMM_ROWS));
+    if (tail.on) {
+      CHK(tail.fork(1));
+      enqueue_post(h, c, false, tst);
+    } else CHK(exchange_factor(h, c, it + 1 < n_iter ? &r : nullptr, BNMTF_KERNEL_GEMM_ROWS));
     if (snap_compact) sink.snapshot(it, c.X);
     if (h->comm) {
       // the three sums of the SSE identity: behind the Gram on the exchange stream (its event covers the fold above)
@@ -1513,12 +1596,16 @@ int bnmf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* 
     f.key0 = (uint32_t)h->seed; f.key1 = (uint32_t)(h->seed >> 32); f.it = (uint32_t)h->iteration;
     f.gunit = mode == kSweepDraw ? h->gunit + it : nullptr;
     f.tau_d = h->tau_d; f.tau_f = h->tau_f; f.rec = h->rec + (size_t)it * 5;
-    launch_finish(f, h->stream);
-    expectation_add(h, it);
-    if (times_out) HIPCHK(hipEventRecord(ev[it + 1], h->stream));
+    launch_finish(f, tst);
+    expectation_add(h, it, tst);
+    // the iteration's stamp: behind its finish kernel, on the stream that ran it (the last one of a call is behind everything the
+    // call enqueued: the compute stream's last kernel is the sweep this tail waited for)
+    if (times_out) HIPCHK(hipEventRecord(ev[it + 1], tst));
+    if (tail.on) CHK(tail.done(1));
     h->iteration++;
   }
   HIPCHK(hipStreamSynchronize(h->stream));
+  if (tail.on) { HIPCHK(hipStreamSynchronize(h->tail_stream)); tail.pending[0] = tail.pending[1] = false; }
   CHK(sink.finish());
   HIPCHK(hipGetLastError());
   ho_scope.commit();

@@ -57,13 +57,16 @@ void launch_gram(const GramArgs& a, hipStream_t st) {
 //   sum_Omega Rp^2 = <U^T U, V^T V> - sum_miss q^2 ;  sum_Omega Rp = (1^T U).(1^T V) - sum_miss q
 //   sum_Omega R Rp = sum (Pv o V)   (Pv = R~^T U only holds observed entries)
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void finish_kernel(FinishArgs a) {
+// Eight waves, one sum each: two per SIMD in 40 registers, so the block sits beside a contraction wave (launch_post's note).
+// The draw's Gamma variate comes from the host (FinishArgs::gunit): the fp64 Marsaglia-Tsang loop that used to be the fall-back
+// here was never taken by a caller and held 122 registers per lane.
+__global__ __launch_bounds__(kFinishThreads) void finish_kernel(FinishArgs a) {
   __shared__ double red[16];
   const int KP = a.KP, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (a.copy_dst)      // (round 6: S's sample was a device-to-device copy of 4 KB on the compute stream, 4.8 us of every iteration)
-    for (int t = threadIdx.x; t < a.copy_n; t += 1024) a.copy_dst[t] = a.copy_src[t];
+    for (int t = threadIdx.x; t < a.copy_n; t += kFinishThreads) a.copy_dst[t] = a.copy_src[t];
   // five sums, one per WAVE (round 5: every wave used to reduce four values over its lanes): waves 0-3 a quarter of <Cr, Cc> each,
-  // waves 4-6 one column of the per-block sweep statistics, wave 7 the column-sum product; the other waves have nothing to do
+  // waves 4-6 one column of the per-block sweep statistics, wave 7 the column-sum product
   double s = 0.0;
   if (wave < 4) {
     const int q4 = KP * KP / 4;                                    // (KP = 32 or 64: 4 or 16 terms per lane, all loads in flight)
@@ -97,8 +100,7 @@ __global__ __launch_bounds__(1024) void finish_kernel(FinishArgs a) {
     double tau;
     if (a.update == 2) tau = (alpha_s - 1.0) / beta_s;            // gamma_mode (distributions/gamma.py:27-29)
     else if (a.update != 0) tau = alpha_s / beta_s;
-    else if (a.gunit) tau = *a.gunit / beta_s;
-    else tau = gamma_draw_serial(alpha_s, beta_s, a.it, kStreamTau, a.key0, a.key1);
+    else tau = *a.gunit / beta_s;
     *a.tau_d = tau;
     *a.tau_f = (float)tau;
     const double ss_tot = a.sumR2 - a.sumR * a.sumR / n;
@@ -184,7 +186,7 @@ void launch_vb_finish(const VbFinishArgs& a, hipStream_t st) {
 }
 
 void launch_finish(const FinishArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(1024), 0, st, a);
+  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(kFinishThreads), 0, st, a);
 }
 
 // ---------------------------------------------------------------------------

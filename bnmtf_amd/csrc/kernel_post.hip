@@ -134,9 +134,9 @@ __device__ __forceinline__ void post_body(const PostArgs& a) {
   }
 }
 template <bool VB>
-__global__ __launch_bounds__(256) void post_kernel(PostArgs a) { post_body<VB>(a); }
+__global__ __launch_bounds__(kPostThreads) void post_kernel(PostArgs a) { post_body<VB>(a); }
 template <bool VB>       // list form (many.h): blockIdx.z = model
-__global__ __launch_bounds__(256) void post_many(const PostArgs* list, int) { post_body<VB>(load_pack(list, blockIdx.z)); }
+__global__ __launch_bounds__(kPostThreads) void post_many(const PostArgs* list, int) { post_body<VB>(load_pack(list, blockIdx.z)); }
 
 // 32 packed entries per block, 32 partial-slab strides per entry (thread = entry e + 32*g), summed through LDS in a fixed
 // order: ceil(PS/32) blocks of 1024 threads (+ one for the column sums), every slab read is a coalesced 256 B segment; a
@@ -172,19 +172,34 @@ __device__ __forceinline__ void gram_reduce_body(const PostArgs& a, int nblk) {
     // the extra block: column sums, in parallel with the Gram blocks.  Thread = column + 64 * group: a wave reads one
     // coalesced row of partials per load, eight loads in flight, 16 groups summed through LDS in a fixed order
     const int col = threadIdx.x & 63, grp = threadIdx.x >> 6;
+    // (the two sums one after the other, each with its eight loads in flight, and the bounds test only in the batch that needs
+    // it: side by side, with a test per load, they held 25 more registers than the Gram blocks below, and the kernel's register
+    // count decides whether it fits beside a contraction wave -- launch_post.  The additions and their order are the same.)
     double v = 0.0, v2 = 0.0;
-    if (col < KP)
-      for (int b0 = grp; b0 < nblk; b0 += 8 * 16) {
-        double w[8], w2[8];
+    for (int pass = 0; pass < (a.S2 ? 2 : 1); ++pass) {
+      const double* part = (pass == 0 ? a.spart : a.s2part) + col;
+      double acc = 0.0;
+      if (col < KP)
+        for (int b0 = grp; b0 < nblk; b0 += 8 * 16) {
+          if (b0 + 16 * 7 < nblk) {
+            double w[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int b = b0 + 16 * u;
-          w[u] = b < nblk ? a.spart[(size_t)b * KP + col] : 0.0;
-          w2[u] = (a.S2 && b < nblk) ? a.s2part[(size_t)b * KP + col] : 0.0;
+            for (int u = 0; u < 8; ++u) w[u] = part[(b0 + 16 * u) * KP];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc += w[u];
+          } else {
+#pragma unroll 1
+            for (int u0 = 0; u0 < 8; u0 += 4) {        // the last batch: four at a time, a term beyond the last block loaded clamped and counted as zero
+              double w[4];
+#pragma unroll
+              for (int u = 0; u < 4; ++u) w[u] = part[min(b0 + 16 * (u0 + u), nblk - 1) * KP];
+#pragma unroll
+              for (int u = 0; u < 4; ++u) acc += b0 + 16 * (u0 + u) < nblk ? w[u] : 0.0;
+            }
+          }
         }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { v += w[u]; v2 += w2[u]; }
-      }
+      if (pass == 0) v = acc; else v2 = acc;
+    }
     red[threadIdx.x] = v;
     __syncthreads();
     if (grp == 0 && col < KP) {
@@ -215,9 +230,13 @@ __device__ __forceinline__ void gram_reduce_body(const PostArgs& a, int nblk) {
   red[threadIdx.x] = s;
   __syncthreads();
   if (g == 0 && t < PS) {                // one barrier, then 32 threads add the 32 strides in a fixed order
+    // (sixteen LDS reads in flight at a time, not all 32: 64 registers of operands were what kept this kernel from fitting
+    // beside a contraction wave -- launch_post; the order of the additions is the same)
     double tot = 0.0;
+#pragma unroll 1
+    for (int j0 = 0; j0 < 32; j0 += 16)
 #pragma unroll
-    for (int j = 0; j < 32; ++j) tot += red[e + 32 * j];
+      for (int j = j0; j < j0 + 16; ++j) tot += red[e + 32 * j];
     int ty, tx;
     tri_tile(t >> 4, NT, &ty, &tx);
     const int row = 4 * ty + ((t >> 2) & 3), col = 4 * tx + (t & 3);
@@ -225,13 +244,16 @@ __device__ __forceinline__ void gram_reduce_body(const PostArgs& a, int nblk) {
     if (ty != tx) { a.C64[col * KP + row] = tot; a.C32[col * KP + row] = (float)tot; }    // the mirror tile
   }
 }
-__global__ __launch_bounds__(1024) void gram_reduce_kernel(PostArgs a, int nblk) { gram_reduce_body(a, nblk); }
+__global__ __launch_bounds__(kGramReduceThreads) void gram_reduce_kernel(PostArgs a, int nblk) { gram_reduce_body(a, nblk); }
 struct GramReducePack { PostArgs a; int nblk; int pad_; };
-__global__ __launch_bounds__(1024) void gram_reduce_many(const GramReducePack* list, int) {
+__global__ __launch_bounds__(kGramReduceThreads) void gram_reduce_many(const GramReducePack* list, int) {
   const GramReducePack p = load_pack(list, blockIdx.z);
   gram_reduce_body(p.a, p.nblk);
 }
 
+// Both kernels are written to be co-resident with the contraction (kernel_gemm.hip: one wave per SIMD holding 312 of its 512
+// registers at KP = 64, 64 KB of LDS), which the one-GPU Gibbs loop runs beside them on another stream (api.hip: TailOverlap):
+// post_kernel one wave per SIMD, gram_reduce_kernel four, in at most 48 registers each (tests/test_tail_resources_cpu.py).
 void launch_post(const PostArgs& a0, hipStream_t st) {
   PostArgs a = a0;
   a.do_layout = 1; a.do_gram = 1; a.blk0 = 0; a.own0 = 0; a.own1 = a.rows;
@@ -239,19 +261,19 @@ void launch_post(const PostArgs& a0, hipStream_t st) {
   const int nt = a.KP / 4, ps = nt * (nt + 1) / 2 * 16;
   const int extra = (a.S2 && a.mpart && a.umax) ? 2 : 1;      // the column-sum block, and (VB with the masked sums) the column-maximum block
   if (g_recorder) {
-    record_launch(a.S2 ? (const void*)post_many<true> : (const void*)post_many<false>, dim3(nblk, 2), dim3(256), 0, a);
+    record_launch(a.S2 ? (const void*)post_many<true> : (const void*)post_many<false>, dim3(nblk, 2), dim3(kPostThreads), 0, a);
     GramReducePack p; memset(&p, 0, sizeof(p)); p.a = a; p.nblk = nblk;
-    record_launch((const void*)gram_reduce_many, dim3((ps + 31) / 32 + extra), dim3(1024), 0, p);
+    record_launch((const void*)gram_reduce_many, dim3((ps + 31) / 32 + extra), dim3(kGramReduceThreads), 0, p);
     return;
   }
-  if (a.S2) hipLaunchKernelGGL(post_kernel<true>, dim3(nblk, 2), dim3(256), 0, st, a); else hipLaunchKernelGGL(post_kernel<false>, dim3(nblk, 2), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(gram_reduce_kernel, dim3((ps + 31) / 32 + extra), dim3(1024), 0, st, a, nblk);
+  if (a.S2) hipLaunchKernelGGL(post_kernel<true>, dim3(nblk, 2), dim3(kPostThreads), 0, st, a); else hipLaunchKernelGGL(post_kernel<false>, dim3(nblk, 2), dim3(kPostThreads), 0, st, a);
+  hipLaunchKernelGGL(gram_reduce_kernel, dim3((ps + 31) / 32 + extra), dim3(kGramReduceThreads), 0, st, a, nblk);
 }
 
 void launch_post_layout(const PostArgs& a0, hipStream_t st) {
   PostArgs a = a0;
   a.do_layout = 1; a.do_gram = 0; a.blk0 = 0; a.own0 = 0; a.own1 = a.rows;
-  if (a.S2) hipLaunchKernelGGL(post_kernel<true>, dim3(post_blocks(a.rows), 1), dim3(256), 0, st, a); else hipLaunchKernelGGL(post_kernel<false>, dim3(post_blocks(a.rows), 1), dim3(256), 0, st, a);
+  if (a.S2) hipLaunchKernelGGL(post_kernel<true>, dim3(post_blocks(a.rows), 1), dim3(kPostThreads), 0, st, a); else hipLaunchKernelGGL(post_kernel<false>, dim3(post_blocks(a.rows), 1), dim3(kPostThreads), 0, st, a);
 }
 
 void launch_post_gram_rows(const PostArgs& a0, int own0, int own1, hipStream_t st) {
@@ -259,9 +281,9 @@ void launch_post_gram_rows(const PostArgs& a0, int own0, int own1, hipStream_t s
   a.do_layout = 0; a.do_gram = 1; a.own0 = own0; a.own1 = own1;
   a.blk0 = own0 / kPostRows;
   const int nblk = own1 > own0 ? (own1 + kPostRows - 1) / kPostRows - a.blk0 : 0;
-  if (nblk > 0) { if (a.S2) hipLaunchKernelGGL(post_kernel<true>, dim3(nblk, 1), dim3(256), 0, st, a); else hipLaunchKernelGGL(post_kernel<false>, dim3(nblk, 1), dim3(256), 0, st, a); }
+  if (nblk > 0) { if (a.S2) hipLaunchKernelGGL(post_kernel<true>, dim3(nblk, 1), dim3(kPostThreads), 0, st, a); else hipLaunchKernelGGL(post_kernel<false>, dim3(nblk, 1), dim3(kPostThreads), 0, st, a); }
   const int nt = a.KP / 4, ps = nt * (nt + 1) / 2 * 16;
-  hipLaunchKernelGGL(gram_reduce_kernel, dim3((ps + 31) / 32 + 1), dim3(1024), 0, st, a, nblk);     // no rows: zeros
+  hipLaunchKernelGGL(gram_reduce_kernel, dim3((ps + 31) / 32 + 1), dim3(kGramReduceThreads), 0, st, a, nblk);     // no rows: zeros
 }
 
 __global__ void gram_cast_kernel(const double* C64, float* C32, int n) {

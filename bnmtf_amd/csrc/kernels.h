@@ -219,6 +219,9 @@ void launch_handover_build(const HandoverArgs& a, hipStream_t st);
 void launch_gram_cast(const double* C64, float* C32, int n, hipStream_t st);      // C32 = (float) C64 after the partial sums were all-reduced
 constexpr int kPostRows = 32;
 inline int post_blocks(int rows) { return (rows + kPostRows - 1) / kPostRows; }
+// threads per block of the kernels behind a half sweep (post_kernel, gram_reduce_kernel) and of the end of a Gibbs iteration
+// (finish_kernel): with their register counts, what lets them run beside the contraction (tests/test_tail_resources_cpu.py)
+constexpr int kPostThreads = 256, kGramReduceThreads = 1024, kFinishThreads = 512;
 
 // ---------------------------------------------------------------------------
 // end of iteration: masked SSE from Gram identities, tau draw, metrics record
@@ -231,7 +234,7 @@ struct FinishArgs {
   double alpha, beta;
   int update;                 // 0 draw, 1 mode (tau = alpha_s/beta_s), 2 ICM (tau = (alpha_s - 1)/beta_s, gamma_mode)
   uint32_t key0, key1, it;
-  const double* gunit;        // Gamma(alpha_s, 1) variate of this iteration computed ahead on the host, or null (draw here)
+  const double* gunit;        // update 0: the Gamma(alpha_s, 1) variate of this iteration, computed ahead on the host (stage_gamma_variates); else unused
   double* tau_d; float* tau_f;
   double* rec;                // [5]: tau, MSE, R2, Rp, SSE  (slot of this iteration)
   const float* copy_src; float* copy_dst; int copy_n;     // a small array that rides along (the tri-factorisation's sample of S into its slot), or null

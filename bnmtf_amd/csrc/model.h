@@ -131,6 +131,10 @@ struct bnmtf_model {
   hipStream_t stream = nullptr;
   hipStream_t aux_stream = nullptr; hipEvent_t ev_aux0 = nullptr, ev_aux1 = nullptr;   // BNMTF S step: the b side of the system beside the A side (api_models.inc)
   hipStream_t xchg_stream = nullptr;    // several GPUs: every collective is issued here, beside the compute stream
+  // one GPU, bnmf_gibbs_run: the relayout / Gram / end-of-iteration kernels run here, beside the next contraction on `stream`
+  // (api.hip: TailOverlap).  ev_tail: sweep done (main -> tail) and tail done (tail -> main), per direction.  Created on first use.
+  hipStream_t tail_stream = nullptr; hipEvent_t ev_tail[4] = {nullptr, nullptr, nullptr, nullptr};
+  int tail_mode = 0;                    // BNMTF_TAIL as it stood when the handle was created: 0 unset (by size: tail_overlap_wanted), 1 `overlap`, 2 `serial` (everything on `stream`, in program order)
   bnmtf::Dir rows, cols;
   // full-matrix copies for predict()/validation
   float* Rfull = nullptr; uint8_t* Mtrain = nullptr; uint8_t* Mscratch = nullptr;
