@@ -4,18 +4,17 @@
 
 The reference fits the candidates of a model search -- folds x ranks x restarts -- one after the other
 (code/cross_validation/line_search_cross_validation.py:54-131, line_search_bnmf.py:53-76) or in a process pool
-(parallel_matrix_cross_validation.py:40-74).  Small BNMF and BNMTF Gibbs models run on the device as ONE block each
-(csrc/kernel_small.hip), so a list of them is one launch per kind; models that do not qualify are run in turn.  Variational models
-(bnmf_vb_optimised, any size its 8-wave kernels serve) walk their iterations in lock-step: every kernel of an iteration is ONE
-launch for all of them (csrc/many.h, api_many.inc: bnmf_vb_run_many), each model ending with the bits of its own run().  So do the
-variational tri-factorisations (bnmtf_vb_optimised: their run(iterations)), of any shapes and ranks together: every launch site of
-an iteration is ONE launch for all of them (csrc/api_trivb_many.inc: bnmtf_vb_run_many); their update orders are drawn from
-Python's `random` model by model, in list order, before the device call -- as the models' own run() calls one after the other
-would draw them.  Models wider than 64 columns (column blocks, _blocked.py: several handles per model) of any of these kinds are
-run by their own run().
-The non-probabilistic models (nmf_np.NMF, nmtf_np.NMTF: their run(iterations)) walk their iterations in lock-step too, NMF and
-NMTF of any shapes and ranks together: every launch site of an iteration is ONE launch for all of them (csrc/api_np_many.inc:
-bnmtf_np_run_many).  ICM models (nmf_icm: their own run(), update rule and minimum_TN) are not taken: ReplicaPool runs them one by one."""
+(parallel_matrix_cross_validation.py:40-74).  Here a list of them shares launches, in one of two ways:
+
+  one launch      small BNMF and BNMTF Gibbs models run on the device as ONE block each (csrc/kernel_small.hip): the models of a
+                  device and a kind are one launch; models that do not qualify are run in turn.
+  lock-step       bnmf_vb_optimised, bnmtf_vb_optimised, nmf_np.NMF and nmtf_np.NMTF models (their run(iterations)) walk their
+                  iterations together: every launch site of an iteration is ONE launch for the models of a device and a family
+                  (csrc/many.h, api_many.inc; the families: _LOCKSTEP), models of any shapes and ranks together, NMF with NMTF.
+                  Each model ends with the bits of its own run().
+
+Models wider than 64 columns (column blocks, _blocked.py: several handles per model) are run by their own run().  ICM models
+(nmf_icm: their own run(), update rule and minimum_TN) are not taken: ReplicaPool runs them one by one."""
 import ctypes as C
 import time
 
@@ -29,42 +28,34 @@ def takes(model):
     return _kind(model) is not None
 
 
-def _kind(model):
+def _kinds():
+    """kind -> (class whose run() run_many stands in for, the attributes an instance must have been given)"""
     from .bnmf_gibbs import bnmf_gibbs_optimised
     from .bnmtf_gibbs import bnmtf_gibbs_optimised
-    if isinstance(model, bnmf_gibbs_optimised) and type(model).run is bnmf_gibbs_optimised.run:
-        return "bnmf"
-    if isinstance(model, bnmtf_gibbs_optimised) and type(model).run is bnmtf_gibbs_optimised.run:
-        return "bnmtf"
     from .bnmf_vb import bnmf_vb_optimised
-    if isinstance(model, bnmf_vb_optimised) and type(model).run is bnmf_vb_optimised.run:
-        return "vb"
     from .bnmtf_vb import bnmtf_vb_optimised
-    if isinstance(model, bnmtf_vb_optimised) and type(model).run is bnmtf_vb_optimised.run:
-        return "trivb"
     from .nmf_np import NMF
     from .nmtf_np import NMTF
-    # (taken once initialise() has given it its factors: run() of a model without them fails its assertion, run_many refuses it)
-    if isinstance(model, NMF) and type(model).run is NMF.run and all(hasattr(model, f) for f in "UV"):
-        return "np"
-    if isinstance(model, NMTF) and type(model).run is NMTF.run and all(hasattr(model, f) for f in "FSG"):
-        return "np"
+    # (NMF / NMTF: taken once initialise() has given them their factors -- run() of a model without them fails its assertion)
+    return (("bnmf", bnmf_gibbs_optimised, ""), ("bnmtf", bnmtf_gibbs_optimised, ""), ("vb", bnmf_vb_optimised, ""),
+            ("trivb", bnmtf_vb_optimised, ""), ("np", NMF, "UV"), ("np", NMTF, "FSG"))
+
+
+def _kind(model):
+    for kind, cls, needs in _kinds():
+        if isinstance(model, cls) and type(model).run is cls.run and all(hasattr(model, f) for f in needs):
+            return kind
     return None
 
 
 def run_many(models, iterations, update='draw', store_samples=True, expectation=None, orders=None):
-    """run(iterations, update, store_samples, expectation) of every model in `models` (bnmf_gibbs_optimised and / or
-    bnmtf_gibbs_optimised instances), with the models of the one-launch path that share a device and a kind sharing a single
-    launch; bnmf_vb_optimised instances (their run(iterations)): the models of a device walk their iterations in lock-step, one
-    launch per kernel for all of them (csrc/api_many.inc).  A Gibbs model wider than 64 columns (column blocks) is run by its own
-    run(iterations, update, store_samples, expectation).  bnmtf_vb_optimised instances (their run(iterations)): the models of a
-    device walk their iterations in lock-step, one launch per launch site for all of them (csrc/api_trivb_many.inc); their update
-    orders are drawn with _draw_orders, model by model in list order, before the device call -- Python's `random` ends as after
-    their run() calls one after the other.  orders (optional): a list as long as `models` whose entry for a bnmtf_vb_optimised is
-    the [iterations][K L + K + L] orders of its run(iterations, orders) (None: drawn here), None for every other model.  NMF / NMTF
-    instances (their run(iterations); update, store_samples and expectation do not apply): the models of a device walk their
-    iterations in lock-step, one launch per launch site for all of them (csrc/api_np_many.inc).  Returns the list of the runs'
-    results, in the order of `models`."""
+    """Every model of `models` (see `takes`) as after its own run(): run(iterations, update, store_samples, expectation) for the
+    Gibbs models, run(iterations) for the others (update, store_samples and expectation do not apply to them).  How they share
+    launches: the module's docstring.  The update orders of the bnmtf_vb_optimised models are drawn with _draw_orders, model by
+    model in list order, before any device call -- Python's `random` ends as after their run() calls one after the other.  orders
+    (optional): a list as long as `models` whose entry for a bnmtf_vb_optimised is the [iterations][K L + K + L] orders of its
+    run(iterations, orders) (None: drawn here), None for every other model.  Returns the list of the runs' results, in the order of
+    `models`."""
     models = list(models)
     if not models:
         return []
@@ -84,9 +75,9 @@ def run_many(models, iterations, update='draw', store_samples=True, expectation=
     # (the shuffles of every tri-factorisation first, in list order: what their run() calls one after the other draw)
     tri_orders = [models[i]._draw_orders(int(iterations)) if orders is None or orders[i] is None
                   else np.ascontiguousarray(orders[i], dtype=np.int32) for i in tri]
-    _run_many_vb([m for m in models if _kind(m) == "vb"], int(iterations))
-    _run_many_trivb([models[i] for i in tri], tri_orders, int(iterations))
-    _run_many_np([m for m in models if _kind(m) == "np"], int(iterations))
+    _run_lockstep("vb", [m for m in models if _kind(m) == "vb"], int(iterations))
+    _run_lockstep("trivb", [models[i] for i in tri], int(iterations), tri_orders)
+    _run_lockstep("np", [m for m in models if _kind(m) == "np"], int(iterations))
     for i, m in enumerate(models):
         if _kind(m) in ("bnmf", "bnmtf") and m._blocks is not None:
             out[i] = m.run(iterations, update, store_samples, expectation)
@@ -116,69 +107,42 @@ def run_many(models, iterations, update='draw', store_samples=True, expectation=
     return out
 
 
-def _run_many_vb(ms, it):
-    """bnmf_vb_optimised.run(it) of every model of `ms` (bnmf_vb_optimised.py:121-153): per device one bnmf_vb_run_many call;
-    models wider than 64 columns (column blocks) run on their own."""
+# The lock-step families: kind -> (what puts a model's state on the device, the C entry point, the trailing shapes of its
+# model-major [models][iterations] output arrays, in the order the entry point and the models' _run_finish take them; the batch's
+# clock follows them).  bnmf_vb_optimised.py:121-153, bnmtf_vb_optimised.py:160-205, nmf_np.py:87-107, nmtf_np.py:116-144.
+_LOCKSTEP = {
+    "vb": (lambda m, it: m._push(), "bnmf_vb_run_many", ((), (3,), (10,))),            # exptau, perf, the ELBO's terms
+    "trivb": (lambda m, it: m._push(), "bnmtf_vb_run_many", ((), (3,), (10,))),
+    "np": (lambda m, it: m._run_prepare(it), "bnmtf_np_run_many", ((3,), ())),         # perf, the I-divergence
+}
+
+
+def _run_lockstep(kind, ms, it, orders=None):
+    """run(it) of every model of `ms`, all of one lock-step family: per device one call of the family's entry point (orders: per
+    model the update orders its run(it, orders) would take, for the family whose entry point takes them); models in column blocks
+    run on their own."""
+    prepare, entry, shapes = _LOCKSTEP[kind]
     by_device = {}
-    for m in ms:
-        if m._blocks is not None:
+    for i, m in enumerate(ms):
+        if getattr(m, "_blocks", None) is not None:
             m.run(it)
         else:
-            by_device.setdefault(m._device, []).append(m)
-    for group in by_device.values():
+            by_device.setdefault(m._device, []).append(i)
+    for idx in by_device.values():
+        group = [ms[i] for i in idx]
         n = len(group)
         for m in group:
-            m._push()
-        hs = (C.c_void_p * n)(*[m._handle().value for m in group])
-        exptau = np.zeros((n, it)); perf = np.zeros((n, it, 3)); terms = np.zeros((n, it, 10)); times = np.zeros((n, it))
+            prepare(m, it)
+        args = [(C.c_void_p * n)(*[m._handle().value for m in group]), n, it]
+        if orders is not None:
+            for i in idx:
+                assert orders[i].shape == (it, ms[i].K * ms[i].L + ms[i].K + ms[i].L), (orders[i].shape, it, ms[i].K, ms[i].L)
+            args.append((C.c_void_p * n)(*[orders[i].ctypes.data for i in idx]))
+        outs = [np.zeros((n, it) + shape) for shape in shapes] + [np.zeros((n, it))]
         info = np.zeros(2, dtype=np.int32)
         t0 = time.perf_counter()
-        _lib.check(_lib.lib().bnmf_vb_run_many(hs, n, it, _lib.ptr(exptau), _lib.ptr(perf), _lib.ptr(terms), _lib.ptr(times), _lib.ptr(info)))
+        _lib.check(getattr(_lib.lib(), entry)(*args, *[_lib.ptr(o) for o in outs], _lib.ptr(info)))
         dt = time.perf_counter() - t0
-        for i, m in enumerate(group):
-            m._run_finish(it, exptau[i], perf[i], terms[i], times[i])
-            m._many_info = (int(info[0]), int(info[1]), dt)     # models that shared launches, argument-list uploads, seconds of the device call
-
-
-def _run_many_trivb(ms, orders, it):
-    """bnmtf_vb_optimised.run(it, orders) of every model of `ms` (bnmtf_vb_optimised.py:160-205) with its orders: per device one
-    bnmtf_vb_run_many call."""
-    by_device = {}
-    for m, o in zip(ms, orders):
-        assert o.shape == (it, m.K * m.L + m.K + m.L), (o.shape, it, m.K, m.L)
-        by_device.setdefault(m._device, []).append((m, o))
-    for group in by_device.values():
-        n = len(group)
-        for m, _ in group:
-            m._push()
-        hs = (C.c_void_p * n)(*[m._handle().value for m, _ in group])
-        ords = (C.c_void_p * n)(*[o.ctypes.data for _, o in group])
-        exptau = np.zeros((n, it)); perf = np.zeros((n, it, 3)); terms = np.zeros((n, it, 10)); times = np.zeros((n, it))
-        info = np.zeros(2, dtype=np.int32)
-        t0 = time.perf_counter()
-        _lib.check(_lib.lib().bnmtf_vb_run_many(hs, n, it, ords, _lib.ptr(exptau), _lib.ptr(perf), _lib.ptr(terms), _lib.ptr(times), _lib.ptr(info)))
-        dt = time.perf_counter() - t0
-        for i, (m, _) in enumerate(group):
-            m._run_finish(it, exptau[i], perf[i], terms[i], times[i])
-            m._many_info = (int(info[0]), int(info[1]), dt)     # models that shared launches, argument-list uploads, seconds of the device call
-
-
-def _run_many_np(ms, it):
-    """NMF.run(it) / NMTF.run(it) of every model of `ms` (nmf_np.py:87-107, nmtf_np.py:116-144): per device one bnmtf_np_run_many
-    call, NMF and NMTF together."""
-    by_device = {}
-    for m in ms:
-        by_device.setdefault(m._device, []).append(m)
-    for group in by_device.values():
-        n = len(group)
-        for m in group:
-            m._run_prepare(it)
-        hs = (C.c_void_p * n)(*[m._handle().value for m in group])
-        perf = np.zeros((n, it, 3)); idiv = np.zeros((n, it)); times = np.zeros((n, it))
-        info = np.zeros(2, dtype=np.int32)
-        t0 = time.perf_counter()
-        _lib.check(_lib.lib().bnmtf_np_run_many(hs, n, it, _lib.ptr(perf), _lib.ptr(idiv), _lib.ptr(times), _lib.ptr(info)))
-        dt = time.perf_counter() - t0
-        for i, m in enumerate(group):
-            m._run_finish(it, perf[i], idiv[i], times[i])
+        for j, m in enumerate(group):
+            m._run_finish(it, *[o[j] for o in outs])
             m._many_info = (int(info[0]), int(info[1]), dt)     # models that shared launches, argument-list uploads, seconds of the device call

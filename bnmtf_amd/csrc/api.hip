@@ -102,8 +102,29 @@ struct EventList {
     return BNMTF_OK;
   }
   hipEvent_t operator[](size_t i) const { return ev[i]; }
+  // out[it] = seconds from ev[0] to ev[it + 1], the stamp behind iteration `it` (the stream is drained); out may be null
+  void seconds(int n_iter, double* out) const {
+    for (int it = 0; out && it < n_iter; ++it) { float ms = 0.f; (void)hipEventElapsedTime(&ms, ev[0], ev[it + 1]); out[it] = (double)ms * 1e-3; }
+  }
   ~EventList() { for (auto e : ev) (void)hipEventDestroy(e); }
 };
+// the variational models' record of n_iter iterations of 16 doubles each: [0] exptau, [1..3] MSE / R^2 / Rp, [4..13] the ELBO's
+// terms; any output may be null
+static void unpack_vb_rec(const double* rec, int n_iter, double* exptau, double* perf, double* terms) {
+  for (int it = 0; it < n_iter; ++it) {
+    const double* q = rec + (size_t)it * 16;
+    if (exptau) exptau[it] = q[0];
+    if (perf) for (int m = 0; m < 3; ++m) perf[(size_t)it * 3 + m] = q[1 + m];
+    if (terms) for (int m = 0; m < 10; ++m) terms[(size_t)it * 10 + m] = q[4 + m];
+  }
+}
+static int vb_reserve_rec(bnmtf_model* h, int n_iter) {      // room on the device for that record
+  if (h->vb_rec_cap >= (size_t)n_iter) return BNMTF_OK;
+  dfree(h->vb_rec); h->vb_rec_cap = 0;
+  CHK(dalloc(&h->vb_rec, (size_t)n_iter * 16));
+  h->vb_rec_cap = n_iter;
+  return BNMTF_OK;
+}
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
@@ -1615,12 +1636,8 @@ int bnmf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* 
   for (int it = 0; it < n_iter; ++it) {
     if (tau_out) tau_out[it] = rec[(size_t)it * 5];
     if (perf_out) for (int m = 0; m < 3; ++m) perf_out[(size_t)it * 3 + m] = rec[(size_t)it * 5 + 1 + m];
-    if (times_out) {
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, ev[0], ev[it + 1]);
-      times_out[it] = (double)ms * 1e-3;
-    }
   }
+  ev.seconds(n_iter, times_out);
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
@@ -1866,7 +1883,5 @@ int bnmtf_gamma_sample(double alpha, double beta, uint64_t seed, uint64_t it, in
 
 #include "api_models.inc"
 #include "api_trivb.inc"
-#include "api_many.inc"
-#include "api_trivb_many.inc"
 #include "api_np.inc"
-#include "api_np_many.inc"
+#include "api_many.inc"

@@ -1,10 +1,13 @@
-// Many variational models, one launch per kernel (round 6; many.h).  The reference's model searches
-// (experiments_gdsc/cross_validation/vb_nmf/linesearch_xval_vb.py:17-52: 10 folds x 4 ranks of a 622 x 138 matrix) are dozens
-// of independent small models; a kernel of one of them occupies a few dozen blocks of the chip and its iteration is a chain of
-// eleven dependent launches.  bnmf_vb_run_many walks the models' iterations in lock-step: the host code of a model's iteration
-// runs with a Recorder installed (the launchers append their list-form kernel and arguments instead of launching), then the
-// records of a launch site become ONE launch with blockIdx.z = model.  The kernels' bodies are the single-model kernels' bodies:
-// every model ends with the bits its own bnmf_vb_run gives.
+// Many models, one launch per launch site (many.h) -- included at the end of api.hip.  The reference's model searches (a
+// cross-validation's folds x ranks, a greedy walk over K, L: experiments_gdsc/cross_validation/) are dozens to hundreds of independent
+// small models; a kernel of one of them occupies a few dozen blocks of the chip, and its iteration is a chain of dependent launches
+// (eleven for bnmf_vb, ~25 for bnmtf_vb with its S chain on one block, K L + 9 for NMTF).  run_many walks the models' iterations in
+// lock-step: the host code of a model's iteration runs with a Recorder installed (the launchers append their list-form kernel, its
+// arguments and the site key instead of launching), then the records of a site that agree in kernel, block and grid become ONE
+// launch with blockIdx.z = model.  Records meet by key, not by position, so models may differ in shape, rank and kind: a shorter S
+// chain has no record at the later passes, a call's first bnmtf_vb iteration forms R~^T E[F] and the column Grams inside the S system
+// and later ones do not.  The list forms run the single-model kernels' bodies: every model ends with the bits of its own run.
+// A family of models (ManyFamily) brings what differs; the three entry points below marshal their arguments and call run_many.
 
 namespace bnmtf { thread_local Recorder* g_recorder = nullptr; }
 
@@ -20,6 +23,22 @@ bool vb_batchable(bnmtf_model* h) {
     if (!fast || d->use_wide) return false;
   }
   return !(vb_chip_ok(h->rows, h->cols) && vb_chip_ok(h->cols, h->rows));
+}
+
+// a model whose iteration consists of kernels that have a list form: one GPU, no per-kernel timers, the overlapped passes over R~,
+// both sweeps on the pair-panel kernel with the covariance term in its 8 + 2-wave shape, no A/B switch without a list form
+bool trivb_batchable(bnmtf_model* h) {
+  if (h->comm || h->profiling || !h->tri_ready || !h->have_state || h->block_mode || !tri_overlap(h)) return false;
+  if (ssys_ab_switch_set() || trivb_ab_switch_set() || getenv("BNMTF_VB_GENERIC")) return false;
+  if (vb_chip_ok(h->rows, h->cols) && vb_chip_ok(h->cols, h->rows)) return false;          // (BNMTF_VB_PATH=masked: the generic sweep)
+  for (int which : {0, 2}) {
+    const Dir& d = which == 0 ? h->rows : h->cols;
+    const Dir& e = which == 0 ? h->ceff : h->reff;
+    if (!(h->use_fast && d.fast_ok && d.wide_can && d.pair_ok && d.f_gen_count == 0 && sweep_vb_cov_supported(d.KP, d.pw) && e.XS && e.XT2) ||
+        d.use_wide)
+      return false;
+  }
+  return true;
 }
 
 struct ManySite {
@@ -81,51 +100,80 @@ int launch_sites(std::vector<Recorder>& recs, const SiteMembers& at, std::vector
   return BNMTF_OK;
 }
 
-// the records of one iteration, site by site: every model enqueues the same launches in the same order (the variational path)
-int launch_recorded(std::vector<Recorder>& recs, std::vector<std::unique_ptr<ManySite>>& sites, int it, hipStream_t st, long* uploads) {
-  const size_t nm = recs.size(), ns = recs[0].recs.size();
-  for (size_t m = 1; m < nm; ++m)
-    if (recs[m].recs.size() != ns) { set_error("run_many: model %d enqueues %d launches an iteration, model 0 %d", (int)m, (int)recs[m].recs.size(), (int)ns); return BNMTF_ESTATE; }
-  SiteMembers at(ns);
-  for (size_t s = 0; s < ns; ++s)
-    for (size_t m = 0; m < nm; ++m) at[s].push_back({(int)m, (int)s});
-  return launch_sites(recs, at, sites, it, st, uploads);
-}
-
 struct RecorderScope {
   explicit RecorderScope(Recorder* r) { g_recorder = r; }
   ~RecorderScope() { g_recorder = nullptr; }
 };
 
-}  // namespace
 
-extern "C" {
+// at[s]: the records of site s, the sites in key order
+void align_sites(const std::vector<Recorder>& recs, SiteMembers& at) {
+  std::map<std::pair<int, int>, size_t> order;
+  for (const Recorder& r : recs)
+    for (const auto& k : r.keys) order[k] = 0;
+  size_t n = 0;
+  for (auto& o : order) o.second = n++;
+  at.assign(n, {});
+  for (size_t i = 0; i < recs.size(); ++i)
+    for (size_t q = 0; q < recs[i].keys.size(); ++q) at[order[recs[i].keys[q]]].push_back({(int)i, (int)q});
+}
 
-// bnmf_vb_run of n_models models (one device).  Outputs per model, model-major: exptau_out[n_models][n_iter],
-// perf_out[n_models][n_iter][3], elbo_terms_out[n_models][n_iter][10], times_out[n_models][n_iter] (the batch's clock: every model
-// of a batch finishes an iteration together); any of them may be null.  Models that cannot join a batch (several GPUs, the
-// 16-wave shapes of large problems, per-kernel timers on) are run one after the other.  *launch_info (optional, 2 ints): models
-// that shared launches, argument-list uploads.
-int bnmf_vb_run_many(bnmtf_handle* hs, int n_models, int n_iter, double* exptau_out, double* perf_out, double* elbo_terms_out, double* times_out,
-                     int* launch_info) try {
-  if (launch_info) launch_info[0] = launch_info[1] = 0;
-  if (n_models <= 0 || !hs) return n_models == 0 ? BNMTF_OK : BNMTF_EINVAL;
-  if (n_iter <= 0) return n_iter == 0 ? BNMTF_OK : BNMTF_EINVAL;
+// a model's slices of the model-major outputs: the family's (up to three) arrays and the batch's clock; any may be null
+struct ManyOut { double* a[3]; double* times; };
+
+// What a family of models brings to run_many.
+struct ManyFamily {
+  const char* name;                    // the entry point, for messages
+  int width[3];                        // doubles per model and iteration of the family's output arrays (0: no such array)
+  bool takes_orders;                   // per model the update orders of its run (bnmtf_vb)
+  bool handover;                       // a HandoverScope per batched model, as the model's own run holds one
+  bool same_length;                    // no site is named: every model enqueues the same launches, aligned by position
+  int (*ready)(bnmtf_model*, int b);   // the right kind of handle, with a state -- or the message and the code
+  bool (*batchable)(bnmtf_model*);     // its iteration consists of kernels that have a list form
+  int (*prepare)(bnmtf_model*, int n_iter, const int32_t* orders);     // before the model's own stream is drained
+  int (*enqueue)(bnmtf_model*, int it);                                // one recorded iteration
+  int (*run_alone)(bnmtf_model*, int n_iter, const int32_t* orders, const ManyOut& o);   // the model's own entry point
+  int (*read_out)(bnmtf_model*, int n_iter, const ManyOut& o);         // the device record -> the family's outputs
+};
+
+int check_many_handles(const ManyFamily& f, bnmtf_handle* hs, int n_models, int n_iter, const int32_t* const* orders) {
+  if (n_models < 0 || (n_models > 0 && (!hs || (f.takes_orders && !orders)))) {
+    set_error("%s: %d models at %p, orders at %p", f.name, n_models, (void*)hs, (const void*)orders);
+    return BNMTF_EINVAL;
+  }
+  if (n_iter < 0) { set_error("run: negative iteration count"); return BNMTF_EINVAL; }
   for (int b = 0; b < n_models; ++b) {
     if (!hs[b]) { set_error("run_many: null handle (model %d)", b); return BNMTF_EINVAL; }
-    if (!hs[b]->vb_ready || !hs[b]->have_state) { set_error("bnmf_vb_run_many before bnmf_vb_set_state (model %d)", b); return BNMTF_ESTATE; }
-    if (hs[b]->device != hs[0]->device) { set_error("run_many: the models of a call share a device"); return BNMTF_EINVAL; }
     for (int c = 0; c < b; ++c) if (hs[c] == hs[b]) { set_error("run_many: model %d is given twice", b); return BNMTF_EINVAL; }
+    if (hs[b]->device != hs[0]->device) { set_error("run_many: the models of a call share a device (model %d: device %d, model 0: device %d)", b, hs[b]->device, hs[0]->device); return BNMTF_EINVAL; }
+    CHK(f.ready(hs[b], b));
+    if (f.takes_orders && n_iter > 0 && !orders[b]) { set_error("%s: orders required (model %d)", f.name, b); return BNMTF_EINVAL; }
   }
-  auto out = [&](double* base, int b, int per) { return base ? base + (size_t)b * n_iter * per : nullptr; };
+  return BNMTF_OK;
+}
+
+// n_iter iterations of n_models models of one family on one device.  The models that can share launches -- two at least -- walk in
+// lock-step on the first one's stream; the others run through their own entry point one after the other.  *launch_info (optional,
+// 2 ints): models that shared launches, argument-list uploads.
+int run_many(const ManyFamily& f, bnmtf_handle* hs, int n_models, int n_iter, const int32_t* const* orders, double* const (&outs)[3],
+             double* times_out, int* launch_info) {
+  if (launch_info) launch_info[0] = launch_info[1] = 0;
+  CHK(check_many_handles(f, hs, n_models, n_iter, orders));
+  if (n_models == 0 || n_iter == 0) return BNMTF_OK;
+  auto out = [&](int b) {
+    ManyOut o;
+    for (int k = 0; k < 3; ++k) o.a[k] = outs[k] ? outs[k] + (size_t)b * n_iter * f.width[k] : nullptr;
+    o.times = times_out ? times_out + (size_t)b * n_iter : nullptr;
+    return o;
+  };
   std::vector<int> batch;
-  for (int b = 0; b < n_models; ++b) if (vb_batchable(hs[b])) batch.push_back(b);
+  for (int b = 0; b < n_models; ++b) if (f.batchable(hs[b])) batch.push_back(b);
   if (batch.size() < 2) batch.clear();
   {
     std::vector<char> in(n_models, 0);
     for (int b : batch) in[b] = 1;
     for (int b = 0; b < n_models; ++b)
-      if (!in[b]) CHK(bnmf_vb_run(hs[b], n_iter, out(exptau_out, b, 1), out(perf_out, b, 3), out(elbo_terms_out, b, 10), out(times_out, b, 1)));
+      if (!in[b]) CHK(f.run_alone(hs[b], n_iter, orders ? orders[b] : nullptr, out(b)));
   }
   if (batch.empty()) return BNMTF_OK;
   HIPCHK(hipSetDevice(hs[0]->device));
@@ -133,9 +181,8 @@ int bnmf_vb_run_many(bnmtf_handle* hs, int n_models, int n_iter, double* exptau_
   std::vector<std::unique_ptr<HandoverScope>> scopes;
   for (int b : batch) {
     bnmtf_model* h = hs[b];
-    if (h->vb_rec_cap < (size_t)n_iter) { dfree(h->vb_rec); CHK(dalloc(&h->vb_rec, (size_t)n_iter * 16)); h->vb_rec_cap = n_iter; }
-    scopes.push_back(std::make_unique<HandoverScope>(h));
-    HIPCHK(hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));
+    CHK(f.prepare(h, n_iter, orders ? orders[b] : nullptr));
+    if (f.handover) scopes.push_back(std::make_unique<HandoverScope>(h));
     HIPCHK(hipStreamSynchronize(h->stream));           // (everything the model's own stream still holds -- its state's upload -- before the batch's stream reads it)
   }
   hipStream_t st = hs[batch[0]]->stream;
@@ -143,34 +190,122 @@ int bnmf_vb_run_many(bnmtf_handle* hs, int n_models, int n_iter, double* exptau_
   CHK(ev.create(times_out ? n_iter + 1 : 0));
   if (times_out) HIPCHK(hipEventRecord(ev[0], st));
   std::vector<Recorder> recs(nb);
+  std::vector<std::vector<std::pair<int, int>>> last(nb);
+  SiteMembers at;
   std::vector<std::unique_ptr<ManySite>> sites;
   long uploads = 0;
   for (int it = 0; it < n_iter; ++it) {
+    bool same = it > 0;
     for (size_t i = 0; i < nb; ++i) {
       recs[i].clear();
       RecorderScope scope(&recs[i]);
-      CHK(enqueue_vb_iteration(hs[batch[i]], it, true));
-      if (recs[i].missing) { set_error("run_many: a recorded variational iteration met a kernel without a list form (%s)", recs[i].missing); return BNMTF_ESTATE; }
+      CHK(f.enqueue(hs[batch[i]], it));
+      if (recs[i].missing) { set_error("run_many: a recorded iteration met a kernel without a list form (%s)", recs[i].missing); return BNMTF_ESTATE; }
+      if (recs[i].keys.size() != recs[i].recs.size()) { set_error("run_many: model %d has %zu records and %zu site keys", batch[i], recs[i].recs.size(), recs[i].keys.size()); return BNMTF_ESTATE; }
+      if (f.same_length && recs[i].recs.size() != recs[0].recs.size()) { set_error("run_many: model %d enqueues %d launches an iteration, model 0 %d", (int)i, (int)recs[i].recs.size(), (int)recs[0].recs.size()); return BNMTF_ESTATE; }
+      same = same && recs[i].keys == last[i];
     }
-    CHK(launch_recorded(recs, sites, it, st, &uploads));
+    if (!same) {                                       // (the first iteration of a call may differ from the later ones)
+      align_sites(recs, at);
+      for (size_t i = 0; i < nb; ++i) last[i] = recs[i].keys;
+    }
+    CHK(launch_sites(recs, at, sites, it, st, &uploads));
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], st));
   }
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
   if (launch_info) { launch_info[0] = (int)nb; launch_info[1] = (int)uploads; }
-  std::vector<double> rec((size_t)n_iter * 16);
+  std::vector<double> tm(times_out ? n_iter : 0);
+  ev.seconds((int)tm.size(), tm.data());
   for (int b : batch) {
-    HIPCHK(hipMemcpy(rec.data(), hs[b]->vb_rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
-    double *e = out(exptau_out, b, 1), *p = out(perf_out, b, 3), *t = out(elbo_terms_out, b, 10), *tm = out(times_out, b, 1);
-    for (int it = 0; it < n_iter; ++it) {
-      const double* q = &rec[(size_t)it * 16];
-      if (e) e[it] = q[0];
-      if (p) for (int m = 0; m < 3; ++m) p[(size_t)it * 3 + m] = q[1 + m];
-      if (t) for (int m = 0; m < 10; ++m) t[(size_t)it * 10 + m] = q[4 + m];
-      if (tm) { float ms = 0.f; (void)hipEventElapsedTime(&ms, ev[0], ev[it + 1]); tm[it] = (double)ms * 1e-3; }
-    }
+    const ManyOut o = out(b);
+    CHK(f.read_out(hs[b], n_iter, o));
+    if (o.times) std::copy(tm.begin(), tm.end(), o.times);
   }
   return BNMTF_OK;
+}
+
+int vb_read_out(bnmtf_model* h, int n_iter, const ManyOut& o) {
+  std::vector<double> rec((size_t)n_iter * 16);
+  HIPCHK(hipMemcpy(rec.data(), h->vb_rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
+  unpack_vb_rec(rec.data(), n_iter, o.a[0], o.a[1], o.a[2]);
+  return BNMTF_OK;
+}
+// (acc: zeroed on the model's own stream, which the driver drains next)
+int vb_prepare(bnmtf_model* h, int n_iter, const int32_t*) {
+  CHK(vb_reserve_rec(h, n_iter));
+  HIPCHK(hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));
+  return BNMTF_OK;
+}
+
+// bnmf_vb_optimised: every model enqueues the same eleven launches.  Not batched: several GPUs, the 16-wave shapes of large
+// problems, per-kernel timers on.
+const ManyFamily kVbFamily = {
+  "bnmf_vb_run_many", {1, 3, 10}, false, true, true,
+  [](bnmtf_model* h, int b) { if (h->vb_ready && h->have_state) return BNMTF_OK; set_error("bnmf_vb_run_many before bnmf_vb_set_state (model %d)", b); return BNMTF_ESTATE; },
+  vb_batchable, vb_prepare,
+  [](bnmtf_model* h, int it) { return enqueue_vb_iteration(h, it, true); },
+  [](bnmtf_model* h, int n_iter, const int32_t*, const ManyOut& o) { return bnmf_vb_run(h, n_iter, o.a[0], o.a[1], o.a[2], o.times); },
+  vb_read_out};
+
+// bnmtf_vb_optimised: the sites of TriSite; the orders of a model's run are uploaded before the loop (the list forms step through
+// them).  Not batched: several GPUs, per-kernel timers, the 16-wave sweeps, an A/B switch.
+const ManyFamily kTriVbFamily = {
+  "bnmtf_vb_run_many", {1, 3, 10}, true, false, false,
+  [](bnmtf_model* h, int b) { if (h->tri_ready && h->have_state) return BNMTF_OK; set_error("bnmtf_vb_run_many before bnmtf_vb_set_state (model %d)", b); return BNMTF_ESTATE; },
+  trivb_batchable,
+  [](bnmtf_model* h, int n_iter, const int32_t* orders) {
+    const size_t n = (size_t)n_iter * ((size_t)h->K * h->L + h->K + h->L);
+    if (h->tri_order_cap < n) { dfree(h->tri_order); h->tri_order_cap = 0; CHK(dalloc(&h->tri_order, n, false)); h->tri_order_cap = n; }
+    HIPCHK(hipMemcpy(h->tri_order, orders, n * sizeof(int), hipMemcpyHostToDevice));
+    return vb_prepare(h, n_iter, nullptr);
+  },
+  [](bnmtf_model* h, int it) { return enqueue_trivb_iteration(h, it, true); },
+  [](bnmtf_model* h, int n_iter, const int32_t* orders, const ManyOut& o) { return bnmtf_vb_run(h, n_iter, orders, o.a[0], o.a[1], o.a[2], o.times); },
+  vb_read_out};
+
+// nmf_np.NMF and nmtf_np.NMTF in any mix: the sites of NpSite; every model with a state is batched.
+const ManyFamily kNpFamily = {
+  "bnmtf_np_run_many", {3, 1, 0}, false, false, false,
+  [](bnmtf_model* h, int b) {
+    if (!h->np) { set_error("run_many: model %d is not a handle of bnmtf_np_create", b); return BNMTF_EINVAL; }
+    if (!h->np->have_state) { set_error("bnmtf_np_run_many before set_state (model %d)", b); return BNMTF_ESTATE; }
+    return BNMTF_OK;
+  },
+  [](bnmtf_model*) { return true; },
+  [](bnmtf_model* h, int n_iter, const int32_t*) { return np_reserve_rec(h->np, n_iter); },
+  [](bnmtf_model* h, int) { return np_iteration(h, h->np->rec); },
+  [](bnmtf_model* h, int n_iter, const int32_t*, const ManyOut& o) { HIPCHK(hipSetDevice(h->device)); return np_run(h, n_iter, o.a[0], o.a[1], o.times); },
+  [](bnmtf_model* h, int n_iter, const ManyOut& o) {
+    std::vector<double> rec((size_t)n_iter * 8);
+    HIPCHK(hipMemcpy(rec.data(), h->np->rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
+    unpack_np_rec(rec.data(), n_iter, o.a[0], o.a[1]);
+    return BNMTF_OK;
+  }};
+
+}  // namespace
+
+extern "C" {
+
+// The *_run of n_models models on one device (include/bnmtf_hip.h).  Outputs per model, model-major, any of them null:
+// exptau_out[n_models][n_iter], perf_out[n_models][n_iter][3], elbo_terms_out[n_models][n_iter][10], idiv_out[n_models][n_iter],
+// times_out[n_models][n_iter] (the batch's clock: the models of a batch finish an iteration together).  orders[b]: model b's
+// [n_iter][K L + K + L] update orders (bnmtf_vb_run's).
+int bnmf_vb_run_many(bnmtf_handle* hs, int n_models, int n_iter, double* exptau_out, double* perf_out, double* elbo_terms_out, double* times_out,
+                     int* launch_info) try {
+  double* const outs[3] = {exptau_out, perf_out, elbo_terms_out};
+  return run_many(kVbFamily, hs, n_models, n_iter, nullptr, outs, times_out, launch_info);
+} BNMTF_ABI_GUARD
+
+int bnmtf_vb_run_many(bnmtf_handle* hs, int n_models, int n_iter, const int32_t* const* orders, double* exptau_out, double* perf_out,
+                      double* elbo_terms_out, double* times_out, int* launch_info) try {
+  double* const outs[3] = {exptau_out, perf_out, elbo_terms_out};
+  return run_many(kTriVbFamily, hs, n_models, n_iter, orders, outs, times_out, launch_info);
+} BNMTF_ABI_GUARD
+
+int bnmtf_np_run_many(bnmtf_handle* hs, int n_models, int n_iter, double* perf_out, double* idiv_out, double* times_out, int* launch_info) try {
+  double* const outs[3] = {perf_out, idiv_out, nullptr};
+  return run_many(kNpFamily, hs, n_models, n_iter, nullptr, outs, times_out, launch_info);
 } BNMTF_ABI_GUARD
 
 }  // extern "C"

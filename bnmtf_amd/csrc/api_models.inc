@@ -400,8 +400,8 @@ int bnmtf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* F_out, float*
   for (int it = 0; it < n_iter; ++it) {
     if (tau_out) tau_out[it] = rec[(size_t)it * 5];
     if (perf_out) for (int m = 0; m < 3; ++m) perf_out[(size_t)it * 3 + m] = rec[(size_t)it * 5 + 1 + m];
-    if (times_out) { float ms = 0.f; (void)hipEventElapsedTime(&ms, ev[0], ev[it + 1]); times_out[it] = (double)ms * 1e-3; }
   }
+  ev.seconds(n_iter, times_out);
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
@@ -771,7 +771,7 @@ int bnmf_vb_run(bnmtf_handle h, int n_iter, double* exptau_out, double* perf_out
   if (n_iter <= 0) return n_iter == 0 ? BNMTF_OK : BNMTF_EINVAL;
   HIPCHK(hipSetDevice(h->device));
   Dir& r = h->rows; Dir& c = h->cols;
-  if (h->vb_rec_cap < (size_t)n_iter) { dfree(h->vb_rec); CHK(dalloc(&h->vb_rec, (size_t)n_iter * 16)); h->vb_rec_cap = n_iter; }
+  CHK(vb_reserve_rec(h, n_iter));
   EventList ev;
   CHK(ev.create(times_out ? n_iter + 1 : 0));
   if (times_out) HIPCHK(hipEventRecord(ev[0], h->stream));
@@ -790,13 +790,8 @@ int bnmf_vb_run(bnmtf_handle h, int n_iter, double* exptau_out, double* perf_out
   drain_events(h);
   std::vector<double> rec((size_t)n_iter * 16);
   HIPCHK(hipMemcpy(rec.data(), h->vb_rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (int it = 0; it < n_iter; ++it) {
-    const double* q = &rec[(size_t)it * 16];
-    if (exptau_out) exptau_out[it] = q[0];
-    if (perf_out) for (int m = 0; m < 3; ++m) perf_out[(size_t)it * 3 + m] = q[1 + m];
-    if (elbo_terms_out) for (int m = 0; m < 10; ++m) elbo_terms_out[(size_t)it * 10 + m] = q[4 + m];
-    if (times_out) { float ms = 0.f; (void)hipEventElapsedTime(&ms, ev[0], ev[it + 1]); times_out[it] = (double)ms * 1e-3; }
-  }
+  unpack_vb_rec(rec.data(), n_iter, exptau_out, perf_out, elbo_terms_out);
+  ev.seconds(n_iter, times_out);
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 

@@ -81,27 +81,23 @@ static void np_enqueue_sweep(bnmtf_model* h, bool rows, float* Xt, const float* 
 static void np_gst(bnmtf_model* h) { NpState* s = h->np; launch_np_small_product(s->S, h->L, 1, s->Xc, h->L, h->K, h->J, s->Y, h->stream); }
 static void np_fs(bnmtf_model* h) { NpState* s = h->np; launch_np_small_product(s->S, 1, h->L, s->Xr, h->K, h->L, h->I, s->Y, h->stream); }
 
-// While a Recorder is installed (api_np_many.inc), the site key (phase, index) of every record: the records of the models of a
-// batch are aligned by key -- phase 0 before the S step, phase 1 its passes (index = pass), phase 2 after it -- not by position.
-struct NpSiteKeys {
-  std::vector<std::pair<int, int>> key;
-  static void mark(NpSiteKeys* k, int phase, int index) {
-    if (k && g_recorder) while (k->key.size() < g_recorder->recs.size()) k->key.push_back({phase, index++});
-  }
-};
+// The launch sites of a recorded iteration (many.h: site_at; api_many.inc), as (phase, index): the records of the models of a batch
+// are aligned by site, not by position -- phase 0 before the S step, phase 1 its passes (index = pass), phase 2 after it: (2, 0) S's
+// copy, (2, 1) G S^T, (2, 2) the F sweep, (2, 3) (F S)^T, (2, 4) and (2, 5) the G sweep and its sums.  NMF's two sweeps meet NMTF's.
+enum NpSite { kNpBeforeS, kNpSPass, kNpAfterS };
 
 // S entries [e0, e1) in row-major order (nmtf_np.py:127-129 for the whole range), one pass per entry plus one that finishes
 // the last; S2 receives the new values and becomes S.  Recorded (the whole range only): no copy of S into S2 beforehand --
 // the passes finish every entry -- and S2 is copied back into S instead of the swap, so that the arguments of every
 // iteration are the same.
-static int np_s_step(bnmtf_model* h, int e0, int e1, NpSiteKeys* keys = nullptr) {
+static int np_s_step(bnmtf_model* h, int e0, int e1) {
   NpState* s = h->np;
   const int nb = np_s_blocks(h->I);
   const bool recording = g_recorder != nullptr;
   if (recording && (e0 != 0 || e1 != h->K * h->L)) { set_error("np_s_step: a recorded S step covers all of S"); return BNMTF_ESTATE; }
+  site_at(kNpBeforeS);
   np_gst(h);
   launch_np_build_p(s->Rn, s->Xr, s->Y, h->I, h->J, h->K, s->P, h->stream);
-  NpSiteKeys::mark(keys, 0, 0);
   if (!recording) HIPCHK(hipMemcpyAsync(s->S2, s->S, (size_t)h->K * h->L * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   NpSPassArgs a; memset(&a, 0, sizeof(a));
   a.Rn = s->Rn; a.P = s->P; a.Ft = s->Xr; a.Gt = s->Xc; a.S_in = s->S; a.S_out = s->S2;
@@ -111,32 +107,48 @@ static int np_s_step(bnmtf_model* h, int e0, int e1, NpSiteKeys* keys = nullptr)
     a.cur = e < e1 ? e : -1;
     a.part_prev = s->spart + (size_t)((e + 1) & 1) * nb * 2;
     a.part_cur = s->spart + (size_t)(e & 1) * nb * 2;
+    site_at(kNpSPass, e - e0);
     launch_np_s_pass(a, h->stream);
-    NpSiteKeys::mark(keys, 1, e - e0);
   }
+  site_at(kNpAfterS);
   if (recording) record_np_copy(s->S2, s->S, h->K * h->L);
   else std::swap(s->S, s->S2);
-  NpSiteKeys::mark(keys, 2, 0);
   return BNMTF_OK;
 }
 
-// One iteration on h->stream -- or, while a Recorder is installed, into its records with their site keys (stats_out: then the
+// One iteration on h->stream -- or, while a Recorder is installed, into its records, each under its site (stats_out: then the
 // run's first record; the list-form end-of-iteration kernel finds the iteration's own).
-static int np_iteration(bnmtf_model* h, double* stats_out, NpSiteKeys* keys = nullptr) {
+static int np_iteration(bnmtf_model* h, double* stats_out) {
   NpState* s = h->np;
   if (h->L == 0) {                                            // nmf_np.py:95-98
+    site_at(kNpAfterS, 2);                                    // (the sites of NMTF's F and G sweeps)
     np_enqueue_sweep(h, true, s->Xr, s->Xc, h->K, 0, h->K, nullptr);
-    NpSiteKeys::mark(keys, 2, 2);                             // (the sites of NMTF's F and G sweeps)
+    site_at(kNpAfterS, 4);
     np_enqueue_sweep(h, false, s->Xc, s->Xr, h->K, 0, h->K, stats_out);
-    NpSiteKeys::mark(keys, 2, 4);
-    return BNMTF_OK;
+  } else {
+    CHK(np_s_step(h, 0, h->K * h->L));                        // nmtf_np.py:127-135; the records behind it follow S's copy: (2, 1) ...
+    np_gst(h);
+    np_enqueue_sweep(h, true, s->Xr, s->Y, h->K, 0, h->K, nullptr);
+    np_fs(h);
+    np_enqueue_sweep(h, false, s->Xc, s->Y, h->L, 0, h->L, stats_out);
   }
-  CHK(np_s_step(h, 0, h->K * h->L, keys));                    // nmtf_np.py:127-135
-  np_gst(h);
-  np_enqueue_sweep(h, true, s->Xr, s->Y, h->K, 0, h->K, nullptr);
-  np_fs(h);
-  np_enqueue_sweep(h, false, s->Xc, s->Y, h->L, 0, h->L, stats_out);
-  NpSiteKeys::mark(keys, 2, 1);
+  h->iteration++;
+  return BNMTF_OK;
+}
+
+// the record of n_iter iterations of 8 sums each; either output may be null
+static void unpack_np_rec(const double* rec, int n_iter, double* perf, double* idiv) {
+  for (int it = 0; it < n_iter; ++it) {
+    if (perf) np_perf(rec + (size_t)it * 8, perf + (size_t)it * 3);
+    if (idiv) idiv[it] = rec[(size_t)it * 8 + 6];
+  }
+}
+// room on the device for the records of a run
+static int np_reserve_rec(NpState* s, int n_iter) {
+  if ((size_t)n_iter <= s->rec_cap) return BNMTF_OK;
+  dfree(s->rec); s->rec_cap = 0;
+  CHK(dalloc(&s->rec, (size_t)n_iter * 8, false));
+  s->rec_cap = n_iter;
   return BNMTF_OK;
 }
 
@@ -144,32 +156,20 @@ static int np_run(bnmtf_model* h, int n_iter, double* perf_out, double* idiv_out
   NpState* s = h->np;
   if (n_iter < 0) { set_error("run: negative iteration count"); return BNMTF_EINVAL; }
   if (n_iter == 0) return BNMTF_OK;
-  if ((size_t)n_iter > s->rec_cap) {
-    dfree(s->rec); s->rec_cap = 0;
-    CHK(dalloc(&s->rec, (size_t)n_iter * 8, false));
-    s->rec_cap = n_iter;
-  }
+  CHK(np_reserve_rec(s, n_iter));
   EventList ev;
   CHK(ev.create(times_out ? n_iter + 1 : 0));
   if (times_out) HIPCHK(hipEventRecord(ev[0], h->stream));
   for (int it = 0; it < n_iter; ++it) {
     CHK(np_iteration(h, s->rec + (size_t)it * 8));
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], h->stream));
-    h->iteration++;
   }
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
   std::vector<double> rec((size_t)n_iter * 8);
   HIPCHK(hipMemcpy(rec.data(), s->rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (int it = 0; it < n_iter; ++it) {
-    if (perf_out) np_perf(&rec[(size_t)it * 8], perf_out + (size_t)it * 3);
-    if (idiv_out) idiv_out[it] = rec[(size_t)it * 8 + 6];
-    if (times_out) {
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, ev[0], ev[it + 1]);
-      times_out[it] = (double)ms * 1e-3;
-    }
-  }
+  unpack_np_rec(rec.data(), n_iter, perf_out, idiv_out);
+  ev.seconds(n_iter, times_out);
   return BNMTF_OK;
 }
 

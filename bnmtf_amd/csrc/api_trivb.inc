@@ -5,24 +5,13 @@
 
 namespace bnmtf {
 
-// While a Recorder is installed (api_trivb_many.inc), the site key (site, index within the site) of every record: the records of
-// the models of a batch are aligned by key, not by position -- a model's first iteration of a call forms R~^T E[F] and the column
-// Grams inside the S system (later ones take them from behind the F sweep), and only K L >= 64 permutes the system for the chain.
+// The launch sites of a recorded iteration (many.h: site_at; api_many.inc): the records of the models of a batch are aligned by
+// site, not by position -- a model's first iteration of a call forms R~^T E[F] and the column Grams inside the S system (later ones
+// take them from behind the F sweep), and only K L >= 64 permutes the system for the chain.
 enum TriSite {
   kTsPv, kTsColGram, kTsGammaPack, kTsSysGemm, kTsSysReduce, kTsSysB, kTsResidual, kTsColsumRows, kTsGemmRows, kTsPermute, kTsChain,
   kTsProductF, kTsSlabF, kTsSweepF, kTsPostF, kTsColGramsNext, kTsPvNext, kTsProductG, kTsSlabG, kTsSweepG, kTsPostG, kTsThird,
-  kTsFinish, kTsEnd
-};
-struct TriSiteKeys {
-  std::vector<std::pair<int, int>> key;
-  int site = -1, sub = 0;
-  void clear() { key.clear(); site = -1; sub = 0; }
-  // the records made since the last call belong to the site named then; the next ones to `s`
-  static void at(TriSiteKeys* k, int s) {
-    if (!k || !g_recorder) return;
-    while (k->key.size() < g_recorder->recs.size()) k->key.push_back({k->site, k->sub++});
-    k->site = s; k->sub = 0;
-  }
+  kTsFinish
 };
 
 static int ensure_tri(bnmtf_model* h) {
@@ -69,11 +58,11 @@ static void enqueue_tri_pv(bnmtf_model* h) {        // slabsS = R~^T E[F]
   g.big = c.big; g.ld = c.n_pad; g.X = r.X; g.slabs = h->slabsS; g.n_pad = c.n_pad; g.split = c.split; g.inner_per_wave = c.ipw; g.tw = c.gemm_tw;
   launch_gemm(g, r.KP, h->stream);
 }
-static int enqueue_tri_ssys(bnmtf_model* h, bool pv_current = false, TriSiteKeys* keys = nullptr) {
+static int enqueue_tri_ssys(bnmtf_model* h, bool pv_current = false) {
   Dir& c = h->cols; Dir& r = h->rows;
   const int K = h->K, L = h->L, n2 = K * L;
   if (!pv_current) {
-    TriSiteKeys::at(keys, kTsPv);
+    site_at(kTsPv);
     GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.big = c.big; g.ld = c.n_pad; g.X = r.X; g.slabs = h->slabsS; g.n_pad = c.n_pad; g.split = c.split; g.inner_per_wave = c.ipw; g.tw = c.gemm_tw;
@@ -83,10 +72,10 @@ static int enqueue_tri_ssys(bnmtf_model* h, bool pv_current = false, TriSiteKeys
   memset(&gp, 0, sizeof(gp));
   gp.n = c.n; gp.n0 = c.n0; gp.L = L; gp.G = c.X; gp.varG = c.var; gp.Gc = h->ss_Gc;
   if (h->tri_w_current) {
-    TriSiteKeys::at(keys, kTsGammaPack);
+    site_at(kTsGammaPack);
     launch_gamma_pack(gp, h->stream);    // (the column Grams of this q(F) were formed behind its sweep: enqueue_tri_colgrams)
   } else {
-    TriSiteKeys::at(keys, kTsColGram);
+    site_at(kTsColGram);
     SColGramArgs w;
     memset(&w, 0, sizeof(w));
     w.n = c.n; w.K = K; w.F = r.X; w.varF = r.var; w.Cf64 = r.C64;
@@ -98,26 +87,26 @@ static int enqueue_tri_ssys(bnmtf_model* h, bool pv_current = false, TriSiteKeys
   SSysGemmArgs g;
   memset(&g, 0, sizeof(g));
   g.n = c.n; g.K = K; g.L = L; g.nsplit = h->ss_nsplit; g.Wc = h->ss_Wc; g.Gc = h->ss_Gc; g.slabs = h->ss_slabs;
-  TriSiteKeys::at(keys, kTsSysGemm);
+  site_at(kTsSysGemm);
   launch_ssys_gemm(g, h->stream);
-  TriSiteKeys::at(keys, kTsSysReduce);
+  site_at(kTsSysReduce);
   launch_ssys_reduce(h->ss_slabs, h->ss_nsplit, K, L, h->ss_AB, h->stream);
   SSysBArgs b;
   memset(&b, 0, sizeof(b));
   b.n = c.n; b.n0 = c.n0; b.K = K; b.L = L; b.slabs = h->slabsS; b.split = c.split; b.n_pad = c.n_pad; b.G = c.X; b.b = h->ss_bpart;
-  TriSiteKeys::at(keys, kTsSysB);
+  site_at(kTsSysB);
   launch_ssys_b(b, h->stream);
   if (h->comm) {
     // several GPUs: (A~, b) of the ranks' column ranges summed with ONE all-reduce (the "K x L Gram" exchange, as bnmtf_gibbs_run's S step)
     launch_ssys_sum_parts(h->ss_bpart, ssys_b_blocks(c.n), (size_t)n2, h->ss_AB + (size_t)n2 * n2, h->stream);
     CHK(comm_allreduce_sum_f32(h->comm, h->ss_AB, n2 * n2 + n2, h->stream));
   }
-  TriSiteKeys::at(keys, kTsResidual);
+  site_at(kTsResidual);
   launch_ssys_residual(h->ss_AB, h->ss_AB + (size_t)n2 * n2, h->comm ? nullptr : h->ss_bpart, ssys_b_blocks(c.n), h->S, n2, h->ss_r, h->stream);
   return BNMTF_OK;
 }
 // order_step (recording): order_dev is the order of the call's first iteration, the list forms add it x order_step
-static void enqueue_tri_chain(bnmtf_model* h, const int* order_dev, int n_order, int only_params, int order_step = 0, TriSiteKeys* keys = nullptr) {
+static void enqueue_tri_chain(bnmtf_model* h, const int* order_dev, int n_order, int only_params, int order_step = 0) {
   SSysChainVbArgs a;
   memset(&a, 0, sizeof(a));
   a.K = h->K; a.L = h->L; a.n_order = n_order; a.only_params = only_params; a.order = order_dev;
@@ -125,11 +114,11 @@ static void enqueue_tri_chain(bnmtf_model* h, const int* order_dev, int n_order,
   a.E = h->S; a.var = h->varS; a.mu = h->muS; a.tauq = h->tauS;
   a.Aperm = nullptr;
   if (n_order == h->K * h->L && !only_params && n_order >= 64 && h->ss_Aperm) {      // a whole pass: the system in the pass's order
-    TriSiteKeys::at(keys, kTsPermute);
+    site_at(kTsPermute);
     launch_ssys_permute(h->ss_AB, order_dev, n_order, h->ss_Aperm, h->stream, order_step);
     a.Aperm = h->ss_Aperm;
   }
-  TriSiteKeys::at(keys, kTsChain);
+  site_at(kTsChain);
   launch_ssys_chain_vb(a, h->stream, order_step);
 }
 
@@ -235,11 +224,11 @@ static bool tri_overlap(const bnmtf_model* h) {
 }
 
 // One iteration of bnmtf_vb_run (update_S in the order's first K L entries, update_F in the next K, update_G in the last L; update_tau,
-// the metrics, the ELBO's pieces) on h->stream -- or, while a Recorder is installed (api_trivb_many.inc: the caller has checked
-// trivb_batchable), into its records, with the site key of every record in *keys.  Recording, the order and the record of the
+// the metrics, the ELBO's pieces) on h->stream -- or, while a Recorder is installed (api_many.inc: the caller has checked
+// trivb_batchable), into its records, each under its site.  Recording, the order and the record of the
 // iteration are the call's FIRST ones (the list forms add `it` steps), and the work that runs on the second stream otherwise
 // (the masked variance sums of G, R~ E[G]) is recorded in line: the same kernels on the same operands, the same bits.
-static int enqueue_trivb_iteration(bnmtf_model* h, int it, bool recording, TriSiteKeys* keys = nullptr) {
+static int enqueue_trivb_iteration(bnmtf_model* h, int it, bool recording) {
   Dir& r = h->rows; Dir& c = h->cols;
   const int K = h->K, L = h->L, per = K * L + K + L;
   const bool overlap = tri_overlap(h);
@@ -268,11 +257,11 @@ static int enqueue_trivb_iteration(bnmtf_model* h, int it, bool recording, TriSi
   };
   {   // ---- S entries in shuffled order
     ScopedKernelTimer t(h, BNMTF_KERNEL_SWEEP_S);
-    CHK(enqueue_tri_ssys(h, overlap && h->tri_pv_current, keys));
+    CHK(enqueue_tri_ssys(h, overlap && h->tri_pv_current));
     if (recording) {
-      TriSiteKeys::at(keys, kTsColsumRows);
+      site_at(kTsColsumRows);
       enqueue_tri_masked_colsum(h, 0, h->stream);
-      TriSiteKeys::at(keys, kTsGemmRows);
+      site_at(kTsGemmRows);
       gemm_rows(h->stream);
     } else if (overlap) {
       HIPCHK(hipEventRecord(h->ev_aux0, h->stream));
@@ -281,45 +270,45 @@ static int enqueue_trivb_iteration(bnmtf_model* h, int it, bool recording, TriSi
       gemm_rows(h->aux_stream);
       HIPCHK(hipEventRecord(h->ev_aux1, h->aux_stream));
     }
-    enqueue_tri_chain(h, ord, K * L, 0, step, keys);
+    enqueue_tri_chain(h, ord, K * L, 0, step);
   }
   // ---- F columns in their shuffled order
   if (overlap) {
-    TriSiteKeys::at(keys, kTsProductF);
+    site_at(kTsProductF);
     enqueue_tri_side_prepare(h, 0, 1);
     if (!recording) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_aux1, 0));
-    TriSiteKeys::at(keys, kTsSlabF);
+    site_at(kTsSlabF);
     slab_product(r.slabs, r.split, r.n_pad, r.slabs, r.n, 1);       // (in place: a unit's half wave reads all of its row before it writes slab 0)
   } else enqueue_tri_side_prepare(h, 0);
   {
     ScopedKernelTimer t(h, BNMTF_KERNEL_SWEEP_ROWS);
-    TriSiteKeys::at(keys, kTsSweepF);
+    site_at(kTsSweepF);
     enqueue_tri_sweep(h, 0, ord + K * L, false, overlap, nullptr, step);
   }
   if (h->comm)
     for (float* X : {r.X, r.var, r.S2}) CHK(comm_allgather_factor(h->comm, X, r.KP, r.nglob, h->world, h->stream));
-  TriSiteKeys::at(keys, kTsPostF);
+  site_at(kTsPostF);
   enqueue_post(h, r, true);
-  TriSiteKeys::at(keys, kTsColGramsNext);
+  site_at(kTsColGramsNext);
   enqueue_tri_colgrams(h);                 // (+ mv_cols for the G sweep below)
   // ---- G columns
   if (overlap) {
-    { ScopedKernelTimer t(h, BNMTF_KERNEL_GEMM_COLS); TriSiteKeys::at(keys, kTsPvNext); enqueue_tri_pv(h); }      // R~^T E[F] of the F just written
+    { ScopedKernelTimer t(h, BNMTF_KERNEL_GEMM_COLS); site_at(kTsPvNext); enqueue_tri_pv(h); }      // R~^T E[F] of the F just written
     h->tri_pv_current = true;
-    TriSiteKeys::at(keys, kTsProductG);
+    site_at(kTsProductG);
     enqueue_tri_side_prepare(h, 2, 1);
-    TriSiteKeys::at(keys, kTsSlabG);
+    site_at(kTsSlabG);
     slab_product(h->slabsS, c.split, c.n_pad, c.slabs, c.n, 0);
   } else enqueue_tri_side_prepare(h, 2, 1 | 4);
   int sweep_blocks = 0;
   {
     ScopedKernelTimer t(h, BNMTF_KERNEL_SWEEP_COLS);
-    TriSiteKeys::at(keys, kTsSweepG);
+    site_at(kTsSweepG);
     enqueue_tri_sweep(h, 2, ord + K * L + K, true, overlap, h->comm ? nullptr : &sweep_blocks, step);
   }
   if (h->comm)
     for (float* X : {c.X, c.var, c.S2}) CHK(comm_allgather_factor(h->comm, X, c.KP, c.nglob, h->world, h->stream));
-  TriSiteKeys::at(keys, kTsPostG);
+  site_at(kTsPostG);
   enqueue_post(h, c, true);
   // ---- update_tau, update_exp_tau, predict(M).  Round 6: exp_square_diff (:235-239) without a pass over R -- it was three
   // direct fp64 passes of 323 us each at 4096^2.  With m = E[F] E[S] (the G sweep's effective factor: mean m, second moment S2e):
@@ -330,7 +319,7 @@ static int enqueue_trivb_iteration(bnmtf_model* h, int it, bool recording, TriSi
   TriThirdArgs t3;
   memset(&t3, 0, sizeof(t3));
   t3.rows = c.n; t3.K = K; t3.L = L; t3.G = c.X + (size_t)c.n0 * 32; t3.S = h->S; t3.mv = h->mv_cols; t3.part = h->tri_third;
-  TriSiteKeys::at(keys, kTsThird);
+  site_at(kTsThird);
   launch_tri_third(t3, h->stream);
   VbFinishArgs f;
   memset(&f, 0, sizeof(f));
@@ -351,9 +340,8 @@ static int enqueue_trivb_iteration(bnmtf_model* h, int it, bool recording, TriSi
     f.acc = h->vbred; f.stats_r = h->vbred + 4; f.nr = 1; f.stats_c = h->vbred + 12; f.nc = 1;
     f.extra = h->vbred + 20; f.n_extra = 1;
   }
-  TriSiteKeys::at(keys, kTsFinish);
+  site_at(kTsFinish);
   launch_vb_finish(f, h->stream);
-  TriSiteKeys::at(keys, kTsEnd);
   if (recording && (sweep_blocks == 0 || g_recorder->missing)) {
     set_error("a recorded tri-factorisation iteration met a kernel without a list form (%s)", g_recorder->missing ? g_recorder->missing : "the G sweep's sums");
     return BNMTF_ESTATE;
@@ -467,7 +455,7 @@ int bnmtf_vb_run(bnmtf_handle h, int n_iter, const int32_t* orders, double* expt
   const int K = h->K, L = h->L, per = K * L + K + L;
   if (h->tri_order_cap < (size_t)n_iter * per) { dfree(h->tri_order); CHK(dalloc(&h->tri_order, (size_t)n_iter * per, false)); h->tri_order_cap = (size_t)n_iter * per; }
   HIPCHK(hipMemcpy(h->tri_order, orders, (size_t)n_iter * per * sizeof(int), hipMemcpyHostToDevice));
-  if (h->vb_rec_cap < (size_t)n_iter) { dfree(h->vb_rec); CHK(dalloc(&h->vb_rec, (size_t)n_iter * 16)); h->vb_rec_cap = n_iter; }
+  CHK(vb_reserve_rec(h, n_iter));
   EventList ev;
   CHK(ev.create(times_out ? n_iter + 1 : 0));
   if (times_out) HIPCHK(hipEventRecord(ev[0], h->stream));
@@ -489,16 +477,8 @@ int bnmtf_vb_run(bnmtf_handle h, int n_iter, const int32_t* orders, double* expt
   drain_events(h);
   std::vector<double> rec((size_t)n_iter * 16);
   HIPCHK(hipMemcpy(rec.data(), h->vb_rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (int it = 0; it < n_iter; ++it) {
-    const double* q = &rec[(size_t)it * 16];
-    if (exptau_out) exptau_out[it] = q[0];
-    if (perf_out) for (int m = 0; m < 3; ++m) perf_out[(size_t)it * 3 + m] = q[1 + m];
-    if (elbo_terms_out) {
-      double* o = elbo_terms_out + (size_t)it * 10;
-      for (int m = 0; m < 10; ++m) o[m] = q[4 + m];       // esd, beta_s, the four sums of F, the four of G
-    }
-    if (times_out) { float ms = 0.f; (void)hipEventElapsedTime(&ms, ev[0], ev[it + 1]); times_out[it] = (double)ms * 1e-3; }
-  }
+  unpack_vb_rec(rec.data(), n_iter, exptau_out, perf_out, elbo_terms_out);       // (terms: esd, beta_s, the four sums of F, the four of G)
+  ev.seconds(n_iter, times_out);
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 

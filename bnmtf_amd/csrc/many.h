@@ -10,6 +10,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 namespace bnmtf {
@@ -35,12 +36,21 @@ struct LaunchRec {
 };
 struct Recorder {                      // (cleared per iteration: the vectors keep their capacity, a record costs a memcpy)
   std::vector<LaunchRec> recs;
+  // keys[q]: the site key (site, index within the site) of recs[q].  The records of the models of a batch meet in a launch by key,
+  // not by position, and the sites are launched in key order; a family that names no site gets (-1, position).
+  std::vector<std::pair<int, int>> keys;
+  int site = -1, sub = 0;
   std::vector<unsigned char> arena;
   const char* missing = nullptr;       // a launcher without a list form was called while recording (record_missing): its kernel
-  void clear() { recs.clear(); arena.clear(); missing = nullptr; }
+  void clear() { recs.clear(); keys.clear(); arena.clear(); missing = nullptr; site = -1; sub = 0; }
   const unsigned char* args(const LaunchRec& r) const { return arena.data() + r.off; }
 };
 extern thread_local Recorder* g_recorder;
+
+// While a Recorder is installed: the records from here on belong to `site`, as (site, first), (site, first + 1), ...
+inline void site_at(int site, int first = 0) {
+  if (Recorder* rc = g_recorder) { rc->site = site; rc->sub = first; }
+}
 
 template <class P>
 inline bool record_launch(const void* many_fn, dim3 grid, dim3 block, size_t lds, const P& p, bool flex = false) {
@@ -52,6 +62,7 @@ inline bool record_launch(const void* many_fn, dim3 grid, dim3 block, size_t lds
   rc->arena.resize(rc->arena.size() + sizeof(P));
   memcpy(rc->arena.data() + r.off, &p, sizeof(P));
   rc->recs.push_back(r);
+  rc->keys.push_back({rc->site, rc->sub++});
   return true;
 }
 

@@ -264,7 +264,7 @@ BNMTF_API int bnmtf_vb_exp_square_diff(bnmtf_handle h, double* esd_out, double s
 BNMTF_API int bnmtf_vb_run(bnmtf_handle h, int n_iter, const int32_t* orders, double* exptau_out, double* perf_out,
                  double* elbo_terms_out, double* times_out);
 /* run(iterations) of n_models tri-factorisations on one device, walked in lock-step: every launch site of an iteration is ONE launch
- * for all of them (csrc/many.h, api_trivb_many.inc) -- the reference's model searches (experiments_gdsc/cross_validation/vb_nmtf/
+ * for all of them (csrc/many.h, api_many.inc) -- the reference's model searches (experiments_gdsc/cross_validation/vb_nmtf/
  * greedysearch_xval_vb.py: folds x a greedy walk over K, L) are dozens to hundreds of independent models of 622 x 138.  Models may
  * differ in shape and in K, L; every model ends with the bits of its own bnmtf_vb_run.  orders[b]: model b's [n_iter][K L + K + L]
  * update orders (bnmtf_vb_run's).  Outputs model-major ([n_models][n_iter]..., as bnmtf_vb_run's; times = the batch's clock); any
@@ -366,7 +366,7 @@ BNMTF_API int bnmtf_np_update(bnmtf_handle h, int which, int k, int l);
 BNMTF_API int bnmtf_np_run(bnmtf_handle h, int n_iter, double* perf_out, double* idiv_out, double* times_out);
 /* run(n_iter) of n_models handles of bnmtf_np_create on one device (NMF and NMTF, any shapes and ranks), walked in lock-step: every
  * launch site of an iteration -- before the S step, S pass t, after it -- is ONE launch for all of them (csrc/many.h,
- * api_np_many.inc).  Every model ends with the bits of its own bnmf_np_run / bnmtf_np_run.  Outputs model-major: perf_out
+ * api_many.inc).  Every model ends with the bits of its own bnmf_np_run / bnmtf_np_run.  Outputs model-major: perf_out
  * [n_models][n_iter][3], idiv_out [n_models][n_iter], times_out [n_models][n_iter] (the batch's clock); any may be null.
  * launch_info (optional, 2 ints): the models that shared launches, the argument-list uploads.  Refuses a null handle, one given
  * twice, handles of several devices and a handle without state. */

@@ -2,7 +2,7 @@
 // HIP runtime, under AddressSanitizer + UBSan (`make asan`) or ThreadSanitizer (`make tsan`).  Kernels do not run, so no number
 // that comes back means anything; what is checked is the host code the calls go through: bnmtf_create's layout passes (worker
 // threads, slot tables, shard ranges, the hand-over table sizes), the arenas and pools of created / destroyed models, every
-// host<->"device" copy's extent (device memory is heap memory here), the sample ring of run(), run_many's batching, and the
+// host<->"device" copy's extent (device memory is heap memory here), the sample ring of run(), run_many's batching and lock-step walks, and the
 // in-process multi-rank rendezvous of comm.hip with one host thread per rank.
 #include <cstdio>
 #include <cstdlib>
@@ -119,9 +119,20 @@ static void vb_round_trip(const Data& d, int K) {
   OK(bnmtf_destroy(h));
 }
 
+// SAN_VERBOSE: the stub's launch counter before and after a scenario's calls (name = null: nothing, the scenario shares the counter
+// with another thread).  The lock-step scenarios launch once per group of records that meet at a site, so equal counts before and
+// after a change to the driver say that the same records still meet.
+struct LaunchCount {
+  const char* name;
+  long before;
+  explicit LaunchCount(const char* name_) : name(name_), before(hipstub_launches()) {}
+  ~LaunchCount() { if (name && getenv("SAN_VERBOSE")) printf("%s: %ld stub launches before, %ld after\n", name, before, hipstub_launches()); }
+};
+
 // several variational models in lock-step (api_many.inc): the recorder, the argument lists, the per-model outputs; two shapes and a
 // model given once only
-static void vb_many(const Data& d1, const Data& d2, int K) {
+static void vb_many(const Data& d1, const Data& d2, int K, const char* report) {
+  LaunchCount count(report);
   std::vector<bnmtf_handle> hs;
   const long live0 = hipstub_live_allocs();
   for (int m = 0; m < 5; ++m) {
@@ -136,11 +147,89 @@ static void vb_many(const Data& d1, const Data& d2, int K) {
   std::vector<double> et((size_t)n * it), perf((size_t)n * it * 3), elbo((size_t)n * it * 10), times((size_t)n * it);
   int info[2];
   OK(bnmf_vb_run_many(hs.data(), n, it, et.data(), perf.data(), elbo.data(), times.data(), info));
+  const int shared = info[0];
   OK(bnmf_vb_run_many(hs.data(), n, 2, nullptr, nullptr, nullptr, nullptr, nullptr));
   OK(bnmf_vb_run_many(hs.data(), 1, 2, et.data(), nullptr, nullptr, nullptr, info));
   const long live1 = hipstub_live_allocs();
   for (bnmtf_handle h : hs) OK(bnmtf_destroy(h));
-  if (getenv("SAN_VERBOSE")) printf("vb_many: live allocations %ld before, %ld with five models, %ld after\n", live0, live1, hipstub_live_allocs());
+  if (report && getenv("SAN_VERBOSE")) printf("vb_many: live allocations %ld before, %ld with five models, %ld after; %d models shared launches\n", live0, live1, hipstub_live_allocs(), shared);
+}
+
+static void tri_vb_set_state(bnmtf_handle h, const Data& d, int K, int L) {
+  std::vector<double> F((size_t)d.I * K, 1.0), S((size_t)K * L, 1.0), G((size_t)d.J * L, 1.0);
+  OK(bnmtf_vb_set_state(h, F.data(), F.data(), F.data(), F.data(), S.data(), S.data(), S.data(), S.data(), G.data(), G.data(), G.data(), G.data(), 1.0));
+}
+
+// several variational tri-factorisations in lock-step: models of different (K, L) -- one with K L >= 64, whose chain walks the
+// permuted system: a site the others do not have -- and shapes; `wide`: also a model whose row sweep takes the 16-wave shape, which
+// runs on its own.  Calls one behind the other (the first iteration of the first has sites the later ones do not), and one after a
+// single model's state was set again (its first iteration then differs from the others').
+static void tri_vb_many(const Data& d1, const Data& d2, bool wide, const char* report) {
+  LaunchCount count(report);
+  const Data dw = make_data(wide ? 6200 : 1, wide ? 90 : 1, 0.1, 35);
+  struct Shape { const Data* d; int K, L; };
+  std::vector<Shape> shapes = {{&d1, 4, 5}, {&d1, 6, 3}, {&d2, 9, 8}, {&d2, 4, 5}};
+  if (wide) shapes.push_back({&dw, 5, 4});
+  std::vector<bnmtf_handle> hs;
+  for (const Shape& sh : shapes) {
+    hs.push_back(create(*sh.d, sh.K, sh.L, 0, 1, nullptr));
+    tri_vb_set_state(hs.back(), *sh.d, sh.K, sh.L);
+  }
+  const int n = (int)hs.size(), it = 3;
+  std::vector<std::vector<int32_t>> orders;
+  std::vector<const int32_t*> op;
+  for (const Shape& sh : shapes) {
+    const int per = sh.K * sh.L + sh.K + sh.L;
+    orders.emplace_back((size_t)it * per);
+    for (int t = 0; t < it; ++t) {
+      int32_t* o = &orders.back()[(size_t)t * per];
+      for (int a = 0; a < sh.K * sh.L; ++a) o[a] = (a + t) % (sh.K * sh.L);
+      for (int k = 0; k < sh.K; ++k) o[sh.K * sh.L + k] = sh.K - 1 - k;
+      for (int l = 0; l < sh.L; ++l) o[sh.K * sh.L + sh.K + l] = (l + t) % sh.L;
+    }
+  }
+  for (auto& o : orders) op.push_back(o.data());
+  std::vector<double> et((size_t)n * it), perf((size_t)n * it * 3), elbo((size_t)n * it * 10), times((size_t)n * it);
+  int info[2];
+  OK(bnmtf_vb_run_many(hs.data(), n, it, op.data(), et.data(), perf.data(), elbo.data(), times.data(), info));
+  if (report && getenv("SAN_VERBOSE")) printf("%s: %d of %d models shared launches\n", report, info[0], n);
+  OK(bnmtf_vb_run_many(hs.data(), n, 2, op.data(), nullptr, nullptr, nullptr, nullptr, nullptr));
+  tri_vb_set_state(hs[1], *shapes[1].d, shapes[1].K, shapes[1].L);
+  OK(bnmtf_vb_run_many(hs.data(), n, 2, op.data(), et.data(), nullptr, nullptr, nullptr, info));
+  OK(bnmtf_vb_run_many(hs.data(), 1, 2, op.data(), et.data(), nullptr, nullptr, nullptr, info));
+  EXPECT_ERR(bnmtf_vb_run_many(hs.data(), n, 2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+  std::vector<bnmtf_handle> dup = {hs[0], hs[1], hs[0]};
+  EXPECT_ERR(bnmtf_vb_run_many(dup.data(), 3, 2, op.data(), nullptr, nullptr, nullptr, nullptr, nullptr));
+  for (bnmtf_handle h : hs) OK(bnmtf_destroy(h));
+}
+
+// NMF and NMTF models in lock-step: different ranks, so the S chains differ in length (the shorter ones have no record at the
+// later passes) and NMF's two sweeps meet NMTF's; with and without outputs; a single model
+static void np_many(const Data& d1, const Data& d2, const char* report) {
+  LaunchCount count(report);
+  struct Shape { const Data* d; int K, L; };
+  const std::vector<Shape> shapes = {{&d1, 5, 0}, {&d1, 3, 4}, {&d2, 8, 0}, {&d2, 5, 6}, {&d1, 2, 2}};
+  std::vector<bnmtf_handle> hs;
+  for (const Shape& sh : shapes) {
+    const Data& d = *sh.d;
+    bnmtf_handle h = nullptr;
+    OK(bnmtf_np_create(d.R.data(), d.M.data(), d.I, d.J, sh.K, sh.L, 0, &h));
+    std::vector<double> F((size_t)d.I * sh.K, 1.0), S((size_t)sh.K * (sh.L ? sh.L : 1), 1.0), G((size_t)d.J * (sh.L ? sh.L : sh.K), 1.0);
+    if (sh.L) OK(bnmtf_np_set_state(h, F.data(), S.data(), G.data()));
+    else OK(bnmf_np_set_state(h, F.data(), G.data()));
+    hs.push_back(h);
+  }
+  const int n = (int)hs.size(), it = 3;
+  std::vector<double> perf((size_t)n * it * 3), idiv((size_t)n * it), times((size_t)n * it);
+  int info[2];
+  OK(bnmtf_np_run_many(hs.data(), n, it, perf.data(), idiv.data(), times.data(), info));
+  if (report && getenv("SAN_VERBOSE")) printf("%s: %d of %d models shared launches\n", report, info[0], n);
+  OK(bnmtf_np_run_many(hs.data(), n, 2, nullptr, nullptr, nullptr, nullptr));
+  OK(bnmtf_np_run_many(hs.data() + 1, 1, 2, perf.data(), idiv.data(), times.data(), info));
+  OK(bnmtf_np_run_many(hs.data(), 0, 2, nullptr, nullptr, nullptr, info));
+  std::vector<bnmtf_handle> dup = {hs[0], hs[1], hs[0]};
+  EXPECT_ERR(bnmtf_np_run_many(dup.data(), 3, 2, nullptr, nullptr, nullptr, nullptr));
+  for (bnmtf_handle h : hs) OK(bnmtf_destroy(h));
 }
 
 // the variational tri-factorisation: set_state / run with shuffled orders / the direct exp_square_diff / single updates / get_state
@@ -296,14 +385,6 @@ static void sharded(const Data& d, int K, int L, int world, const char* token, i
       }
       OK(bnmtf_destroy(h));
       rc[r] = 1;
-  exception_stays_inside(make_data(515, 389, 0.12, 27), 24);
-  vb_many(make_data(300, 120, 0.15, 21), make_data(210, 150, 0.1, 22), 12);
-  {   // two host threads, a list of models each (the recorder is thread-local)
-    const Data da = make_data(280, 110, 0.15, 23), db = make_data(190, 160, 0.1, 24), dc = make_data(260, 100, 0.2, 25), dd = make_data(150, 170, 0.1, 26);
-    std::thread t1([&] { vb_many(da, db, 10); });
-    std::thread t2([&] { vb_many(dc, dd, 14); });
-    t1.join(); t2.join();
-  }
     });
   for (auto& t : ts) t.join();
   for (int r = 0; r < world; ++r) if (!rc[r]) { fprintf(stderr, "rank %d did not finish\n", r); exit(2); }
@@ -330,6 +411,17 @@ int main(int argc, char** argv) {
   tri_vb_round_trip(make_data(90, 70, 0.1, 15), 4, 5, 3);
   tri_vb_round_trip(make_data(1200, 1100, 0.1, 16), 12, 9, 2);         // the on-chip F / G sweeps' host side, the blocked chain's (K L >= 64)
   batches();
+  exception_stays_inside(make_data(515, 389, 0.12, 27), 24);
+  vb_many(make_data(300, 120, 0.15, 21), make_data(210, 150, 0.1, 22), 12, "vb_many");
+  tri_vb_many(make_data(300, 120, 0.15, 31), make_data(210, 150, 0.1, 32), true, "tri_vb_many");
+  np_many(make_data(300, 120, 0.15, 33), make_data(210, 150, 0.1, 34), "np_many");
+  {   // two host threads, a list of models each (the recorder is thread-local)
+    const Data da = make_data(280, 110, 0.15, 23), db = make_data(190, 160, 0.1, 24), dc = make_data(260, 100, 0.2, 25), dd = make_data(150, 170, 0.1, 26);
+    LaunchCount count("two threads of vb_many, tri_vb_many, np_many");
+    std::thread t1([&] { vb_many(da, db, 10, nullptr); tri_vb_many(da, db, false, nullptr); np_many(da, db, nullptr); });
+    std::thread t2([&] { vb_many(dc, dd, 14, nullptr); tri_vb_many(dc, dd, false, nullptr); np_many(dc, dd, nullptr); });
+    t1.join(); t2.join();
+  }
   column_blocks(make_data(150, 120, 0.15, 21));
   column_blocks(make_data(70, 60, 0.1, 22));             // (blocks that qualify for the one-launch arena)
   tri_blocks(make_data(130, 110, 0.12, 23));

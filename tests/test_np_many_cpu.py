@@ -1,4 +1,4 @@
-"""Many non-probabilistic models in one device call (csrc/api_np_many.inc, bnmtf_amd.run_many with NMF / NMTF, the drivers'
+"""Many non-probabilistic models in one device call (csrc/api_many.inc, bnmtf_amd.run_many with NMF / NMTF, the drivers'
 batched=) -- what needs no GPU: the entry point is declared and exported, the list-form half sweeps keep the single-model
 kernels' register budget, there is no CPU path, and the drivers plan the same folds batched or not."""
 import os

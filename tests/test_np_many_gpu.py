@@ -1,4 +1,4 @@
-"""Many non-probabilistic models in one launch per launch site (csrc/api_np_many.inc; bnmtf_amd.run_many with nmf_np.NMF /
+"""Many non-probabilistic models in one launch per launch site (csrc/api_many.inc; bnmtf_amd.run_many with nmf_np.NMF /
 nmtf_np.NMTF, the cross-validation drivers' batched=).  The list-form kernels run the single-model kernels' bodies, so every model
 must end with the BITS of its own run(): the factors, every iteration's metrics and the printed I-divergences.  No tolerances."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""Many variational tri-factorisations in one device call (csrc/api_trivb_many.inc, bnmtf_amd.run_many with bnmtf_vb_optimised) --
+"""Many variational tri-factorisations in one device call (csrc/api_many.inc, bnmtf_amd.run_many with bnmtf_vb_optimised) --
 what needs no GPU: run_many takes the class's own run() and refuses a subclass that brings its own, the entry point is declared,
 exported and bound, the list forms keep the single-model kernels' register budgets, and the empty calls return at once."""
 import os
@@ -84,7 +84,7 @@ def test_list_forms_keep_the_single_model_kernels_budgets():
                             ("ssys_reduce_kernel", "ssys_reduce_many"), ("ssys_b_kernel", "ssys_b_many"),
                             ("ssys_residual_kernel", "ssys_residual_many")],
         "kernel_bnmtf.hip": [("slab_product_kernel", "slab_product_many")],
-        # (the 8 + 2-wave shape: a model whose sweeps take the 16-wave one is not batched -- api_trivb_many.inc, trivb_batchable)
+        # (the 8 + 2-wave shape: a model whose sweeps take the 16-wave one is not batched -- api_many.inc, trivb_batchable)
         "kernel_sweep_vb.hip": [("sweep_vb_kernelILi1ELi8ELi2ELi1EE", "sweep_vb_manyILi1ELi8ELi2ELi1EE")],
     }
     procs = {tu: _resources(tu) for tu in pairs}

@@ -1,4 +1,4 @@
-"""Many variational tri-factorisations in one launch per launch site (csrc/api_trivb_many.inc; bnmtf_amd.run_many with
+"""Many variational tri-factorisations in one launch per launch site (csrc/api_many.inc; bnmtf_amd.run_many with
 bnmtf_vb_optimised models, a batched ReplicaPool): the list-form kernels run the single-model kernels' bodies, so every model must
 end with the BITS of its own run() -- the twelve q arrays, exptau, the metrics and the ELBO terms of every iteration, elbo() -- and
 Python's `random` (the update orders' shuffles) must end where the runs one after the other leave it.  No tolerances."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Variational tri-factorisations one by one against many per launch (bnmtf_vb_run_many, csrc/api_trivb_many.inc), on one GPU, every
+"""Variational tri-factorisations one by one against many per launch (bnmtf_vb_run_many, csrc/api_many.inc), on one GPU, every
 alternative in the same process:
 
   1. microseconds per model-iteration of 1, 10 and 40 GDSC-shaped models (622 x 138, 19 % missing; (K, L) in 5..10 x folds;
