@@ -100,19 +100,24 @@ class bnmf_gibbs_optimised(DeviceModel):
         self.U, self.V, self.tau = U, V, tau.value
         self._device_state = (self._h, U.copy(), V.copy(), tau.value)
 
-    def run(self, iterations, update='draw', store_samples=True, expectation=None):
+    def run(self, iterations, update='draw', store_samples=True, expectation=None, *, M_test=None):
         """:121-157.  One device call runs all iterations; samples, tau, metrics and
         cumulative times come back afterwards.  store_samples=False skips the all_U/all_V
         hand-off (device-resident benchmark mode); update='mode' runs the ICM harness;
         expectation=(burn_in, thinning) also accumulates the posterior means of exactly that
         approx_expectation(burn_in, thinning) on the device (what the model-selection drivers
-        need: with store_samples=False no sample ever crosses to the host)."""
+        need: with store_samples=False no sample ever crosses to the host).  M_test (a 0/1 matrix shaped like R; it may overlap M): the held-out MSE / R^2 / Rp of the state
+        every iteration ends with are computed on the device and kept in all_performances_test; without it no
+        such attribute exists after the call."""
+        Mt = self._check_heldout(M_test)
         if self._blocks is not None:
             return self._run_blocked(iterations, _lib.UPDATE_MODE if update == 'mode' else _lib.UPDATE_DRAW, store_samples, expectation)
         bufs = self._run_prepare(iterations, store_samples, expectation)
+        self._set_heldout(Mt)
         it, U_out, V_out, taus, perf, times = bufs
         _lib.check(_lib.lib().bnmf_gibbs_run(self._handle(), it, _lib.UPDATE_MODE if update == 'mode' else _lib.UPDATE_DRAW,
                                              _lib.ptr(U_out), _lib.ptr(V_out), _lib.ptr(taus), _lib.ptr(perf), _lib.ptr(times)))
+        self._finish_heldout(it)
         return self._run_finish(bufs, store_samples)
 
     def _run_blocked(self, iterations, update, store_samples, expectation, minimum_TN=0.0, icm=False):

@@ -125,14 +125,18 @@ class bnmf_vb_optimised(DeviceModel):
         self.update_tau()
         self.update_exp_tau()
 
-    def run(self, iterations):
-        """:121-153.  all_elbo (the value the reference only prints) is kept as an extra attribute."""
+    def run(self, iterations, *, M_test=None):
+        """:121-153.  all_elbo (the value the reference only prints) is kept as an extra attribute.  M_test: the held-out metrics
+        of E[U] E[V]^T behind every iteration, in all_performances_test (see bnmf_gibbs_optimised.run)."""
+        Mt = self._check_heldout(M_test)
         it = int(iterations)
         if self._blocks is not None:
             return self._run_blocked(it)
         self._push()
+        self._set_heldout(Mt)
         exptau = np.zeros(it); perf = np.zeros((it, 3)); terms = np.zeros((it, 10)); times = np.zeros(it)
         _lib.check(_lib.lib().bnmf_vb_run(self._handle(), it, _lib.ptr(exptau), _lib.ptr(perf), _lib.ptr(terms), _lib.ptr(times)))
+        self._finish_heldout(it)
         self._run_finish(it, exptau, perf, terms, times)
 
     def _run_finish(self, it, exptau, perf, terms, times):

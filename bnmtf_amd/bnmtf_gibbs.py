@@ -111,14 +111,20 @@ class bnmtf_gibbs_optimised(DeviceModel):
         self.F, self.S, self.G, self.tau = F, S, G, tau.value
         self._device_state = (self._h, F.copy(), S.copy(), G.copy(), tau.value)
 
-    def run(self, iterations, update='draw', store_samples=True, expectation=None):
-        """:138-180.  expectation=(burn_in, thinning): posterior means accumulated on the device (see bnmf_gibbs_optimised.run)."""
+    def run(self, iterations, update='draw', store_samples=True, expectation=None, *, M_test=None):
+        """:138-180.  expectation=(burn_in, thinning): posterior means accumulated on the device (see bnmf_gibbs_optimised.run).
+        M_test (a 0/1 matrix shaped like R; it may overlap M): the held-out MSE / R^2 / Rp of the state
+        every iteration ends with are computed on the device and kept in all_performances_test; without it no
+        such attribute exists after the call."""
+        Mt = self._check_heldout(M_test)
         if self._blocks is not None:
             return self._run_blocked(iterations, _lib.UPDATE_MODE if update == 'mode' else _lib.UPDATE_DRAW, store_samples, expectation)
         bufs = self._run_prepare(iterations, store_samples, expectation)
+        self._set_heldout(Mt)
         it, F_out, S_out, G_out, taus, perf, times = bufs
         _lib.check(_lib.lib().bnmtf_gibbs_run(self._handle(), it, _lib.UPDATE_MODE if update == 'mode' else _lib.UPDATE_DRAW,
                                               _lib.ptr(F_out), _lib.ptr(S_out), _lib.ptr(G_out), _lib.ptr(taus), _lib.ptr(perf), _lib.ptr(times)))
+        self._finish_heldout(it)
         return self._run_finish(bufs, store_samples)
 
     def _run_blocked(self, iterations, update, store_samples, expectation, minimum_TN=0.0, icm=False):

@@ -121,14 +121,18 @@ class bnmtf_vb_optimised(DeviceModel):
             out[it, K * L + K:] = indices_l
         return out
 
-    def run(self, iterations, orders=None):
-        """:160-205.  orders (optional): int array [iterations][K L + K + L] of update orders instead of fresh shuffles."""
+    def run(self, iterations, orders=None, *, M_test=None):
+        """:160-205.  orders (optional): int array [iterations][K L + K + L] of update orders instead of fresh shuffles.  M_test:
+        the held-out metrics of E[F] E[S] E[G]^T behind every iteration, in all_performances_test (see bnmf_gibbs_optimised.run)."""
+        Mt = self._check_heldout(M_test)
         it = int(iterations)
         orders = self._draw_orders(it) if orders is None else np.ascontiguousarray(orders, dtype=np.int32)
         assert orders.shape == (it, self.K * self.L + self.K + self.L)
         self._push()
+        self._set_heldout(Mt)
         exptau = np.zeros(it); perf = np.zeros((it, 3)); terms = np.zeros((it, 10)); times = np.zeros(it)
         _lib.check(_lib.lib().bnmtf_vb_run(self._handle(), it, _lib.ptr(orders), _lib.ptr(exptau), _lib.ptr(perf), _lib.ptr(terms), _lib.ptr(times)))
+        self._finish_heldout(it)
         self._run_finish(it, exptau, perf, terms, times)
 
     def _run_finish(self, it, exptau, perf, terms, times):

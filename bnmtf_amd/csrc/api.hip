@@ -1093,6 +1093,8 @@ static void expectation_add(bnmtf_model* h, int it, hipStream_t st = nullptr) { 
 
 using namespace bnmtf;
 
+#include "api_heldout.inc"
+
 // ======================================================================= C ABI
 extern "C" {
 
@@ -1334,6 +1336,7 @@ int bnmtf_destroy(bnmtf_handle h) try {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->comm) comm_destroy(h->comm);
   np_free(h);
+  heldout_free(h);
   small_free(h);            // (first: a small model's arena also holds Rfull, the posterior sums, Ad / Bd -- their pointers are cleared)
   free_dir(h->rows); free_dir(h->cols); free_dir(h->reff); free_dir(h->ceff);
   dfree(h->slabsS); dfree(h->CfS); dfree(h->deltaS); dfree(h->s_partial); dfree(h->s_w); dfree(h->s_omp); dfree(h->lambdaS); dfree(h->s_numer); dfree(h->s_taup);
@@ -1463,7 +1466,10 @@ int bnmtf_describe(bnmtf_handle h, char* buf, size_t buflen) try {
   // (+ which kernels the last variational half sweep ran on: vb_chip_ok)
   static const char* const kVbPath[] = {"", " vb_sweep=generic", " vb_sweep=pairs", " vb_sweep=masked"};
   static const char* const kTriPath[] = {"", " tri_vb_sweeps=generic", " tri_vb_sweeps=pairs+cov", ""};      // (bnmtf_vb_run: api_trivb.inc enqueue_tri_sweep)
-  snprintf(buf, buflen, "%s%s%s", h->description.c_str(), kVbPath[h->last_vb_path & 3], kTriPath[h->last_tri_path & 3]);
+  // (+ the held-out mask's entries, bnmtf_set_heldout; a model of the one-launch kind runs the multi-launch path while it has one)
+  char held[64] = "";
+  if (h->held_n) snprintf(held, sizeof(held), " heldout=%zu%s", h->held_n, h->small ? " run_path=multi-launch" : "");
+  snprintf(buf, buflen, "%s%s%s%s", h->description.c_str(), kVbPath[h->last_vb_path & 3], kTriPath[h->last_tri_path & 3], held);
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
@@ -1526,6 +1532,7 @@ int bnmf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* 
   if (n_iter == 0) return BNMTF_OK;
   HIPCHK(hipSetDevice(h->device));
   if (update < 0 || update > BNMTF_UPDATE_ICM) { set_error("unknown update rule"); return BNMTF_EINVAL; }
+  CHK(heldout_begin(h, n_iter));
   if (small_wanted(h)) {                       // a small model: the whole call is one launch (kernel_small.hip)
     SmallOut o{U_out, V_out, tau_out, perf_out, times_out};
     return small_run_many(&h, 1, n_iter, update, &o);
@@ -1619,6 +1626,7 @@ int bnmf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* 
     f.tau_d = h->tau_d; f.tau_f = h->tau_f; f.rec = h->rec + (size_t)it * 5;
     launch_finish(f, tst);
     expectation_add(h, it, tst);
+    heldout_enqueue(h, it, tst);                 // (a mask set: U, V are final since their sweeps, which this stream has waited for)
     // the iteration's stamp: behind its finish kernel, on the stream that ran it (the last one of a call is behind everything the
     // call enqueued: the compute stream's last kernel is the sweep this tail waited for)
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], tst));
@@ -1631,6 +1639,7 @@ int bnmf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* 
   HIPCHK(hipGetLastError());
   ho_scope.commit();
   drain_events(h);
+  heldout_end(h, n_iter);
   std::vector<double> rec((size_t)n_iter * 5);
   HIPCHK(hipMemcpy(rec.data(), h->rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
   for (int it = 0; it < n_iter; ++it) {
@@ -1648,6 +1657,7 @@ int bnmf_gibbs_run_many(const bnmtf_handle* hs, int n_models, int n_iter, int up
   if (n_models == 0 || n_iter == 0) return BNMTF_OK;
   if (update < 0 || update > BNMTF_UPDATE_ICM) { set_error("unknown update rule"); return BNMTF_EINVAL; }
   for (int b = 0; b < n_models; ++b) if (hs[b]->L != 0) { set_error("bnmf_gibbs_run_many on a BNMTF handle (model %d)", b); return BNMTF_ESTATE; }
+  for (int b = 0; b < n_models; ++b) CHK(heldout_refuse_many(hs[b], "bnmf_gibbs_run_many", b));
   // models of the one-launch path go down in one grid per device; the others run one after the other
   std::vector<bnmtf_model*> batch; std::vector<SmallOut> outs;
   auto out_of = [&](int b) { return SmallOut{U_outs ? U_outs[b] : nullptr, V_outs ? V_outs[b] : nullptr, tau_outs ? tau_outs[b] : nullptr,

@@ -242,7 +242,7 @@ int vb_prepare(bnmtf_model* h, int n_iter, const int32_t*) {
 // problems, per-kernel timers on.
 const ManyFamily kVbFamily = {
   "bnmf_vb_run_many", {1, 3, 10}, false, true, true,
-  [](bnmtf_model* h, int b) { if (h->vb_ready && h->have_state) return BNMTF_OK; set_error("bnmf_vb_run_many before bnmf_vb_set_state (model %d)", b); return BNMTF_ESTATE; },
+  [](bnmtf_model* h, int b) { if (h->vb_ready && h->have_state) return heldout_refuse_many(h, "bnmf_vb_run_many", b); set_error("bnmf_vb_run_many before bnmf_vb_set_state (model %d)", b); return BNMTF_ESTATE; },
   vb_batchable, vb_prepare,
   [](bnmtf_model* h, int it) { return enqueue_vb_iteration(h, it, true); },
   [](bnmtf_model* h, int n_iter, const int32_t*, const ManyOut& o) { return bnmf_vb_run(h, n_iter, o.a[0], o.a[1], o.a[2], o.times); },
@@ -252,7 +252,7 @@ const ManyFamily kVbFamily = {
 // them).  Not batched: several GPUs, per-kernel timers, the 16-wave sweeps, an A/B switch.
 const ManyFamily kTriVbFamily = {
   "bnmtf_vb_run_many", {1, 3, 10}, true, false, false,
-  [](bnmtf_model* h, int b) { if (h->tri_ready && h->have_state) return BNMTF_OK; set_error("bnmtf_vb_run_many before bnmtf_vb_set_state (model %d)", b); return BNMTF_ESTATE; },
+  [](bnmtf_model* h, int b) { if (h->tri_ready && h->have_state) return heldout_refuse_many(h, "bnmtf_vb_run_many", b); set_error("bnmtf_vb_run_many before bnmtf_vb_set_state (model %d)", b); return BNMTF_ESTATE; },
   trivb_batchable,
   [](bnmtf_model* h, int n_iter, const int32_t* orders) {
     const size_t n = (size_t)n_iter * ((size_t)h->K * h->L + h->K + h->L);

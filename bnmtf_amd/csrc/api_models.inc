@@ -297,6 +297,7 @@ int bnmtf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* F_out, float*
   if (n_iter <= 0) return n_iter == 0 ? BNMTF_OK : BNMTF_EINVAL;
   if (update < 0 || update > BNMTF_UPDATE_ICM) { set_error("unknown update rule"); return BNMTF_EINVAL; }
   HIPCHK(hipSetDevice(h->device));
+  CHK(heldout_begin(h, n_iter));
   if (small_wanted(h)) {                       // a small model: the whole call is one launch (kernel_small.hip)
     SmallOut o{F_out, G_out, tau_out, perf_out, times_out};
     o.S = S_out;
@@ -388,6 +389,7 @@ int bnmtf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* F_out, float*
     launch_finish(f, h->stream);
     CHK(sink.close_slot(it));
     expectation_add(h, it);
+    heldout_enqueue(h, it, h->stream);
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], h->stream));
     h->iteration++;
   }
@@ -395,6 +397,7 @@ int bnmtf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* F_out, float*
   CHK(sink.finish());
   HIPCHK(hipGetLastError());
   drain_events(h);
+  heldout_end(h, n_iter);
   std::vector<double> rec((size_t)n_iter * 5);
   HIPCHK(hipMemcpy(rec.data(), h->rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
   for (int it = 0; it < n_iter; ++it) {
@@ -414,6 +417,7 @@ int bnmtf_gibbs_run_many(const bnmtf_handle* hs, int n_models, int n_iter, int u
   if (n_models == 0 || n_iter == 0) return BNMTF_OK;
   if (update < 0 || update > BNMTF_UPDATE_ICM) { set_error("unknown update rule"); return BNMTF_EINVAL; }
   for (int b = 0; b < n_models; ++b) if (hs[b]->L == 0) { set_error("bnmtf_gibbs_run_many on a BNMF handle (model %d)", b); return BNMTF_ESTATE; }
+  for (int b = 0; b < n_models; ++b) CHK(heldout_refuse_many(hs[b], "bnmtf_gibbs_run_many", b));
   auto out_of = [&](int b) {
     SmallOut o{F_outs ? F_outs[b] : nullptr, G_outs ? G_outs[b] : nullptr, tau_outs ? tau_outs[b] : nullptr, perf_outs ? perf_outs[b] : nullptr,
                times_outs ? times_outs[b] : nullptr, F_final ? F_final[b] : nullptr, G_final ? G_final[b] : nullptr, tau_final ? tau_final[b] : nullptr};
@@ -772,6 +776,7 @@ int bnmf_vb_run(bnmtf_handle h, int n_iter, double* exptau_out, double* perf_out
   HIPCHK(hipSetDevice(h->device));
   Dir& r = h->rows; Dir& c = h->cols;
   CHK(vb_reserve_rec(h, n_iter));
+  CHK(heldout_begin(h, n_iter));
   EventList ev;
   CHK(ev.create(times_out ? n_iter + 1 : 0));
   if (times_out) HIPCHK(hipEventRecord(ev[0], h->stream));
@@ -779,6 +784,7 @@ int bnmf_vb_run(bnmtf_handle h, int n_iter, double* exptau_out, double* perf_out
   HIPCHK(hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));
   for (int it = 0; it < n_iter; ++it) {
     CHK(enqueue_vb_iteration(h, it, false));
+    heldout_enqueue(h, it, h->stream);           // (a mask set: on E[U], E[V] of this iteration)
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], h->stream));
   }
   if (h->comm)      // q(U), q(V) parameters of the other ranks' rows (bnmf_vb_get_state returns whole matrices)
@@ -788,6 +794,7 @@ int bnmf_vb_run(bnmtf_handle h, int n_iter, double* exptau_out, double* perf_out
   HIPCHK(hipGetLastError());
   ho_scope.commit();
   drain_events(h);
+  heldout_end(h, n_iter);
   std::vector<double> rec((size_t)n_iter * 16);
   HIPCHK(hipMemcpy(rec.data(), h->vb_rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
   unpack_vb_rec(rec.data(), n_iter, exptau_out, perf_out, elbo_terms_out);

@@ -263,6 +263,7 @@ static int ensure_small_state(bnmtf_model* h) {
 // bnmtf_set_small_path: 0 never, 1 by this rule (default), 2 always.
 static bool small_wanted(const bnmtf_model* h, int batch = 1) {
   if (!(h->small && h->small_mode != 0 && h->use_fast && h->profiling == 0)) return false;
+  if (h->held_n) return false;               // a held-out mask (bnmtf_set_heldout): its kernel follows each iteration of the multi-launch loop
   if (h->small_mode == 2) return true;
   // (the tri-factorisation: alone, a model that fills a CU runs 4.0 k iterations/s here against 6.5 k on the multi-launch path with the
   // whole chip to itself (622 x 138, K = L = 10); two of them in one call are already ahead.  Ranks above 10 take the S step's

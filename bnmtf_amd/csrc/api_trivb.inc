@@ -456,6 +456,7 @@ int bnmtf_vb_run(bnmtf_handle h, int n_iter, const int32_t* orders, double* expt
   if (h->tri_order_cap < (size_t)n_iter * per) { dfree(h->tri_order); CHK(dalloc(&h->tri_order, (size_t)n_iter * per, false)); h->tri_order_cap = (size_t)n_iter * per; }
   HIPCHK(hipMemcpy(h->tri_order, orders, (size_t)n_iter * per * sizeof(int), hipMemcpyHostToDevice));
   CHK(vb_reserve_rec(h, n_iter));
+  CHK(heldout_begin(h, n_iter));
   EventList ev;
   CHK(ev.create(times_out ? n_iter + 1 : 0));
   if (times_out) HIPCHK(hipEventRecord(ev[0], h->stream));
@@ -467,6 +468,7 @@ int bnmtf_vb_run(bnmtf_handle h, int n_iter, const int32_t* orders, double* expt
   HIPCHK(hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));
   for (int it = 0; it < n_iter; ++it) {
     CHK(enqueue_trivb_iteration(h, it, false));
+    heldout_enqueue(h, it, h->stream);           // (a mask set: on E[F], E[S], E[G] of this iteration)
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], h->stream));
   }
   if (h->comm)      // the q parameters of the other ranks' rows / columns (bnmtf_vb_get_state returns whole matrices)
@@ -475,6 +477,7 @@ int bnmtf_vb_run(bnmtf_handle h, int n_iter, const int32_t* orders, double* expt
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
   drain_events(h);
+  heldout_end(h, n_iter);
   std::vector<double> rec((size_t)n_iter * 16);
   HIPCHK(hipMemcpy(rec.data(), h->vb_rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
   unpack_vb_rec(rec.data(), n_iter, exptau_out, perf_out, elbo_terms_out);       // (terms: esd, beta_s, the four sums of F, the four of G)

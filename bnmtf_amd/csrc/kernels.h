@@ -519,4 +519,25 @@ void launch_np_s_pass(const NpSPassArgs& a, hipStream_t st);
 void record_np_copy(const float* src, float* dst, int n);   // (many.h: a list-form record only) dst[0 .. n) = src[0 .. n)
 void launch_np_metrics(const float* R, const uint8_t* M, const float* Ut, const float* Yt, int I, int J, int K, double* part, hipStream_t st);
 
+// ---------------------------------------------------------------------------
+// Held-out metric sums of the current factors, once per iteration (kernel_heldout.hip): the six sums of metrics_from_sums over a
+// sparse list of entries, fp64, no pass over R
+// ---------------------------------------------------------------------------
+constexpr int kHeldoutRowsPerBlock = 4;      // a wave per row of R, four waves per block
+struct HeldoutArgs {
+  const uint32_t* rowptr;            // [I + 1] the held-out entries of row i are [rowptr[i], rowptr[i + 1])
+  const uint32_t* col;               // [n] their columns, ascending within a row
+  const float* rval;                 // [n] their values of R
+  int I;
+  const float* A; int KPa, Wa;       // rows factor [I][KPa] (U, or F), Wa columns in use
+  const float* B; int KPb, Wb;       // columns factor [J][KPb] (V, or G)
+  const float* S; int K, L;          // tri-factorisation: [K][L] unpadded; null: P = A B^T
+  double* part;                      // [heldout_blocks(I)][8] the blocks' partial sums
+  double* rec;                       // [8] the iteration's record: n, sum R, sum R^2, sum P, sum P^2, sum R P, 0, 0
+};
+inline int heldout_blocks(int I) { return (I + kHeldoutRowsPerBlock - 1) / kHeldoutRowsPerBlock; }
+void launch_heldout(const HeldoutArgs& a, hipStream_t st);
+// rval[e] = R[i][col[e]] for the entries e of every row i (R [I][J])
+void launch_heldout_values(const float* R, int I, int J, const uint32_t* rowptr, const uint32_t* col, float* rval, hipStream_t st);
+
 }  // namespace bnmtf

@@ -212,4 +212,8 @@ struct bnmtf_model {
   hipEvent_t snap_ready[8] = {nullptr}, copy_done[8] = {nullptr};
   double create_ms = 0.0;                                   // wall time of bnmtf_create (host layout + uploads)
   bnmtf::NpState* np = nullptr;                             // a handle of bnmtf_np_create (nmf_np / nmtf_np): its buffers
+  // held-out performance per iteration (bnmtf_set_heldout; api_heldout.inc, kernel_heldout.hip): the row-sorted list of the mask's
+  // entries, the blocks' partial sums, the record [iterations][8] of the last run call and the iterations it holds
+  uint32_t* held_rowptr = nullptr; uint32_t* held_col = nullptr; float* held_val = nullptr; size_t held_n = 0;
+  double* held_part = nullptr; double* held_rec = nullptr; size_t held_rec_cap = 0; int held_iters = 0;
 };

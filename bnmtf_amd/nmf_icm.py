@@ -36,17 +36,21 @@ class nmf_icm(bnmf_gibbs_optimised):
             self.V = 1.0 / self.lambdaV
         self.tau = gamma_mode(self.alpha_s(), self.beta_s())
 
-    def run(self, iterations, minimum_TN=0.):
-        """:114-150.  One device call runs all iterations; returns None like the reference."""
+    def run(self, iterations, minimum_TN=0., *, M_test=None):
+        """:114-150.  One device call runs all iterations; returns None like the reference.  M_test: the held-out metrics of the
+        point estimate every iteration ends with, in all_performances_test (see bnmf_gibbs_optimised.run)."""
+        Mt = self._check_heldout(M_test)
         it = int(iterations)
         if self._blocks is not None:            # ranks above 64: column blocks (_blocked.py), ICM rules
             self._run_blocked(it, _lib.UPDATE_ICM, False, None, minimum_TN=float(minimum_TN), icm=True)
             return
         self._push()
+        self._set_heldout(Mt)
         taus = np.zeros(it); perf = np.zeros((it, 3)); times = np.zeros(it)
         L = _lib.lib()
         _lib.check(L.bnmtf_set_minimum_tn(self._handle(), float(minimum_TN)))
         _lib.check(L.bnmf_gibbs_run(self._handle(), it, _lib.UPDATE_ICM, None, None, _lib.ptr(taus), _lib.ptr(perf), _lib.ptr(times)))
+        self._finish_heldout(it)
         self._pull()
         self.all_tau = taus
         self.all_times = list(times)

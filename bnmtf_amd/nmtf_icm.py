@@ -19,17 +19,20 @@ class nmtf_icm(bnmtf_gibbs_optimised):
         super().initialise(init_S=init_S, init_FG=init_FG)
         self.tau = gamma_mode(self.alpha_s(), self.beta_s())
 
-    def run(self, iterations, minimum_TN=0.):
-        """:132-173; returns None like the reference."""
+    def run(self, iterations, minimum_TN=0., *, M_test=None):
+        """:132-173; returns None like the reference.  M_test: see nmf_icm.run."""
+        Mt = self._check_heldout(M_test)
         it = int(iterations)
         if self._blocks is not None:           # K or L above 64: blocks (_blocked.py), the same updates with the Gamma mode for tau
             self._run_blocked(it, _lib.UPDATE_ICM, False, None, minimum_TN=float(minimum_TN), icm=True)
             return
         self._push()
+        self._set_heldout(Mt)
         taus = np.zeros(it); perf = np.zeros((it, 3)); times = np.zeros(it)
         L = _lib.lib()
         _lib.check(L.bnmtf_set_minimum_tn(self._handle(), float(minimum_TN)))
         _lib.check(L.bnmtf_gibbs_run(self._handle(), it, _lib.UPDATE_ICM, None, None, None, _lib.ptr(taus), _lib.ptr(perf), _lib.ptr(times)))
+        self._finish_heldout(it)
         self._pull()
         self.all_tau = taus
         self.all_times = list(times)

@@ -281,6 +281,20 @@ BNMTF_API int bnmtf_vb_run_many(bnmtf_handle* hs, int n_models, int n_iter, cons
 BNMTF_API int bnmtf_metric_sums(bnmtf_handle h, const uint8_t* Mp, const double* A, const double* S,
                       const double* B, double sums_out[6]);
 
+/* ---- held-out performance per iteration -----------------------------------
+ * The reference's convergence experiments follow the test error over the iterations by predict(M_test) on stored samples
+ * (experiments/experiments_toy/convergence/); here the run loops evaluate the state each iteration ends with -- the sample of a
+ * Gibbs run, the point estimate of ICM, E[.] of the variational models -- on a sparse list of held-out entries, on the device
+ * (csrc/kernel_heldout.hip: fp64 products of the fp32 factors, fixed summation order, no pass over R).
+ * M_test [I][J]: nonzero = held out (it may overlap the training mask, as predict() allows); NULL clears.  Any handle of
+ * bnmtf_create; one created with world > 1 is refused with BNMTF_EINVAL, as is a mask without entries.  While a mask is set,
+ * bnmf_gibbs_run, bnmtf_gibbs_run, bnmf_vb_run and bnmtf_vb_run record the six sums of every iteration, a model of the
+ * one-launch kind runs the multi-launch path, and the *_run_many entry points refuse the handle. */
+BNMTF_API int bnmtf_set_heldout(bnmtf_handle h, const double* M_test);
+/* the records of the last run call: sums_out [n_iter][6] = n, sum R, sum R^2, sum P, sum P^2, sum R P per iteration (R as the
+ * device holds it, fp32).  BNMTF_ESTATE if that call ran fewer than n_iter iterations or no mask was set. */
+BNMTF_API int bnmtf_get_heldout(bnmtf_handle h, int n_iter, double* sums_out);
+
 /* ---- distributions (stand-alone hooks; code/models/distributions/) ----- */
 /* TN_vector_draw (truncated_normal_vector.py:37-50): out[e] ~ TN(mu[e],tau[e]) on
  * [0,inf); RNG counter (elem0+e, col, it, STREAM_HOOK). */
