@@ -592,6 +592,9 @@ static void enqueue_vb_sweep(bnmtf_model* h, Dir& d, Dir& o, uint32_t stream_id,
 }
 static int vb_esd_direct(bnmtf_model* h, double* out, double* terms = nullptr) {
   const int I = h->I, J = h->J, K = h->K;
+  // metric_kernel's second-moment pass is one load of 32 x K into tiles of 64 columns (not chunked like its first product), and
+  // Ad / Bd / A2d / B2d hold 64 columns: a handle is at most BNMTF_MAX_RANK = 64 wide (bnmtf_create), wider models are column blocks
+  if (K > 64) { set_error("exp_square_diff: a handle of %d columns (the second-moment pass holds 64; wider models run as column blocks)", K); return BNMTF_EINVAL; }
   std::vector<double> a((size_t)I * K), b((size_t)J * K), a2((size_t)I * K), b2((size_t)J * K);
   CHK(download_matrix(h, h->rows.X, I, K, h->rows.KP, a.data()));
   CHK(download_matrix(h, h->cols.X, J, K, h->cols.KP, b.data()));
