@@ -79,7 +79,58 @@ def metrics_from_sums(s):
     return {"MSE": sse / n, "R^2": (1.0 - sse / ss_tot) if ss_tot != 0.0 else np.inf, "Rp": float(rp)}
 
 
-class DeviceModel(object):
+class HeldoutMixin(object):
+    """Held-out performance per iteration, run(..., M_test=): what the classes that own a device handle (`_h`, `_handle()`, R) share
+    -- DeviceModel's and nmf_np.NPDevice's.  The mask is validated on the host, set on the handle before the device call and its
+    record of six sums per iteration finished into all_performances_test behind it."""
+
+    def _check_heldout(self, M_test):
+        """run()'s M_test argument, before any device call: None, or the 0/1 mask as contiguous fp64 (what bnmtf_set_heldout
+        takes).  Same shape as R, at least one entry; it may overlap the training mask, as predict() allows."""
+        if M_test is None:
+            return None
+        Mt = np.asarray(M_test)
+        assert Mt.shape == self.R.shape, "Input matrix R is not of the same size as the held-out indicator matrix M_test: " \
+            "%s and %s respectively." % (self.R.shape, Mt.shape)
+        assert ((Mt == 0) | (Mt == 1)).all(), "The indicator matrix M_test must contain only 0 and 1."
+        assert Mt.any(), "The held-out indicator matrix M_test has no entries."
+        from ._lib import BnmtfError
+        if getattr(self, "_blocks", None) is not None:
+            raise BnmtfError("%s: run(M_test=) is not available for a model in column blocks (a rank above 64): its factors live "
+                             "in several device models; use predict(M_test) after the run" % type(self).__name__)
+        if getattr(self, "_world", 1) > 1:
+            raise BnmtfError("%s: run(M_test=) is not available for a sharded model (world = %d): the held-out record is kept "
+                             "on one GPU only" % (type(self).__name__, self._world))
+        return np.ascontiguousarray(Mt, dtype=np.float64)
+
+    def _set_heldout(self, Mt):
+        """The mask of _check_heldout onto the handle -- or, with None, a mask left there by an earlier run() off it."""
+        held = getattr(self, "_heldout", None)
+        if Mt is None:
+            if held is not None and held[0] is self._h:
+                _lib.check(_lib.lib().bnmtf_set_heldout(self._handle(), None))
+            self._heldout = None
+            if hasattr(self, "all_performances_test"):
+                del self.all_performances_test
+            return
+        _lib.check(_lib.lib().bnmtf_set_heldout(self._handle(), _lib.ptr(Mt)))
+        self._heldout = (self._h, int(Mt.sum()))
+
+    def _heldout_sums(self, iterations):
+        """[iterations][6] held-out sums of the last run() call (n, sum R, sum R^2, sum P, sum P^2, sum R P)."""
+        sums = np.zeros((int(iterations), 6))
+        _lib.check(_lib.lib().bnmtf_get_heldout(self._handle(), int(iterations), _lib.ptr(sums)))
+        return sums
+
+    def _finish_heldout(self, iterations):
+        """Behind a run() that was given M_test: all_performances_test, finished on the host like all the metrics."""
+        if getattr(self, "_heldout", None) is None:
+            return
+        per = [metrics_from_sums(s) for s in self._heldout_sums(iterations)]
+        self.all_performances_test = {m: [p[m] for p in per] for m in ('MSE', 'R^2', 'Rp')}
+
+
+class DeviceModel(HeldoutMixin):
     """Owns the bnmtf_handle of one model instance (created lazily, after any fork)."""
 
     def _init_device(self, seed, device, rank, world, comm_id):
@@ -164,52 +215,6 @@ class DeviceModel(object):
         tau = C.c_double(); cnt = C.c_uint64()
         _lib.check(_lib.lib().bnmtf_get_expectation(self._handle(), _lib.ptr(A), _lib.ptr(S), _lib.ptr(B), C.byref(tau), C.byref(cnt)))
         return (A, S, B, tau.value)
-
-    # -- held-out performance per iteration: run(..., M_test=) ---------------------
-    def _check_heldout(self, M_test):
-        """run()'s M_test argument, before any device call: None, or the 0/1 mask as contiguous fp64 (what bnmtf_set_heldout
-        takes).  Same shape as R, at least one entry; it may overlap the training mask, as predict() allows."""
-        if M_test is None:
-            return None
-        Mt = np.asarray(M_test)
-        assert Mt.shape == self.R.shape, "Input matrix R is not of the same size as the held-out indicator matrix M_test: " \
-            "%s and %s respectively." % (self.R.shape, Mt.shape)
-        assert ((Mt == 0) | (Mt == 1)).all(), "The indicator matrix M_test must contain only 0 and 1."
-        assert Mt.any(), "The held-out indicator matrix M_test has no entries."
-        from ._lib import BnmtfError
-        if getattr(self, "_blocks", None) is not None:
-            raise BnmtfError("%s: run(M_test=) is not available for a model in column blocks (a rank above 64): its factors live "
-                             "in several device models; use predict(M_test) after the run" % type(self).__name__)
-        if self._world > 1:
-            raise BnmtfError("%s: run(M_test=) is not available for a sharded model (world = %d): the held-out record is kept "
-                             "on one GPU only" % (type(self).__name__, self._world))
-        return np.ascontiguousarray(Mt, dtype=np.float64)
-
-    def _set_heldout(self, Mt):
-        """The mask of _check_heldout onto the handle -- or, with None, a mask left there by an earlier run() off it."""
-        held = getattr(self, "_heldout", None)
-        if Mt is None:
-            if held is not None and held[0] is self._h:
-                _lib.check(_lib.lib().bnmtf_set_heldout(self._handle(), None))
-            self._heldout = None
-            if hasattr(self, "all_performances_test"):
-                del self.all_performances_test
-            return
-        _lib.check(_lib.lib().bnmtf_set_heldout(self._handle(), _lib.ptr(Mt)))
-        self._heldout = (self._h, int(Mt.sum()))
-
-    def _heldout_sums(self, iterations):
-        """[iterations][6] held-out sums of the last run() call (n, sum R, sum R^2, sum P, sum P^2, sum R P)."""
-        sums = np.zeros((int(iterations), 6))
-        _lib.check(_lib.lib().bnmtf_get_heldout(self._handle(), int(iterations), _lib.ptr(sums)))
-        return sums
-
-    def _finish_heldout(self, iterations):
-        """Behind a run() that was given M_test: all_performances_test, finished on the host like all the metrics."""
-        if getattr(self, "_heldout", None) is None:
-            return
-        per = [metrics_from_sums(s) for s in self._heldout_sums(iterations)]
-        self.all_performances_test = {m: [p[m] for p in per] for m in ('MSE', 'R^2', 'Rp')}
 
     # -- device facts ---------------------------------------------------------
     def omega_counts(self):

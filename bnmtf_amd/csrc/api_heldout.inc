@@ -20,15 +20,18 @@ static int heldout_begin(bnmtf_model* h, int n_iter) {
   return BNMTF_OK;
 }
 
-// behind the last kernel of iteration `it` of the call, on the stream that ran it: the sums of the state the iteration ends with
+// behind the last kernel of iteration `it` of the call, on the stream that ran it: the sums of the state the iteration ends with.
+// While a Recorder is installed (a lock-step run_many) the pair is recorded behind the iteration's records; its arguments are then
+// the same bytes in every iteration.  A handle of bnmtf_np_create: np_heldout_enqueue (api_np.inc).
 static void heldout_enqueue(bnmtf_model* h, int it, hipStream_t st) {
   if (!h->held_n) return;
   HeldoutArgs a;
+  memset(&a, 0, sizeof(a));                              // (padding too: a recorded list compares argument bytes)
   a.rowptr = h->held_rowptr; a.col = h->held_col; a.rval = h->held_val; a.I = h->I;
   a.A = h->rows.X; a.KPa = h->rows.KP; a.Wa = h->rows.W;
   a.B = h->cols.X; a.KPb = h->cols.KP; a.Wb = h->cols.W;
   a.S = h->L > 0 ? h->S : nullptr; a.K = h->K; a.L = h->L;
-  a.part = h->held_part; a.rec = h->held_rec + (size_t)it * 8;
+  a.part = h->held_part; a.rec = g_recorder ? h->held_rec : h->held_rec + (size_t)it * 8;
   launch_heldout(a, st);
 }
 
@@ -37,7 +40,7 @@ static void heldout_end(bnmtf_model* h, int n_iter) {
   if (h->held_n) h->held_iters = n_iter;
 }
 
-// the *_run_many entry points take no model with a mask (its record would have nowhere to go)
+// the one-launch *_gibbs_run_many entry points take no model with a mask (their kernel has no per-iteration hook)
 static int heldout_refuse_many(const bnmtf_model* h, const char* entry, int b) {
   if (!h->held_n) return BNMTF_OK;
   set_error("%s: model %d has a held-out mask (bnmtf_set_heldout): clear it, or run the model by its own run call", entry, b);
@@ -50,7 +53,6 @@ extern "C" {
 
 int bnmtf_set_heldout(bnmtf_handle h, const double* M_test) try {
   if (!h) { set_error("bnmtf_set_heldout: null handle"); return BNMTF_EINVAL; }
-  if (h->np) { set_error("bnmtf_set_heldout: a handle of bnmtf_np_create keeps no held-out record"); return BNMTF_EINVAL; }
   if (h->world > 1) { set_error("bnmtf_set_heldout: a sharded model (world = %d) keeps no held-out record: one GPU only", h->world); return BNMTF_EINVAL; }
   if (h->block_mode) { set_error("bnmtf_set_heldout: a block of a wider factorisation keeps no held-out record"); return BNMTF_EINVAL; }
   HIPCHK(hipSetDevice(h->device));

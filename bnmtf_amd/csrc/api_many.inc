@@ -135,6 +135,8 @@ struct ManyFamily {
   int (*run_alone)(bnmtf_model*, int n_iter, const int32_t* orders, const ManyOut& o);   // the model's own entry point
   int (*read_out)(bnmtf_model*, int n_iter, const ManyOut& o);         // the device record -> the family's outputs
 };
+// (every family: a model with a held-out mask -- bnmtf_set_heldout -- reserves its record in prepare and appends the held-out launch
+// pair at kHeldoutSite behind the iteration's records; a model without one records nothing there.)
 
 int check_many_handles(const ManyFamily& f, bnmtf_handle* hs, int n_models, int n_iter, const int32_t* const* orders) {
   if (n_models < 0 || (n_models > 0 && (!hs || (f.takes_orders && !orders)))) {
@@ -202,7 +204,8 @@ int run_many(const ManyFamily& f, bnmtf_handle* hs, int n_models, int n_iter, co
       CHK(f.enqueue(hs[batch[i]], it));
       if (recs[i].missing) { set_error("run_many: a recorded iteration met a kernel without a list form (%s)", recs[i].missing); return BNMTF_ESTATE; }
       if (recs[i].keys.size() != recs[i].recs.size()) { set_error("run_many: model %d has %zu records and %zu site keys", batch[i], recs[i].recs.size(), recs[i].keys.size()); return BNMTF_ESTATE; }
-      if (f.same_length && recs[i].recs.size() != recs[0].recs.size()) { set_error("run_many: model %d enqueues %d launches an iteration, model 0 %d", (int)i, (int)recs[i].recs.size(), (int)recs[0].recs.size()); return BNMTF_ESTATE; }
+      auto unnamed = [](const Recorder& r) { size_t n = 0; for (const auto& k : r.keys) n += k.first < 0; return n; };      // (the held-out pair has a site)
+      if (f.same_length && unnamed(recs[i]) != unnamed(recs[0])) { set_error("run_many: model %d enqueues %d launches an iteration, model 0 %d", (int)i, (int)unnamed(recs[i]), (int)unnamed(recs[0])); return BNMTF_ESTATE; }
       same = same && recs[i].keys == last[i];
     }
     if (!same) {                                       // (the first iteration of a call may differ from the later ones)
@@ -214,6 +217,7 @@ int run_many(const ManyFamily& f, bnmtf_handle* hs, int n_models, int n_iter, co
   }
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
+  for (int b : batch) heldout_end(hs[b], n_iter);
   if (launch_info) { launch_info[0] = (int)nb; launch_info[1] = (int)uploads; }
   std::vector<double> tm(times_out ? n_iter : 0);
   ev.seconds((int)tm.size(), tm.data());
@@ -234,6 +238,7 @@ int vb_read_out(bnmtf_model* h, int n_iter, const ManyOut& o) {
 // (acc: zeroed on the model's own stream, which the driver drains next)
 int vb_prepare(bnmtf_model* h, int n_iter, const int32_t*) {
   CHK(vb_reserve_rec(h, n_iter));
+  CHK(heldout_begin(h, n_iter));
   HIPCHK(hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));
   return BNMTF_OK;
 }
@@ -242,9 +247,9 @@ int vb_prepare(bnmtf_model* h, int n_iter, const int32_t*) {
 // problems, per-kernel timers on.
 const ManyFamily kVbFamily = {
   "bnmf_vb_run_many", {1, 3, 10}, false, true, true,
-  [](bnmtf_model* h, int b) { if (h->vb_ready && h->have_state) return heldout_refuse_many(h, "bnmf_vb_run_many", b); set_error("bnmf_vb_run_many before bnmf_vb_set_state (model %d)", b); return BNMTF_ESTATE; },
+  [](bnmtf_model* h, int b) { if (h->vb_ready && h->have_state) return BNMTF_OK; set_error("bnmf_vb_run_many before bnmf_vb_set_state (model %d)", b); return BNMTF_ESTATE; },
   vb_batchable, vb_prepare,
-  [](bnmtf_model* h, int it) { return enqueue_vb_iteration(h, it, true); },
+  [](bnmtf_model* h, int it) { CHK(enqueue_vb_iteration(h, it, true)); heldout_enqueue(h, it, h->stream); return BNMTF_OK; },
   [](bnmtf_model* h, int n_iter, const int32_t*, const ManyOut& o) { return bnmf_vb_run(h, n_iter, o.a[0], o.a[1], o.a[2], o.times); },
   vb_read_out};
 
@@ -252,7 +257,7 @@ const ManyFamily kVbFamily = {
 // them).  Not batched: several GPUs, per-kernel timers, the 16-wave sweeps, an A/B switch.
 const ManyFamily kTriVbFamily = {
   "bnmtf_vb_run_many", {1, 3, 10}, true, false, false,
-  [](bnmtf_model* h, int b) { if (h->tri_ready && h->have_state) return heldout_refuse_many(h, "bnmtf_vb_run_many", b); set_error("bnmtf_vb_run_many before bnmtf_vb_set_state (model %d)", b); return BNMTF_ESTATE; },
+  [](bnmtf_model* h, int b) { if (h->tri_ready && h->have_state) return BNMTF_OK; set_error("bnmtf_vb_run_many before bnmtf_vb_set_state (model %d)", b); return BNMTF_ESTATE; },
   trivb_batchable,
   [](bnmtf_model* h, int n_iter, const int32_t* orders) {
     const size_t n = (size_t)n_iter * ((size_t)h->K * h->L + h->K + h->L);
@@ -260,7 +265,7 @@ const ManyFamily kTriVbFamily = {
     HIPCHK(hipMemcpy(h->tri_order, orders, n * sizeof(int), hipMemcpyHostToDevice));
     return vb_prepare(h, n_iter, nullptr);
   },
-  [](bnmtf_model* h, int it) { return enqueue_trivb_iteration(h, it, true); },
+  [](bnmtf_model* h, int it) { CHK(enqueue_trivb_iteration(h, it, true)); heldout_enqueue(h, it, h->stream); return BNMTF_OK; },
   [](bnmtf_model* h, int n_iter, const int32_t* orders, const ManyOut& o) { return bnmtf_vb_run(h, n_iter, orders, o.a[0], o.a[1], o.a[2], o.times); },
   vb_read_out};
 
@@ -273,8 +278,8 @@ const ManyFamily kNpFamily = {
     return BNMTF_OK;
   },
   [](bnmtf_model*) { return true; },
-  [](bnmtf_model* h, int n_iter, const int32_t*) { return np_reserve_rec(h->np, n_iter); },
-  [](bnmtf_model* h, int) { return np_iteration(h, h->np->rec); },
+  [](bnmtf_model* h, int n_iter, const int32_t*) { CHK(np_reserve_rec(h->np, n_iter)); return heldout_begin(h, n_iter); },
+  [](bnmtf_model* h, int it) { CHK(np_iteration(h, h->np->rec)); np_heldout_enqueue(h, it); return BNMTF_OK; },
   [](bnmtf_model* h, int n_iter, const int32_t*, const ManyOut& o) { HIPCHK(hipSetDevice(h->device)); return np_run(h, n_iter, o.a[0], o.a[1], o.times); },
   [](bnmtf_model* h, int n_iter, const ManyOut& o) {
     std::vector<double> rec((size_t)n_iter * 8);

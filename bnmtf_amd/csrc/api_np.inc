@@ -136,6 +136,19 @@ static int np_iteration(bnmtf_model* h, double* stats_out) {
   return BNMTF_OK;
 }
 
+// The held-out sums (api_heldout.inc) of the factors iteration `it` of the call ends with, behind its last kernel -- or, while a
+// Recorder is installed, recorded behind its records.  fp64 from the fp32 factors themselves, not through Y.
+static void np_heldout_enqueue(bnmtf_model* h, int it) {
+  if (!h->held_n) return;
+  NpState* s = h->np;
+  HeldoutNpArgs a; memset(&a, 0, sizeof(a));                  // (padding too: a recorded list compares argument bytes)
+  a.rowptr = h->held_rowptr; a.col = h->held_col; a.rval = h->held_val;
+  a.Xr = s->Xr; a.Xc = s->Xc; a.S = h->L > 0 ? s->S : nullptr;
+  a.part = h->held_part; a.rec = g_recorder ? h->held_rec : h->held_rec + (size_t)it * 8;
+  a.I = h->I; a.J = h->J; a.K = h->K; a.L = h->L;
+  launch_heldout_np(a, h->stream);
+}
+
 // the record of n_iter iterations of 8 sums each; either output may be null
 static void unpack_np_rec(const double* rec, int n_iter, double* perf, double* idiv) {
   for (int it = 0; it < n_iter; ++it) {
@@ -157,15 +170,18 @@ static int np_run(bnmtf_model* h, int n_iter, double* perf_out, double* idiv_out
   if (n_iter < 0) { set_error("run: negative iteration count"); return BNMTF_EINVAL; }
   if (n_iter == 0) return BNMTF_OK;
   CHK(np_reserve_rec(s, n_iter));
+  CHK(heldout_begin(h, n_iter));
   EventList ev;
   CHK(ev.create(times_out ? n_iter + 1 : 0));
   if (times_out) HIPCHK(hipEventRecord(ev[0], h->stream));
   for (int it = 0; it < n_iter; ++it) {
     CHK(np_iteration(h, s->rec + (size_t)it * 8));
+    np_heldout_enqueue(h, it);                   // (a mask set: on U, V or F, S, G of this iteration)
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], h->stream));
   }
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
+  heldout_end(h, n_iter);
   std::vector<double> rec((size_t)n_iter * 8);
   HIPCHK(hipMemcpy(rec.data(), s->rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
   unpack_np_rec(rec.data(), n_iter, perf_out, idiv_out);

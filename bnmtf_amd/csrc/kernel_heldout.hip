@@ -15,7 +15,18 @@
 // order; a butterfly over the wave; the block's four waves in wave order (LDS [4][6]: consecutive doubles, one bank pair each);
 // heldout_fold_kernel adds the blocks' partials, thread t blocks t, t + 256, ..., then a tree over LDS [6][256] (thread-major:
 // conflict-free).
+//
+// Column-major factors of rank up to 256 (the handles of bnmtf_np_create: U [K][I], V [K][J], or F, S, G): heldout_np_kernel.
+// Same grid, same partials, same fold.  The lanes run along the row's entries instead -- lane l takes entries beg + l, beg + l + 64,
+// ... -- and for a fixed k the 64 addresses V[k J + j_l] ascend within one stretch of column k.  The row's own factor row (U_ik, or
+// (F_i S)_l formed in fp64 from the fp32 F_i and S, lanes along l) is staged once per row in LDS as doubles ([4][256], 8 KiB) and
+// read by broadcast.  Order of the sums: the lane's entries in list order, then as above.
+//
+// List forms (many.h): blockIdx.z = model, the arguments through load_pack, the single-model kernels' bodies.  The main kernels
+// leave with blockIdx.x >= the model's own heldout_blocks(I); the fold finds its record `it` records behind the run's first, so a
+// model's argument bytes are the same in every iteration.
 #include "kernels.h"
+#include "many.h"
 
 namespace bnmtf {
 
@@ -28,7 +39,7 @@ __device__ inline double wave_sum(double v) {
 }
 
 template <int KP, bool TRI>
-__global__ __launch_bounds__(256) void heldout_kernel(HeldoutArgs a) {
+__device__ __forceinline__ void heldout_body(const HeldoutArgs& a) {
   constexpr int LPE = KP / 4;          // lanes per entry
   constexpr int EPS = 64 / LPE;        // entries per wave step
   __shared__ __attribute__((aligned(16))) float Ssh[TRI ? 64 * KP : 4];     // S [K][KP], zero beyond column L
@@ -102,8 +113,90 @@ __global__ __launch_bounds__(256) void heldout_kernel(HeldoutArgs a) {
   }
 }
 
+template <int KP, bool TRI>
+__global__ __launch_bounds__(256) void heldout_kernel(HeldoutArgs a) { heldout_body<KP, TRI>(a); }
+
+template <int KP, bool TRI>
+__global__ __launch_bounds__(256) void heldout_many(const HeldoutArgs* list, int) {
+  const HeldoutArgs a = load_pack(list, blockIdx.z);
+  if ((int)blockIdx.x >= heldout_blocks(a.I)) return;
+  heldout_body<KP, TRI>(a);
+}
+
+// Column-major fp32 factors, ranks up to kHeldoutNpMaxRank: a lane per entry of the row.
+template <bool TRI>
+__device__ __forceinline__ void heldout_np_body(const HeldoutNpArgs& a) {
+  __shared__ double rowf[kHeldoutRowsPerBlock][kHeldoutNpMaxRank];       // the waves' factor rows: U_i, or F_i S
+  __shared__ double red[kHeldoutRowsPerBlock][6];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.x * kHeldoutRowsPerBlock + wave;
+  const bool row_ok = i < a.I;
+  const int W = TRI ? a.L : a.K;                 // columns of the row's factor row = rows of Xc
+  double* const mine = rowf[wave];
+
+  // ---- the row's factor row, fp64, lanes along its columns
+  if (row_ok) {
+    if (TRI) {
+      for (int l = lane; l < W; l += 64) {
+        double v = 0.0;
+        for (int k = 0; k < a.K; ++k) v = fma((double)a.Xr[(size_t)k * a.I + i], (double)a.S[(size_t)k * a.L + l], v);
+        mine[l] = v;
+      }
+    } else {
+      for (int k = lane; k < W; k += 64) mine[k] = (double)a.Xr[(size_t)k * a.I + i];
+    }
+  }
+  __syncthreads();
+
+  // ---- the row's entries, 64 per step
+  const uint32_t beg = row_ok ? a.rowptr[i] : 0u, end = row_ok ? a.rowptr[i + 1] : 0u;
+  double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  uint32_t e = beg + (uint32_t)lane;
+  bool live = e < end;
+  uint32_t j = live ? a.col[e] : 0u;
+  float r32 = live ? a.rval[e] : 0.f;
+  for (uint32_t base = beg; base < end; base += 64) {
+    const float* bcol = a.Xc + j;                // (a lane without an entry reads column 0: J >= 1)
+    const uint32_t en = e + 64;
+    const bool ln = en < end;
+    const uint32_t jn = ln ? a.col[en] : 0u;
+    const float rn = ln ? a.rval[en] : 0.f;
+    double p = 0.0;
+#pragma unroll 4
+    for (int k = 0; k < W; ++k) p = fma(mine[k], (double)bcol[(size_t)k * a.J], p);
+    if (live) {
+      const double r = (double)r32;
+      s[0] += 1.0; s[1] += r; s[2] = fma(r, r, s[2]); s[3] += p; s[4] = fma(p, p, s[4]); s[5] = fma(r, p, s[5]);
+    }
+    e = en; live = ln; j = jn; r32 = rn;
+  }
+
+  // ---- wave, then block
+#pragma unroll
+  for (int m = 0; m < 6; ++m) s[m] = wave_sum(s[m]);
+  if (lane == 0)
+    for (int m = 0; m < 6; ++m) red[wave][m] = s[m];
+  __syncthreads();
+  if (threadIdx.x < 8) {
+    double v = 0.0;
+    if (threadIdx.x < 6)
+      for (int w = 0; w < kHeldoutRowsPerBlock; ++w) v += red[w][threadIdx.x];
+    a.part[(size_t)blockIdx.x * 8 + threadIdx.x] = v;
+  }
+}
+
+template <bool TRI>
+__global__ __launch_bounds__(256) void heldout_np_kernel(HeldoutNpArgs a) { heldout_np_body<TRI>(a); }
+
+template <bool TRI>
+__global__ __launch_bounds__(256) void heldout_np_many(const HeldoutNpArgs* list, int) {
+  const HeldoutNpArgs a = load_pack(list, blockIdx.z);
+  if ((int)blockIdx.x >= heldout_blocks(a.I)) return;
+  heldout_np_body<TRI>(a);
+}
+
 // the blocks' partial sums in a fixed order, into the iteration's record
-__global__ __launch_bounds__(256) void heldout_fold_kernel(const double* part, int nblocks, double* rec) {
+__device__ __forceinline__ void heldout_fold_body(const double* part, int nblocks, double* rec) {
   __shared__ double red[6][256];
   const int tid = threadIdx.x;
   double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -117,6 +210,24 @@ __global__ __launch_bounds__(256) void heldout_fold_kernel(const double* part, i
   }
   if (tid < 8) rec[tid] = tid < 6 ? red[tid][0] : 0.0;
 }
+__global__ __launch_bounds__(256) void heldout_fold_kernel(const double* part, int nblocks, double* rec) { heldout_fold_body(part, nblocks, rec); }
+// list form: rec = the run's FIRST record, the iteration's one is `it` records behind it (the argument list stays the same)
+struct HeldoutFoldPack { const double* part; double* rec; int nblocks, pad; };
+__global__ __launch_bounds__(256) void heldout_fold_many(const HeldoutFoldPack* list, int it) {
+  const HeldoutFoldPack p = load_pack(list, blockIdx.z);
+  heldout_fold_body(p.part, p.nblocks, p.rec + (size_t)it * 8);
+}
+
+// the fold behind a main kernel of `nblocks` blocks -- launched, or recorded behind the main kernel's record
+void launch_fold(const double* part, int nblocks, double* rec, hipStream_t st) {
+  if (g_recorder) {
+    HeldoutFoldPack p; memset(&p, 0, sizeof(p));
+    p.part = part; p.rec = rec; p.nblocks = nblocks;
+    record_launch((const void*)heldout_fold_many, dim3(1), dim3(256), 0, p);
+    return;
+  }
+  hipLaunchKernelGGL(heldout_fold_kernel, dim3(1), dim3(256), 0, st, part, nblocks, rec);
+}
 
 // the values of R at the listed entries: a wave per row, its lanes along the row's entries
 __global__ __launch_bounds__(256) void heldout_values_kernel(const float* R, int I, int J, const uint32_t* rowptr, const uint32_t* col, float* rval) {
@@ -129,16 +240,33 @@ __global__ __launch_bounds__(256) void heldout_values_kernel(const float* R, int
 
 }  // namespace
 
+// While a Recorder is installed (many.h): a.rec is the run's first record, and the pair is recorded at kHeldoutSite, behind every
+// site of the model's family.  (The caller has zeroed the pack's padding: a recorded list compares argument bytes.)
 void launch_heldout(const HeldoutArgs& a, hipStream_t st) {
   const dim3 grid(heldout_blocks(a.I)), block(256);
-  if (a.S) {
+  if (g_recorder) {
+    const void* fn = a.S ? (a.KPb == 32 ? (const void*)heldout_many<32, true> : (const void*)heldout_many<64, true>)
+                         : (a.KPb == 32 ? (const void*)heldout_many<32, false> : (const void*)heldout_many<64, false>);
+    site_at(kHeldoutSite);
+    record_launch(fn, grid, block, 0, a, true);
+  } else if (a.S) {
     if (a.KPb == 32) hipLaunchKernelGGL((heldout_kernel<32, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((heldout_kernel<64, true>), grid, block, 0, st, a);
   } else {
     if (a.KPb == 32) hipLaunchKernelGGL((heldout_kernel<32, false>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((heldout_kernel<64, false>), grid, block, 0, st, a);
   }
-  hipLaunchKernelGGL(heldout_fold_kernel, dim3(1), dim3(256), 0, st, (const double*)a.part, (int)grid.x, a.rec);
+  launch_fold(a.part, (int)grid.x, a.rec, st);
+}
+
+void launch_heldout_np(const HeldoutNpArgs& a, hipStream_t st) {
+  const dim3 grid(heldout_blocks(a.I)), block(256);
+  if (g_recorder) {
+    site_at(kHeldoutSite);
+    record_launch(a.S ? (const void*)heldout_np_many<true> : (const void*)heldout_np_many<false>, grid, block, 0, a, true);
+  } else if (a.S) hipLaunchKernelGGL(heldout_np_kernel<true>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(heldout_np_kernel<false>, grid, block, 0, st, a);
+  launch_fold(a.part, (int)grid.x, a.rec, st);
 }
 
 void launch_heldout_values(const float* R, int I, int J, const uint32_t* rowptr, const uint32_t* col, float* rval, hipStream_t st) {

@@ -535,8 +535,24 @@ struct HeldoutArgs {
   double* part;                      // [heldout_blocks(I)][8] the blocks' partial sums
   double* rec;                       // [8] the iteration's record: n, sum R, sum R^2, sum P, sum P^2, sum R P, 0, 0
 };
-inline int heldout_blocks(int I) { return (I + kHeldoutRowsPerBlock - 1) / kHeldoutRowsPerBlock; }
+// the same sums for the column-major fp32 factors of a handle of bnmtf_np_create (ranks up to kHeldoutNpMaxRank)
+constexpr int kHeldoutNpMaxRank = 256;
+struct HeldoutNpArgs {
+  const uint32_t* rowptr; const uint32_t* col; const float* rval;      // as above
+  const float* Xr;                   // [K][I] U, or F
+  const float* Xc;                   // [K][J] V, or [L][J] G
+  const float* S;                    // tri-factorisation: [K][L]; null: P = U V^T
+  double* part; double* rec;         // as above
+  int I, J, K, L;
+};
+// the site key of the held-out launch pair in a recorded iteration (many.h): behind every site of TriSite, NpSite and the
+// position-aligned records (site -1) of the bnmf_vb family
+constexpr int kHeldoutSite = 1 << 20;
+__host__ __device__ inline int heldout_blocks(int I) { return (I + kHeldoutRowsPerBlock - 1) / kHeldoutRowsPerBlock; }
+// launched on st -- or, while a Recorder is installed, recorded (then `rec` is the run's FIRST record: the list-form fold finds the
+// iteration's own) -- the main kernel and the fold
 void launch_heldout(const HeldoutArgs& a, hipStream_t st);
+void launch_heldout_np(const HeldoutNpArgs& a, hipStream_t st);
 // rval[e] = R[i][col[e]] for the entries e of every row i (R [I][J])
 void launch_heldout_values(const float* R, int I, int J, const uint32_t* rowptr, const uint32_t* col, float* rval, hipStream_t st);
 

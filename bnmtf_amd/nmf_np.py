@@ -9,6 +9,7 @@ owns a few rows, their data and their P = U V^T in registers); run() is one devi
     NMF = NMF(R, M, K)
     NMF.initialise(init_UV, expo_prior)     # 'ones' | 'random' | 'exponential'
     NMF.run(iterations)                     # fills all_times, all_performances; prints the I-divergence per iteration
+    NMF.run(iterations, M_test=Mt)          # ... and all_performances_test: MSE / R^2 / Rp on Mt behind every iteration
     NMF.predict(M_pred); NMF.compute_I_div()
 
 Same constructor arguments, attributes and assertion messages as the reference; build-only extras are keyword-only
@@ -19,7 +20,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._base import check_R_M, check_rank, compute_MSE, compute_R2, compute_Rp
+from ._base import HeldoutMixin, check_R_M, check_rank, compute_MSE, compute_R2, compute_Rp
 
 MAX_RANK_NP = 256
 
@@ -36,8 +37,9 @@ def metrics_from_np_sums(s):
     return {"MSE": sse / n, "R^2": (1.0 - sse / ss_tot) if ss_tot != 0.0 else np.inf, "Rp": float(rp)}
 
 
-class NPDevice(object):
-    """The bnmtf_np_create handle of one model (created at the first device call) and the calls both models share."""
+class NPDevice(HeldoutMixin):
+    """The bnmtf_np_create handle of one model (created at the first device call) and the calls both models share.  run(M_test=):
+    the helpers of _base.HeldoutMixin; the record holds six sums, finished with metrics_from_sums."""
 
     def _init_np(self, name, device, rank, world):
         if int(world) != 1 or int(rank) != 0:
@@ -95,10 +97,16 @@ class NPDevice(object):
         _lib.check(_lib.lib().bnmtf_np_metrics(self._handle(), _lib.ptr(Mp), _lib.ptr(out)))
         return out
 
-    def _run_device(self, fn, iterations):
+    def _run_device(self, fn, iterations, M_test=None):
+        """run(): M_test as the six other classes take it -- the held-out metrics of the factors every iteration ends with, in
+        all_performances_test; the attribute exists only after a call that was given a mask, and the trajectory is the same
+        bits with and without one."""
+        Mt = self._check_heldout(M_test)
         it = int(iterations)
         perf, idiv, times = self._run_prepare(it)
+        self._set_heldout(Mt)
         _lib.check(fn(self._handle(), it, _lib.ptr(perf), _lib.ptr(idiv), _lib.ptr(times)))
+        self._finish_heldout(it)
         return self._run_finish(it, perf, idiv, times)
 
     def _run_prepare(self, it):
@@ -167,10 +175,11 @@ class NMF(NPDevice):
             self.U = np.random.exponential(scale=1.0 / expo_prior, size=(self.I, self.K))
             self.V = np.random.exponential(scale=1.0 / expo_prior, size=(self.J, self.K))
 
-    def run(self, iterations):
-        """:87-107.  One device call runs all iterations."""
+    def run(self, iterations, *, M_test=None):
+        """:87-107.  One device call runs all iterations.  M_test: the held-out metrics of U V^T behind every iteration, in
+        all_performances_test (see bnmf_gibbs_optimised.run)."""
         self._check_initialised()
-        self._run_device(_lib.lib().bnmf_np_run, iterations)
+        self._run_device(_lib.lib().bnmf_np_run, iterations, M_test)
 
     def _check_initialised(self):
         assert hasattr(self, 'U') and hasattr(self, 'V'), "U and V have not been initialised - please run NMF.initialise() first."

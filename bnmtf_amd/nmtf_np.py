@@ -8,7 +8,7 @@ predecessor left -- one launch per entry, each applying the previous entry's cha
 
     NMTF = NMTF(R, M, K, L)
     NMTF.initialise(init_S, init_FG, expo_prior)    # init_S: 'ones'|'random'|'exponential'; init_FG: ... |'kmeans'
-    NMTF.run(iterations)
+    NMTF.run(iterations)                            # M_test=Mt: all_performances_test, the held-out metrics per iteration
     NMTF.predict(M_pred); NMTF.compute_I_div()
 
 One GPU; ranks 1 <= K, L <= 256."""
@@ -71,10 +71,11 @@ class NMTF(NPDevice):
             kmeans_G.cluster()
             self.G = kmeans_G.clustering_results + 0.2
 
-    def run(self, iterations):
-        """:116-144.  One device call runs all iterations."""
+    def run(self, iterations, *, M_test=None):
+        """:116-144.  One device call runs all iterations.  M_test: the held-out metrics of F S G^T behind every iteration, in
+        all_performances_test (see bnmf_gibbs_optimised.run)."""
         self._check_initialised()
-        self._run_device(_lib.lib().bnmtf_np_run, iterations)
+        self._run_device(_lib.lib().bnmtf_np_run, iterations, M_test)
 
     def _check_initialised(self):
         assert hasattr(self, 'F') and hasattr(self, 'S') and hasattr(self, 'G'), \

@@ -287,9 +287,12 @@ BNMTF_API int bnmtf_metric_sums(bnmtf_handle h, const uint8_t* Mp, const double*
  * Gibbs run, the point estimate of ICM, E[.] of the variational models -- on a sparse list of held-out entries, on the device
  * (csrc/kernel_heldout.hip: fp64 products of the fp32 factors, fixed summation order, no pass over R).
  * M_test [I][J]: nonzero = held out (it may overlap the training mask, as predict() allows); NULL clears.  Any handle of
- * bnmtf_create; one created with world > 1 is refused with BNMTF_EINVAL, as is a mask without entries.  While a mask is set,
- * bnmf_gibbs_run, bnmtf_gibbs_run, bnmf_vb_run and bnmtf_vb_run record the six sums of every iteration, a model of the
- * one-launch kind runs the multi-launch path, and the *_run_many entry points refuse the handle. */
+ * bnmtf_create or bnmtf_np_create; one created with world > 1 or as a block of a wider factorisation is refused with BNMTF_EINVAL,
+ * as is a mask without entries.  While a mask is set, bnmf_gibbs_run, bnmtf_gibbs_run, bnmf_vb_run, bnmtf_vb_run, bnmf_np_run and
+ * bnmtf_np_run record the six sums of every iteration, and so do bnmf_vb_run_many, bnmtf_vb_run_many and bnmtf_np_run_many for
+ * each of their models that has one (the held-out kernels join the models' shared launches; models with and without a mask mix).
+ * A model of the one-launch kind runs the multi-launch path, and bnmf_gibbs_run_many / bnmtf_gibbs_run_many refuse the handle:
+ * their kernel has no per-iteration hook. */
 BNMTF_API int bnmtf_set_heldout(bnmtf_handle h, const double* M_test);
 /* the records of the last run call: sums_out [n_iter][6] = n, sum R, sum R^2, sum P, sum P^2, sum R P per iteration (R as the
  * device holds it, fp32).  BNMTF_ESTATE if that call ran fewer than n_iter iterations or no mask was set. */
