@@ -75,6 +75,10 @@ def run_many(models, iterations, update='draw', store_samples=True, expectation=
         raise TypeError("run_many takes models whose run() is bnmf_gibbs_optimised.run, bnmtf_gibbs_optimised.run, "
                         "bnmf_vb_optimised.run, bnmtf_vb_optimised.run, NMF.run or NMTF.run, the last two initialised (got %s)"
                         % sorted({type(m).__name__ for m in models if not takes(m)}))
+    for i, m in enumerate(models):
+        if getattr(m, "_layout", "dense") == 'observed':
+            raise _lib.BnmtfError("run_many: model %d has layout='observed' (batched launches and pools take models of the dense "
+                                  "layout: run it on its own)" % i)
     if orders is not None and len(orders) != len(models):
         raise ValueError("run_many: %d orders for %d models" % (len(orders), len(models)))
     if M_tests is not None:

@@ -13,14 +13,20 @@ lambdaU, lambdaV, U, V, tau, all_U, all_V, all_tau, all_times, all_performances)
 methods and assertion messages as the reference.  Build-only extras are
 keyword-only: seed (Philox key; default drawn from numpy.random so that
 numpy.random.seed() makes runs reproducible, as in the reference), device,
-verbose, rank/world/comm_id (row/column sharding over several GPUs).
+verbose, rank/world/comm_id (row/column sharding over several GPUs), layout.
+
+layout='observed' keeps the per-entry state on the OBSERVED entries instead of the missing
+ones (_observed.py): cost and device memory follow the number of
+observed entries, the layout for matrices that are mostly missing.  Same chain for the same
+seed (same conditionals, same Philox keying), ranks up to 256 on one handle, one GPU; no
+M_test=, expectation=, run_many, set_sweep_path / set_small_path / set_profiling.
 """
 import ctypes as C
 import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _observed
 from ._base import DeviceModel, broadcast_lambda, check_rank, check_R_M, metrics_from_sums
 from ._blocked import BLOCK, MAX_BLOCKS, ColumnBlocks
 
@@ -28,12 +34,17 @@ MAX_RANK_BLOCKED = BLOCK * MAX_BLOCKS      # 256: ranks above 64 run as column b
 
 
 class bnmf_gibbs_optimised(DeviceModel):
-    def __init__(self, R, M, K, priors, *, seed=None, device=0, verbose=True, rank=0, world=1, comm_id=None):
+    def __init__(self, R, M, K, priors, *, seed=None, device=0, verbose=True, rank=0, world=1, comm_id=None, layout='dense'):
+        _observed.check_layout(layout)
+        self._layout = layout
         self.R = np.array(R, dtype=float)
         self.M = np.array(M, dtype=float)
         self.K = K
         check_R_M(self.R, self.M)
-        check_rank("bnmf_gibbs_optimised", MAX_RANK_BLOCKED, K=self.K)
+        if layout == 'observed':
+            _observed.check_constructor(self, world)
+        else:
+            check_rank("bnmf_gibbs_optimised", MAX_RANK_BLOCKED, K=self.K)
         (self.I, self.J) = self.R.shape
         self.size_Omega = self.M.sum()
         self.alpha, self.beta = float(priors['alpha']), float(priors['beta'])
@@ -43,7 +54,7 @@ class bnmf_gibbs_optimised(DeviceModel):
         self._init_device(seed, device, rank, world, comm_id)
         # ranks above 64 (the reference has no limit, :54-78): column blocks of at most 64, one device model each (_blocked.py)
         self._blocks = None
-        if self.K > BLOCK:
+        if self.K > BLOCK and layout == 'dense':       # (the observed-entry layout ties no rank to a lane: one handle up to 256)
             assert world == 1, "ranks above %d run on one GPU (column blocks: DESIGN.md section 8)" % BLOCK
             self._blocks = ColumnBlocks(self, bnmf_gibbs_optimised)
 
@@ -58,6 +69,12 @@ class bnmf_gibbs_optimised(DeviceModel):
     def _handle(self):
         if getattr(self, "_blocks", None) is not None:       # shape-only entry points (omega_counts, ...): the first block's handle
             return self._blocks.handles()[0]
+        if self._layout == 'observed':
+            if self._h is None:
+                if self._seed is None:      # follow NumPy's global seeding like the reference's samplers do
+                    self._seed = int(np.random.randint(0, 2 ** 62))
+                self._h = _observed.create_handle(self)
+            return self._h
         return super(bnmf_gibbs_optimised, self)._handle()
 
     # Initialise and run the sampler (bnmf_gibbs_optimised.py:94-96)
@@ -92,11 +109,15 @@ class bnmf_gibbs_optimised(DeviceModel):
         if held is not None and held[0] is self._h and float(tau) == held[3] and np.array_equal(self.U, held[1]) and np.array_equal(self.V, held[2]):
             return
         self._device_state = None
+        if self._layout == 'observed':
+            _lib.check(_lib.lib().bnmf_obs_set_state(self._handle(), _lib.ptr(_lib.f64(self.U)), _lib.ptr(_lib.f64(self.V)), float(tau)))
+            return
         _lib.check(_lib.lib().bnmf_set_state(self._handle(), _lib.ptr(_lib.f64(self.U)), _lib.ptr(_lib.f64(self.V)), float(tau)))
 
     def _pull(self):
         U = np.zeros((self.I, self.K)); V = np.zeros((self.J, self.K)); tau = C.c_double()
-        _lib.check(_lib.lib().bnmf_get_state(self._handle(), _lib.ptr(U), _lib.ptr(V), C.byref(tau)))
+        get_state = _lib.lib().bnmf_obs_get_state if self._layout == 'observed' else _lib.lib().bnmf_get_state
+        _lib.check(get_state(self._handle(), _lib.ptr(U), _lib.ptr(V), C.byref(tau)))
         self.U, self.V, self.tau = U, V, tau.value
         self._device_state = (self._h, U.copy(), V.copy(), tau.value)
 
@@ -109,6 +130,9 @@ class bnmf_gibbs_optimised(DeviceModel):
         need: with store_samples=False no sample ever crosses to the host).  M_test (a 0/1 matrix shaped like R; it may overlap M): the held-out MSE / R^2 / Rp of the state
         every iteration ends with are computed on the device and kept in all_performances_test; without it no
         such attribute exists after the call."""
+        if self._layout == 'observed':
+            bufs = self._run_observed(iterations, _lib.UPDATE_MODE if update == 'mode' else _lib.UPDATE_DRAW, store_samples, expectation, M_test)
+            return self._run_finish(bufs, store_samples)
         Mt = self._check_heldout(M_test)
         if self._blocks is not None:
             return self._run_blocked(iterations, _lib.UPDATE_MODE if update == 'mode' else _lib.UPDATE_DRAW, store_samples, expectation)
@@ -119,6 +143,25 @@ class bnmf_gibbs_optimised(DeviceModel):
                                              _lib.ptr(U_out), _lib.ptr(V_out), _lib.ptr(taus), _lib.ptr(perf), _lib.ptr(times)))
         self._finish_heldout(it)
         return self._run_finish(bufs, store_samples)
+
+    def _run_observed(self, iterations, update, store_samples, expectation, M_test):
+        """run() with layout='observed': one device call (bnmf_obs_run) runs all iterations -- per iteration the two half sweeps on
+        the entry lists and the end-of-iteration kernel; samples, tau, metrics and times come back as from bnmf_gibbs_run."""
+        if M_test is not None:
+            _observed.refuse(self, "run(M_test=)", "held-out curves are kept by the dense layout only; use predict(M_test) after the run")
+        if expectation is not None:
+            _observed.refuse(self, "run(expectation=)", "the posterior sums on the device belong to the dense layout; approx_expectation averages the stored samples")
+        it = int(iterations)
+        self._push()
+        self._dev_expect = None
+        if update == _lib.UPDATE_ICM:
+            U_out = V_out = None
+        else:
+            U_out = _lib.sample_buffer((it, self.I, self.K)) if store_samples else None
+            V_out = _lib.sample_buffer((it, self.J, self.K)) if store_samples else None
+        bufs = (it, U_out, V_out, np.zeros(it), np.zeros((it, 3)), np.zeros(it))
+        _lib.check(_lib.lib().bnmf_obs_run(self._handle(), it, int(update), _lib.ptr(U_out), _lib.ptr(V_out), _lib.ptr(bufs[3]), _lib.ptr(bufs[4]), _lib.ptr(bufs[5])))
+        return bufs
 
     def _run_blocked(self, iterations, update, store_samples, expectation, minimum_TN=0.0, icm=False):
         """run() of a model wider than 64 columns: the blocks' half sweeps in turn (_blocked.py); tau by the update rule's own
@@ -180,6 +223,8 @@ class bnmf_gibbs_optimised(DeviceModel):
         return super(bnmf_gibbs_optimised, self)._device_expectation(burn_in, thinning)
 
     def _metric_sums(self, M_pred, A, S, B):
+        if self._layout == 'observed':          # the list-metric kernel: the host turns the mask into a list
+            return _observed.metric_sums(self, M_pred, self.U if A is None else A, self.V if B is None else B)
         if self._blocks is not None:
             if M_pred is not None:
                 Mp_ = np.asarray(M_pred)
@@ -193,8 +238,35 @@ class bnmf_gibbs_optimised(DeviceModel):
             return "column blocks %s: " % (self._blocks.ranges,) + " | ".join(ch.describe() for ch in self._blocks.children)
         return super(bnmf_gibbs_optimised, self).describe()
 
+    # the dense layout's switches and device facts: refused for the observed-entry layout before any device call
+    def set_sweep_path(self, fast=True):
+        if self._layout == 'observed':
+            _observed.refuse(self, "set_sweep_path", "it has one sweep kernel; BNMTF_OBS_LONG=1 forces its long form")
+        return super(bnmf_gibbs_optimised, self).set_sweep_path(fast)
+
+    def set_small_path(self, on='auto'):
+        if self._layout == 'observed':
+            _observed.refuse(self, "set_small_path", "the one-launch path belongs to the dense layout")
+        return super(bnmf_gibbs_optimised, self).set_small_path(on)
+
+    def set_profiling(self, enable=True, kernel=None, every=1):
+        if self._layout == 'observed':
+            _observed.refuse(self, "set_profiling", "the per-kernel event brackets belong to the dense layout")
+        return super(bnmf_gibbs_optimised, self).set_profiling(enable, kernel, every)
+
+    def is_small(self):
+        return False if self._layout == 'observed' else super(bnmf_gibbs_optimised, self).is_small()
+
+    def omega_counts(self):
+        if self._layout == 'observed':
+            Mb = self.M != 0
+            return int(Mb.sum()), Mb.sum(axis=1).astype(np.uint32), Mb.sum(axis=0).astype(np.uint32)
+        return super(bnmf_gibbs_optimised, self).omega_counts()
+
     def _run_prepare(self, iterations, store_samples, expectation):
         """State on the device, expectation switch, output arrays of one run() call (also used by bnmtf_amd.run_many)."""
+        if self._layout == 'observed':
+            _observed.refuse(self, "run_many", "batched launches take models of the dense layout")
         it = int(iterations)
         self._push()
         self._set_expectation(expectation, it)
@@ -226,7 +298,7 @@ class bnmf_gibbs_optimised(DeviceModel):
         return self.alpha + self.size_Omega / 2.0
 
     def beta_s(self):
-        if self._blocks is not None:           # :164-165 from the full-width masked SSE
+        if self._blocks is not None or self._layout == 'observed':           # :164-165 from the full-width masked SSE
             s = self._metric_sums(None, np.asarray(self.U, dtype=float), None, np.asarray(self.V, dtype=float))
             return self.beta + 0.5 * (s[2] - 2.0 * s[5] + s[4])
         self._push()
@@ -240,6 +312,9 @@ class bnmf_gibbs_optimised(DeviceModel):
             return self._blocks.cond(which, k)
         n = self.I if which == 0 else self.J
         numer = np.zeros(n); tauk = np.zeros(n)
+        if self._layout == 'observed':
+            _lib.check(_lib.lib().bnmf_obs_cond_params(self._handle(), which, int(k), _lib.ptr(numer), _lib.ptr(tauk)))
+            return numer, tauk
         _lib.check(_lib.lib().bnmf_cond_params(self._handle(), which, int(k), _lib.ptr(numer), _lib.ptr(tauk)))
         return numer, tauk
 

@@ -44,6 +44,7 @@ static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 extern "C" int bnmtf_shard_range(int64_t n, int rank, int world, int64_t* first, int64_t* count);
 namespace bnmtf {
 static void np_free(bnmtf_model* h);   // api_np.inc
+static void obs_free(bnmtf_model* h);  // api_obs.inc
 
 template <typename T>
 static int dalloc(T** p, size_t count, bool zero = true) {
@@ -56,6 +57,15 @@ template <typename T>
 static void dfree(T*& p) {
   if (p) (void)hipFree(p);
   p = nullptr;
+}
+
+// a handle of bnmtf_obs_create (the observed-entry layout, api_obs.inc) holds none of what the other entry points work on
+static int refuse_obs(const bnmtf_model* h, const char* fn) {
+  if (h && h->obs) {      // (fn null: reached through ensure_std, from any of the sampler and variational calls)
+    set_error("%s%sa handle of bnmtf_obs_create runs only the bnmf_obs_* calls (layout='observed')", fn ? fn : "", fn ? ": " : "");
+    return BNMTF_EINVAL;
+  }
+  return BNMTF_OK;
 }
 
 // A model search builds and destroys a model per candidate (fold x rank x restart), all of the same few sizes: the one device
@@ -1336,6 +1346,7 @@ int bnmtf_destroy(bnmtf_handle h) try {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->comm) comm_destroy(h->comm);
   np_free(h);
+  obs_free(h);
   heldout_free(h);
   small_free(h);            // (first: a small model's arena also holds Rfull, the posterior sums, Ad / Bd -- their pointers are cleared)
   free_dir(h->rows); free_dir(h->cols); free_dir(h->reff); free_dir(h->ceff);
@@ -1374,6 +1385,7 @@ int bnmtf_sync(bnmtf_handle h) try {
 } BNMTF_ABI_GUARD
 
 int bnmtf_omega_counts(bnmtf_handle h, uint64_t* total, uint32_t* row, uint32_t* col) try {
+  CHK(refuse_obs(h, "bnmtf_omega_counts"));
   if (total) *total = (uint64_t)h->n_obs;
   if (row) memcpy(row, h->rows.obs_count.data(), sizeof(uint32_t) * h->I);
   if (col) memcpy(col, h->cols.obs_count.data(), sizeof(uint32_t) * h->J);
@@ -1397,11 +1409,13 @@ int bnmtf_host_free(void* p) try {
 } BNMTF_ABI_GUARD
 
 int bnmtf_set_expectation(bnmtf_handle h, int burn_in, int thinning) try {
+  CHK(refuse_obs(h, "bnmtf_set_expectation"));
   if (burn_in >= 0 && thinning < 1) { set_error("thinning must be >= 1"); return BNMTF_EINVAL; }
   h->exp_burn = burn_in; h->exp_thin = thinning < 1 ? 1 : thinning;
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 int bnmtf_get_expectation(bnmtf_handle h, double* A, double* S, double* B, double* tau, uint64_t* count) try {
+  CHK(refuse_obs(h, "bnmtf_get_expectation"));
   if (!h->exp_rows || h->exp_count == 0) { set_error("no samples accumulated (bnmtf_set_expectation before run, burn_in < iterations)"); return BNMTF_ESTATE; }
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1422,6 +1436,7 @@ int bnmtf_get_expectation(bnmtf_handle h, double* A, double* S, double* B, doubl
 
 int bnmtf_set_iteration(bnmtf_handle h, uint64_t it) { h->iteration = it; return BNMTF_OK; }
 int bnmtf_set_tau(bnmtf_handle h, double tau) try {        // the noise precision alone (the factors on the device stay as they are)
+  CHK(refuse_obs(h, "bnmtf_set_tau"));
   if (!h->have_state) { set_error("bnmtf_set_tau before the state is set"); return BNMTF_ESTATE; }
   HIPCHK(hipSetDevice(h->device));
   return set_tau(h, tau);
@@ -1434,13 +1449,14 @@ int bnmtf_set_minimum_tn(bnmtf_handle h, double minimum_TN) try {
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 int bnmtf_set_profiling(bnmtf_handle h, int enable) try {
+  CHK(refuse_obs(h, "bnmtf_set_profiling"));
   // 0: off; 1: every kernel; 2 + k: kernel k only (so that a timed region carries two event records, not eight)
   h->profiling = enable == 0 ? 0u : (enable == 1 ? 0xFFFFFFFFu : 1u << (unsigned)((enable - 2) & 31));
   h->profile_stride = enable >= 2 ? (uint64_t)((enable - 2) >> 5) + 1 : 1;     // every n-th iteration only: an event record costs the queue a few microseconds
   for (int i = 0; i < BNMTF_KERNEL_COUNT; ++i) { h->kernel_ms[i] = 0; h->kernel_launches[i] = 0; }
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
-int bnmtf_set_sweep_path(bnmtf_handle h, int fast) { h->use_fast = fast != 0; h->ho_regions_current = false; return BNMTF_OK; }
+int bnmtf_set_sweep_path(bnmtf_handle h, int fast) { CHK(refuse_obs(h, "bnmtf_set_sweep_path")); h->use_fast = fast != 0; h->ho_regions_current = false; return BNMTF_OK; }
 int bnmtf_comm_info(bnmtf_handle h, int* kind, int* ranks) { return comm_info(h->comm, kind, ranks); }
 int bnmtf_has_experiments(void) try {
 #ifdef BNMTF_EXPERIMENTS
@@ -1450,12 +1466,14 @@ int bnmtf_has_experiments(void) try {
 #endif
 } BNMTF_ABI_GUARD
 int bnmtf_set_small_path(bnmtf_handle h, int mode) try {
+  CHK(refuse_obs(h, "bnmtf_set_small_path"));
   if (mode < 0 || mode > 2) { set_error("bnmtf_set_small_path: mode 0 (never), 1 (auto) or 2 (always)"); return BNMTF_EINVAL; }
   h->small_mode = mode;
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
-int bnmtf_is_small(bnmtf_handle h, int* out) { *out = small_wanted(h) ? 1 : 0; return BNMTF_OK; }
+int bnmtf_is_small(bnmtf_handle h, int* out) { CHK(refuse_obs(h, "bnmtf_is_small")); *out = small_wanted(h) ? 1 : 0; return BNMTF_OK; }
 int bnmtf_kernel_stats(bnmtf_handle h, int kernel, double* total_ms, uint64_t* launches) try {
+  CHK(refuse_obs(h, "bnmtf_kernel_stats"));
   if (kernel < 0 || kernel >= BNMTF_KERNEL_COUNT) { set_error("bad kernel id"); return BNMTF_EINVAL; }
   HIPCHK(hipStreamSynchronize(h->stream));
   drain_events(h);
@@ -1475,6 +1493,7 @@ int bnmtf_describe(bnmtf_handle h, char* buf, size_t buflen) try {
 
 // ------------------------------------------------------------------ BNMF Gibbs
 int bnmf_set_state(bnmtf_handle h, const double* U, const double* V, double tau) try {
+  CHK(refuse_obs(h, "bnmf_set_state"));
   if (h->L != 0) { set_error("bnmf_set_state on a BNMTF handle"); return BNMTF_ESTATE; }
   HIPCHK(hipSetDevice(h->device));
   h->std_cur = false; h->small_cur = false;
@@ -1491,6 +1510,7 @@ int bnmf_set_state(bnmtf_handle h, const double* U, const double* V, double tau)
 } BNMTF_ABI_GUARD
 
 int bnmf_get_state(bnmtf_handle h, double* U, double* V, double* tau) try {
+  CHK(refuse_obs(h, "bnmf_get_state"));
   if (!h->have_state) { set_error("no state set"); return BNMTF_ESTATE; }
   HIPCHK(hipSetDevice(h->device));
   if (h->small && h->small_cur) CHK(small_download_state(h, U, V));
@@ -1506,6 +1526,7 @@ int bnmf_get_state(bnmtf_handle h, double* U, double* V, double* tau) try {
 } BNMTF_ABI_GUARD
 
 int bnmf_cond_params(bnmtf_handle h, int which, int k, double* numer_out, double* tau_out) try {
+  CHK(refuse_obs(h, "bnmf_cond_params"));
   if (!h->have_state) { set_error("no state set"); return BNMTF_ESTATE; }
   if (h->world != 1) { set_error("cond_params is a single-GPU test hook"); return BNMTF_EINVAL; }
   Dir& d = which == 0 ? h->rows : h->cols;
@@ -1526,6 +1547,7 @@ int bnmf_cond_params(bnmtf_handle h, int which, int k, double* numer_out, double
 
 int bnmf_gibbs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* V_out,
                    double* tau_out, double* perf_out, double* times_out) try {
+  CHK(refuse_obs(h, "bnmf_gibbs_run"));
   if (h->L != 0) { set_error("bnmf_gibbs_run on a BNMTF handle"); return BNMTF_ESTATE; }
   if (!h->have_state) { set_error("bnmf_gibbs_run before bnmf_set_state"); return BNMTF_ESTATE; }
   if (n_iter < 0) { set_error("negative iteration count"); return BNMTF_EINVAL; }
@@ -1707,6 +1729,7 @@ int bnmf_gibbs_run_many(const bnmtf_handle* hs, int n_models, int n_iter, int up
 // other blocks are those of a rank-K_b model on the residual data R - sum_{b' != b} U_b' V_b'^T -- exactly the reference's
 // sequential column order when the blocks' half sweeps run in turn, rows first (:134-137), then columns (:139-142).
 int bnmf_set_column_block(bnmtf_handle h, int col0) try {
+  CHK(refuse_obs(h, "bnmf_set_column_block"));
   if (col0 < 0) { set_error("negative column offset"); return BNMTF_EINVAL; }
   if (h->L != 0 || h->comm) { set_error("column blocks: BNMF handles on one GPU"); return BNMTF_ESTATE; }
   h->col0 = (uint32_t)col0;
@@ -1716,6 +1739,7 @@ int bnmf_set_column_block(bnmtf_handle h, int col0) try {
 } BNMTF_ABI_GUARD
 
 int bnmf_set_residual_data(bnmtf_handle h, const bnmtf_handle* others, int n_others) try {
+  CHK(refuse_obs(h, "bnmf_set_residual_data"));
   if (n_others < 0 || n_others > kMaxOtherBlocks) { set_error("at most %d other column blocks", kMaxOtherBlocks); return BNMTF_EINVAL; }
   if (h->comm) { set_error("residual data: one GPU"); return BNMTF_ESTATE; }       // (the target may be a BNMTF handle -- an S block of a wider tri-factorisation; the others are two-factor products)
   HIPCHK(hipSetDevice(h->device));
@@ -1743,6 +1767,7 @@ int bnmf_set_residual_data(bnmtf_handle h, const bnmtf_handle* others, int n_oth
 // :139-142) with the handle's current tau and iteration counter, the relayout + Gram the other direction reads.  tau, the
 // metrics, the samples and the iteration counter are the caller's (a column-blocked model: bnmtf_amd/_blocked.py).
 int bnmf_half_sweep(bnmtf_handle h, int which, int update) try {
+  CHK(refuse_obs(h, "bnmf_half_sweep"));
   if (which < 0 || which > 1 || update < 0 || update > BNMTF_UPDATE_ICM) { set_error("bnmf_half_sweep: which in {0, 1}, a known update rule"); return BNMTF_EINVAL; }
   if (h->L != 0 || h->comm) { set_error("bnmf_half_sweep: BNMF handles on one GPU"); return BNMTF_ESTATE; }
   if (!h->have_state) { set_error("no state set"); return BNMTF_ESTATE; }
@@ -1770,11 +1795,13 @@ static int metric_sums_impl(bnmtf_handle h, const uint8_t* Mp, const double* A, 
 int bnmtf_metric_sums(bnmtf_handle h, const uint8_t* Mp, const double* A, const double* S, const double* B,
                       double sums_out[6]) { return metric_sums_impl(h, Mp, A, S, B, sums_out, 0); }
 int bnmtf_metric_sums_wide(bnmtf_handle h, const uint8_t* Mp, const double* A, const double* B, int Kc, double sums_out[6]) try {
+  CHK(refuse_obs(h, "bnmtf_metric_sums_wide"));
   if (!A || !B || Kc <= 0) { set_error("bnmtf_metric_sums_wide: A [I][Kc], B [J][Kc] and Kc > 0 required"); return BNMTF_EINVAL; }
   if (h->L != 0) { set_error("bnmtf_metric_sums_wide on a BNMTF handle"); return BNMTF_ESTATE; }
   return metric_sums_impl(h, Mp, A, nullptr, B, sums_out, Kc);
 } BNMTF_ABI_GUARD
 static int metric_sums_impl(bnmtf_handle h, const uint8_t* Mp, const double* A, const double* S, const double* B, double sums_out[6], int Kc_given) {
+  CHK(refuse_obs(h, "bnmtf_metric_sums"));
   HIPCHK(hipSetDevice(h->device));
   const int I = h->I, J = h->J;
   std::vector<double> a_own, b_own, as;
@@ -1844,6 +1871,7 @@ static int metric_sums_impl(bnmtf_handle h, const uint8_t* Mp, const double* A, 
 }
 
 int bnmtf_beta_s(bnmtf_handle h, double* out) try {
+  CHK(refuse_obs(h, "bnmtf_beta_s"));
   double s[6];
   CHK(bnmtf_metric_sums(h, nullptr, nullptr, nullptr, nullptr, s));
   *out = h->beta + 0.5 * (s[2] - 2.0 * s[5] + s[4]);
@@ -1894,4 +1922,5 @@ int bnmtf_gamma_sample(double alpha, double beta, uint64_t seed, uint64_t it, in
 #include "api_models.inc"
 #include "api_trivb.inc"
 #include "api_np.inc"
+#include "api_obs.inc"
 #include "api_many.inc"

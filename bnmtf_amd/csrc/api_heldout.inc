@@ -53,6 +53,7 @@ extern "C" {
 
 int bnmtf_set_heldout(bnmtf_handle h, const double* M_test) try {
   if (!h) { set_error("bnmtf_set_heldout: null handle"); return BNMTF_EINVAL; }
+  CHK(refuse_obs(h, "bnmtf_set_heldout"));
   if (h->world > 1) { set_error("bnmtf_set_heldout: a sharded model (world = %d) keeps no held-out record: one GPU only", h->world); return BNMTF_EINVAL; }
   if (h->block_mode) { set_error("bnmtf_set_heldout: a block of a wider factorisation keeps no held-out record"); return BNMTF_EINVAL; }
   HIPCHK(hipSetDevice(h->device));

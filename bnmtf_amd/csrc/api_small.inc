@@ -231,6 +231,7 @@ static int small_download_state(bnmtf_model* h, double* U, double* V, double* S 
 // it the current state if the small path holds it.
 static int ensure_std(bnmtf_model* h) {
   if (h->np) { set_error("a handle of bnmtf_np_create runs only the bnmf_np_* / bnmtf_np_* calls"); return BNMTF_EINVAL; }
+  CHK(refuse_obs(h, nullptr));
   if (!h->std_built) {
     HIPCHK(hipSetDevice(h->device));
     CHK(build_standard(h, h->L > 0 ? h->lam_S.data() : nullptr, nullptr));

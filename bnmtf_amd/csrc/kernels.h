@@ -556,4 +556,49 @@ void launch_heldout_np(const HeldoutNpArgs& a, hipStream_t st);
 // rval[e] = R[i][col[e]] for the entries e of every row i (R [I][J])
 void launch_heldout_values(const float* R, int I, int J, const uint32_t* rowptr, const uint32_t* col, float* rval, hipStream_t st);
 
+// ---------------------------------------------------------------------------
+// Observed-entry layout of the two-factor Gibbs / ICM models (kernel_obs.hip): the residual on the observed
+// entries, one wave per unit, no contraction and no Gram matrix
+// ---------------------------------------------------------------------------
+constexpr int kObsWaves = 4;           // units (waves) per block
+constexpr int kObsMaxRank = 256;       // K: nothing ties a rank to a lane; the unit's row and prior rates take 2 KiB of LDS per wave
+constexpr int kObsMaxSlots = 8;        // register form: entries per lane (instantiations 1, 2, 4, 8); a unit of more than 512 entries runs the long form
+struct ObsSweepArgs {
+  const uint32_t* ptr;               // [n + 1] the entries of unit u are [ptr[u], ptr[u + 1])
+  const uint32_t* idx;               // their inner indices, ascending within a unit
+  const float* val;                  // their values of R
+  int n, m, K, KP;                   // units, inner extent, rank, row stride of the row-major factors (K rounded up to 4; padding columns zero)
+  int mode;                          // kSweepDraw / kSweepMode
+  int cond_k;                        // >= 0: evaluate (numer, tau) of this column only and change nothing
+  int force_long;                    // every unit down the long form (BNMTF_OBS_LONG=1)
+  float min_x;                       // mode updates: lower clamp of the new value (ICM minimum_TN)
+  const float* lambda;               // [n][KP]
+  float* X; float* XT; int ldT;      // this direction's factor [n][KP] and transposed [K][ldT]
+  const float* Xo; const float* XoT; int ldT_o;   // the other factor [m][KP] and [K][ldT_o], ldT_o > m: XoT[k][m] is zero
+  float* escratch;                   // [entries] the long form's residual, at the entry's list position
+  const float* tau;                  // device scalar
+  uint32_t key0, key1, it, stream;
+  double* part;                      // null, or [obs_sweep_blocks(n)][4]: SSE, sum P, sum P^2, sum R P of the final residual
+  double* numer_out; double* tau_out;   // cond_k >= 0: [n]
+  float* snap;                       // null, or the sample slot [n][K]
+};
+struct ObsFinishArgs {
+  const double* part; int nb;        // the V half sweep's partial sums
+  double n_obs, sumR, sumR2, alpha, beta;
+  int update;                        // 0 draw (tau = gunit / beta_s), 1 mode (alpha_s / beta_s), 2 ICM ((alpha_s - 1) / beta_s)
+  const double* gunit;               // update 0: the iteration's Gamma(alpha_s, 1) variate (stage_gamma_variates)
+  double* tau_d; float* tau_f;
+  double* rec;                       // [5]: tau, MSE, R^2, Rp, SSE
+};
+struct ObsMetricArgs {
+  const uint32_t* row; const uint32_t* col; const float* val; size_t n;   // the entries, any order
+  const double* A; const double* B; int K;                                // [I][K], [J][K]
+  double* part;                      // [obs_metric_blocks(n)][8]
+};
+inline int obs_sweep_blocks(int n) { return (n + kObsWaves - 1) / kObsWaves; }
+inline int obs_metric_blocks(size_t n) { const size_t b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b)); }
+void launch_obs_sweep(const ObsSweepArgs& a, hipStream_t st);
+void launch_obs_finish(const ObsFinishArgs& a, hipStream_t st);
+void launch_obs_metric(const ObsMetricArgs& a, double* out8, hipStream_t st);   // out8: n, sum R, sum R^2, sum P, sum P^2, sum R P, 0, 0
+
 }  // namespace bnmtf

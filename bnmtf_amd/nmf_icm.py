@@ -14,7 +14,7 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _observed
 from ._base import metrics_from_sums
 from .bnmf_gibbs import bnmf_gibbs_optimised
 
@@ -39,6 +39,12 @@ class nmf_icm(bnmf_gibbs_optimised):
     def run(self, iterations, minimum_TN=0., *, M_test=None):
         """:114-150.  One device call runs all iterations; returns None like the reference.  M_test: the held-out metrics of the
         point estimate every iteration ends with, in all_performances_test (see bnmf_gibbs_optimised.run)."""
+        if self._layout == 'observed':          # (DESIGN.md section 2.7: the ICM rules on the observed-entry kernel)
+            if M_test is not None:
+                _observed.refuse(self, "run(M_test=)", "held-out curves are kept by the dense layout only; use predict(M_test) after the run")
+            _lib.check(_lib.lib().bnmtf_set_minimum_tn(self._handle(), float(minimum_TN)))
+            it, _, _, taus, perf, times = self._run_observed(iterations, _lib.UPDATE_ICM, False, None, None)
+            return self._finish_icm(it, taus, perf, times)
         Mt = self._check_heldout(M_test)
         it = int(iterations)
         if self._blocks is not None:            # ranks above 64: column blocks (_blocked.py), ICM rules
@@ -51,6 +57,10 @@ class nmf_icm(bnmf_gibbs_optimised):
         _lib.check(L.bnmtf_set_minimum_tn(self._handle(), float(minimum_TN)))
         _lib.check(L.bnmf_gibbs_run(self._handle(), it, _lib.UPDATE_ICM, None, None, _lib.ptr(taus), _lib.ptr(perf), _lib.ptr(times)))
         self._finish_heldout(it)
+        return self._finish_icm(it, taus, perf, times)
+
+    def _finish_icm(self, it, taus, perf, times):
+        """Behind the device call of run(), either layout: the point estimate and the per-iteration records."""
         self._pull()
         self.all_tau = taus
         self.all_times = list(times)

@@ -393,6 +393,40 @@ BNMTF_API int bnmtf_np_run_many(bnmtf_handle* hs, int n_models, int n_iter, doub
  * sum P, sum P^2, sum R P, the I-divergence sum R log(R / P) - R + P (nmf_np.py:146-148), sum (R - P)^2 */
 BNMTF_API int bnmtf_np_metrics(bnmtf_handle h, const uint8_t* Mp, double* out);
 
+/* ---- observed-entry layout of the two-factor Gibbs / ICM models (layout='observed') ---------
+ * A handle of its own kind for matrices that are mostly missing: the device holds the OBSERVED entries as a row list and a column
+ * list, both factors in fp32 and the residual R_ij - U_i.V_j on the observed entries; cost and memory are proportional to the
+ * number of observed entries and nothing of size I x J exists.  The entries come as three lists of length n, in any order, no
+ * entry twice, every row and every column of R at least once: rows[e] in [0, I), cols[e] in [0, J), values[e] = R[rows[e]][cols[e]].
+ * 1 <= K <= BNMTF_OBS_MAX_RANK, one GPU.  Same conditionals, same Philox keying and candidate sequence as bnmf_gibbs_run.  Such a
+ * handle takes the calls below, bnmtf_set_minimum_tn, bnmtf_set_iteration / bnmtf_get_iteration, bnmtf_sync, bnmtf_describe and
+ * bnmtf_destroy; every other call refuses it.  BNMTF_OBS_LONG=1 in the environment at creation sends every unit down the kernel's
+ * long form (a test switch: the results are the same bits). */
+#define BNMTF_OBS_MAX_RANK 256
+BNMTF_API int bnmtf_obs_create(int I, int J, int K, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values,
+                     const double* lambda_rows, const double* lambda_cols, double alpha, double beta, uint64_t seed, int device,
+                     bnmtf_handle* out);
+/* A TEST HOOK, not an interface to build on (it may change with the handle's layout): the host half of bnmtf_obs_create on its
+ * own, so that the builder the device data come from can be tested without a GPU (tests/test_obs_cpu.py).  Pure function: the
+ * same checks -- an entry outside the matrix, an entry twice, a row or column without entries are refused -- and the two lists
+ * the device would hold: row_ptr [I + 1], row_col [n] (columns ascending within a row), row_val [n]; col_ptr [J + 1], col_row [n]
+ * (rows ascending within a column), col_val [n].  Any output may be null. */
+BNMTF_API int bnmtf_obs_build_lists(int I, int J, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values,
+                          uint32_t* row_ptr, uint32_t* row_col, float* row_val, uint32_t* col_ptr, uint32_t* col_row, float* col_val);
+/* U [I][K], V [J][K], tau */
+BNMTF_API int bnmf_obs_set_state(bnmtf_handle h, const double* U, const double* V, double tau);
+BNMTF_API int bnmf_obs_get_state(bnmtf_handle h, double* U, double* V, double* tau);
+/* run(n_iter) with the arguments of bnmf_gibbs_run: update = BNMTF_UPDATE_*; U_out [n][I][K], V_out [n][J][K] (fp32 samples),
+ * tau_out [n], perf_out [n][3] (MSE, R^2, Rp on the observed entries), times_out [n]; any output may be null */
+BNMTF_API int bnmf_obs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* V_out, double* tau_out, double* perf_out,
+                 double* times_out);
+/* as bnmf_cond_params: numerator and precision of column k's conditional for every row (which = 0) or column (which = 1) */
+BNMTF_API int bnmf_obs_cond_params(bnmtf_handle h, int which, int k, double* numer_out, double* tau_out);
+/* the six sums of metrics_from_sums -- n, sum R, sum R^2, sum P, sum P^2, sum R P with P = A_i . B_j -- over a list of entries
+ * (any order; they need not be observed ones), A [I][K] and B [J][K] in fp64; fp64 throughout, fixed summation order */
+BNMTF_API int bnmf_obs_metric_sums(bnmtf_handle h, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values,
+                         const double* A, const double* B, double sums_out[6]);
+
 #ifdef __cplusplus
 }
 #endif
