@@ -115,6 +115,11 @@ _SIGS = {
     "bnmf_obs_run": ([_P, C.c_int, C.c_int, _P, _P, _P, _P, _P], C.c_int),
     "bnmf_obs_cond_params": ([_P, C.c_int, C.c_int, _P, _P], C.c_int),
     "bnmf_obs_metric_sums": ([_P, C.c_uint64, _P, _P, _P, _P, _P, _P], C.c_int),
+    "bnmf_vbo_set_state": ([_P] * 9 + [C.c_double], C.c_int),
+    "bnmf_vbo_get_state": ([_P] * 9, C.c_int),
+    "bnmf_vbo_run": ([_P, C.c_int, _P, _P, _P, _P], C.c_int),
+    "bnmf_vbo_update": ([_P, C.c_int, C.c_int, C.c_int], C.c_int),
+    "bnmf_vbo_exp_square_diff": ([_P, C.POINTER(C.c_double)], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 

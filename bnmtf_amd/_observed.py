@@ -1,6 +1,7 @@
-"""layout='observed' of bnmf_gibbs_optimised / nmf_icm: the host side of the observed-entry layout.
+"""layout='observed' of bnmf_gibbs_optimised / nmf_icm, and bnmf_vb_observed: the host side of the observed-entry layout
+(DESIGN.md section 2.7).
 
-The device keeps the residual R_ij - U_i.V_j on the OBSERVED entries (csrc/kernel_obs.hip), so cost and device memory follow the
+The device keeps the residual R_ij - U_i.V_j on the OBSERVED entries (csrc/kernel_obs.hip, kernel_obs_vb.hip), so cost and device memory follow the
 number of observed entries: the layout for matrices that are mostly missing.  R and M stay dense NumPy arrays at the Python
 boundary; this module turns the mask into the entry lists the library takes, owns the bnmtf_obs_create handle of a model and
 states what the layout does not run."""

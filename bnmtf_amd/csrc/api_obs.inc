@@ -4,6 +4,8 @@
 // proportional to the number of observed entries.  None of the samplers' layouts, no dense operand, no copy of R or M.  The
 // iteration is two launches of obs_sweep_kernel and obs_finish_kernel (kernel_obs.hip) on the handle's stream; the samples leave
 // through the SampleSink like bnmf_gibbs_run's, written into their slots by the sweeps themselves.  One GPU.
+// The variational model on the same handle (bnmf_vbo_*, at the end of this file): its q parameters, the transposed S2 and the
+// half sweeps' partial sums are allocated by the first bnmf_vbo_set_state, so a Gibbs / ICM handle holds none of them.
 
 namespace bnmtf {
 
@@ -13,6 +15,10 @@ struct ObsList {                 // one direction: units, their entries' inner i
   float* lambda = nullptr;                                         // [n][KP]
   double* numer = nullptr; double* taup = nullptr;                 // cond-params scratch [n]
   uint32_t longest = 0; size_t long_units = 0;                     // most entries of a unit; units beyond the register form
+  // variational state (bnmf_vbo_set_state): q's mu, tau, var [n][KP] beside the expectation in X / XT; S2 = var + X^2 transposed
+  // [K][ldT] with XT's zero word behind every column; the half sweep's partial sums [obs_sweep_blocks(n)][6]
+  float* mu = nullptr; float* tauq = nullptr; float* var = nullptr; float* S2T = nullptr;
+  double* vstat = nullptr;
 };
 struct ObsState {
   ObsList rows, cols;
@@ -22,6 +28,8 @@ struct ObsState {
   double* scal = nullptr;          // tau_d, tau_f and out8 of the metric sums (one allocation)
   double* out8 = nullptr;
   bool force_long = false;
+  bool vb_alloc = false, vb_state = false;   // the variational buffers exist; they hold the state of the last bnmf_vbo_set_state / run
+  double* esd_part = nullptr;      // [obs_vb_esd_blocks(I)] exp_square_diff's partial sums
 };
 
 static void obs_free(bnmtf_model* h) {
@@ -29,8 +37,9 @@ static void obs_free(bnmtf_model* h) {
   if (!s) return;
   for (ObsList* d : {&s->rows, &s->cols}) {
     dfree(d->ptr); dfree(d->idx); dfree(d->val); dfree(d->X); dfree(d->XT); dfree(d->lambda); dfree(d->numer); dfree(d->taup);
+    dfree(d->mu); dfree(d->tauq); dfree(d->var); dfree(d->S2T); dfree(d->vstat);
   }
-  dfree(s->escratch); dfree(s->part); dfree(s->scal);
+  dfree(s->escratch); dfree(s->part); dfree(s->scal); dfree(s->esd_part);
   h->tau_d = nullptr; h->tau_f = nullptr;
   delete s;
   h->obs = nullptr;
@@ -229,6 +238,7 @@ int bnmf_obs_set_state(bnmtf_handle h, const double* U, const double* V, double 
   CHK(obs_put(h, h->obs->cols, V));
   CHK(set_tau(h, tau));
   h->have_state = true;
+  h->obs->vb_state = false;          // (the expectations were replaced: a variational state ends here)
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
@@ -336,6 +346,165 @@ int bnmf_obs_metric_sums(bnmtf_handle h, uint64_t n, const int32_t* rows, const 
   double out8[8];
   HIPCHK(hipMemcpy(out8, h->obs->out8, sizeof(out8), hipMemcpyDeviceToHost));
   for (int m = 0; m < 6; ++m) sums_out[m] = out8[m];
+  return BNMTF_OK;
+} BNMTF_ABI_GUARD
+
+}  // extern "C"
+
+// ---- the variational two-factor model on the handle's lists (kernel_obs_vb.hip; DESIGN.md section 2.7) -----------------------
+namespace bnmtf {
+
+static int vbo_check(bnmtf_model* h, bool need_state) {
+  if (!h || !h->obs) { set_error("not a handle of bnmtf_obs_create"); return BNMTF_EINVAL; }
+  if (need_state && !(h->obs->vb_state && h->have_state)) { set_error("bnmf_vbo_set_state has not been called"); return BNMTF_ESTATE; }
+  HIPCHK(hipSetDevice(h->device));
+  return BNMTF_OK;
+}
+
+static int vbo_alloc(bnmtf_model* h) {
+  ObsState* s = h->obs;
+  if (s->vb_alloc) return BNMTF_OK;
+  for (ObsList* d : {&s->rows, &s->cols}) {
+    if (!d->mu) CHK(dalloc(&d->mu, (size_t)d->n * s->KP));
+    if (!d->tauq) CHK(dalloc(&d->tauq, (size_t)d->n * s->KP));
+    if (!d->var) CHK(dalloc(&d->var, (size_t)d->n * s->KP));
+    if (!d->S2T) CHK(dalloc(&d->S2T, (size_t)h->K * d->ldT));
+    if (!d->vstat) CHK(dalloc(&d->vstat, (size_t)obs_sweep_blocks(d->n) * 6));
+  }
+  if (!s->esd_part) CHK(dalloc(&s->esd_part, (size_t)obs_vb_esd_blocks(h->I)));
+  s->vb_alloc = true;
+  return BNMTF_OK;
+}
+
+// fp64 host [n][K] x 4 -> the direction's fp32 q: mu, tau, var [n][KP]; the expectation in X / XT; S2 = var + exp^2 in S2T
+static int vbo_put(bnmtf_model* h, ObsList& d, const double* mu, const double* tau, const double* ex, const double* var) {
+  const int K = h->K, KP = h->obs->KP;
+  const size_t nk = (size_t)d.n * KP;
+  std::vector<float> m(nk, 0.f), t(nk, 0.f), v(nk, 0.f), s2((size_t)K * d.ldT, 0.f);
+  for (int u = 0; u < d.n; ++u)
+    for (int k = 0; k < K; ++k) {
+      const size_t src = (size_t)u * K + k, at = (size_t)u * KP + k;
+      m[at] = (float)mu[src]; t[at] = (float)tau[src]; v[at] = (float)var[src];
+      const float e = (float)ex[src];
+      s2[(size_t)k * d.ldT + u] = fmaf(e, e, v[at]);              // (as the sweep forms it)
+    }
+  CHK(obs_put(h, d, ex));
+  HIPCHK(hipMemcpyAsync(d.mu, m.data(), nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(d.tauq, t.data(), nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(d.var, v.data(), nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(d.S2T, s2.data(), s2.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return BNMTF_OK;
+}
+
+static ObsVbSweepArgs vbo_sweep_args(bnmtf_model* h, bool rows) {
+  ObsState* s = h->obs;
+  ObsList& d = rows ? s->rows : s->cols;
+  ObsList& o = rows ? s->cols : s->rows;
+  ObsVbSweepArgs a; memset(&a, 0, sizeof(a));
+  a.ptr = d.ptr; a.idx = d.idx; a.val = d.val;
+  a.n = d.n; a.m = o.n; a.K = h->K; a.KP = s->KP;
+  a.only_k = -1; a.moments = 1; a.force_long = s->force_long ? 1 : 0;
+  a.lambda = d.lambda;
+  a.X = d.X; a.XT = d.XT; a.S2T = d.S2T; a.ldT = d.ldT;
+  a.mu = d.mu; a.tauq = d.tauq; a.var = d.var;
+  a.Xo = o.X; a.XoT = o.XT; a.S2oT = o.S2T; a.ldT_o = o.ldT;
+  a.escratch = s->escratch;
+  a.tau = h->tau_f;
+  return a;
+}
+
+}  // namespace bnmtf
+
+extern "C" {
+
+int bnmf_vbo_set_state(bnmtf_handle h, const double* muU, const double* tauU, const double* expU, const double* varU,
+                       const double* muV, const double* tauV, const double* expV, const double* varV, double exptau) try {
+  CHK(vbo_check(h, false));
+  if (!muU || !tauU || !expU || !varU || !muV || !tauV || !expV || !varV) { set_error("bnmf_vbo_set_state: null argument"); return BNMTF_EINVAL; }
+  CHK(vbo_alloc(h));
+  h->obs->vb_state = false;
+  CHK(vbo_put(h, h->obs->rows, muU, tauU, expU, varU));
+  CHK(vbo_put(h, h->obs->cols, muV, tauV, expV, varV));
+  CHK(set_tau(h, exptau));
+  h->have_state = true;
+  h->obs->vb_state = true;
+  return BNMTF_OK;
+} BNMTF_ABI_GUARD
+
+int bnmf_vbo_get_state(bnmtf_handle h, double* muU, double* tauU, double* expU, double* varU,
+                       double* muV, double* tauV, double* expV, double* varV) try {
+  CHK(vbo_check(h, true));
+  ObsState* s = h->obs;
+  ObsList& r = s->rows; ObsList& c = s->cols;
+  if (muU) CHK(download_matrix(h, r.mu, h->I, h->K, s->KP, muU));
+  if (tauU) CHK(download_matrix(h, r.tauq, h->I, h->K, s->KP, tauU));
+  if (expU) CHK(download_matrix(h, r.X, h->I, h->K, s->KP, expU));
+  if (varU) CHK(download_matrix(h, r.var, h->I, h->K, s->KP, varU));
+  if (muV) CHK(download_matrix(h, c.mu, h->J, h->K, s->KP, muV));
+  if (tauV) CHK(download_matrix(h, c.tauq, h->J, h->K, s->KP, tauV));
+  if (expV) CHK(download_matrix(h, c.X, h->J, h->K, s->KP, expV));
+  if (varV) CHK(download_matrix(h, c.var, h->J, h->K, s->KP, varV));
+  return BNMTF_OK;
+} BNMTF_ABI_GUARD
+
+int bnmf_vbo_run(bnmtf_handle h, int n_iter, double* exptau_out, double* perf_out, double* elbo_terms_out, double* times_out) try {
+  CHK(vbo_check(h, true));
+  if (n_iter < 0) { set_error("negative iteration count"); return BNMTF_EINVAL; }
+  if (n_iter == 0) return BNMTF_OK;
+  ObsState* s = h->obs;
+  CHK(vb_reserve_rec(h, n_iter));
+  EventList ev;
+  CHK(ev.create(times_out ? n_iter + 1 : 0));
+  if (times_out) HIPCHK(hipEventRecord(ev[0], h->stream));
+  for (int it = 0; it < n_iter; ++it) {
+    ObsVbSweepArgs a = vbo_sweep_args(h, true);
+    a.stat = s->rows.vstat;
+    launch_obs_vb_sweep(a, h->stream);
+    a = vbo_sweep_args(h, false);
+    a.stat = s->cols.vstat; a.part = s->part;
+    launch_obs_vb_sweep(a, h->stream);
+    ObsVbFinishArgs f; memset(&f, 0, sizeof(f));
+    f.stat_r = s->rows.vstat; f.nb_r = obs_sweep_blocks(h->I);
+    f.stat_c = s->cols.vstat; f.part = s->part; f.nb_c = obs_sweep_blocks(h->J);
+    f.n_obs = h->n_obs; f.sumR = h->sumR; f.sumR2 = h->sumR2; f.alpha = h->alpha; f.beta = h->beta;
+    f.tau_d = h->tau_d; f.tau_f = h->tau_f; f.rec = h->vb_rec + (size_t)it * 16;
+    launch_obs_vb_finish(f, h->stream);
+    if (times_out) HIPCHK(hipEventRecord(ev[it + 1], h->stream));
+    h->iteration++;
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipGetLastError());
+  std::vector<double> rec((size_t)n_iter * 16);
+  HIPCHK(hipMemcpy(rec.data(), h->vb_rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
+  unpack_vb_rec(rec.data(), n_iter, exptau_out, perf_out, elbo_terms_out);
+  ev.seconds(n_iter, times_out);
+  return BNMTF_OK;
+} BNMTF_ABI_GUARD
+
+int bnmf_vbo_update(bnmtf_handle h, int which, int k, int moments) try {
+  CHK(vbo_check(h, true));
+  if (which != 0 && which != 1) { set_error("bnmf_vbo_update: which is 0 (rows) or 1 (columns)"); return BNMTF_EINVAL; }
+  if (k < 0 || k >= h->K) { set_error("column %d out of range", k); return BNMTF_EINVAL; }
+  ObsVbSweepArgs a = vbo_sweep_args(h, which == 0);
+  a.only_k = k; a.moments = moments ? 1 : 0;
+  launch_obs_vb_sweep(a, h->stream);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipGetLastError());
+  return BNMTF_OK;
+} BNMTF_ABI_GUARD
+
+int bnmf_vbo_exp_square_diff(bnmtf_handle h, double* out) try {
+  CHK(vbo_check(h, true));
+  if (!out) { set_error("bnmf_vbo_exp_square_diff: null argument"); return BNMTF_EINVAL; }
+  ObsState* s = h->obs;
+  ObsVbEsdArgs a; memset(&a, 0, sizeof(a));
+  a.ptr = s->rows.ptr; a.idx = s->rows.idx; a.val = s->rows.val; a.n = h->I; a.K = h->K; a.KP = s->KP;
+  a.X = s->rows.X; a.var = s->rows.var; a.Xo = s->cols.X; a.varo = s->cols.var; a.part = s->esd_part;
+  launch_obs_vb_esd(a, s->out8, h->stream);
+  HIPCHK(hipMemcpyAsync(out, s->out8, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipGetLastError());
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 

@@ -1,0 +1,276 @@
+// Observed-entry layout of the variational two-factor model ("VB on the entry lists"): kernel_obs.hip's
+// form A with the variational column update (bnmf_vb_optimised.py:189-211 restated on the OBSERVED entries of a unit).  For
+// column k of unit i, with E / S2 = var + E^2 of the other factor:
+//   sa = sum_{j in Omega_i} S2_jk,   sb = sum_{j in Omega_i} E_jk^2,   se = sum_{j in Omega_i} e_ij E_jk
+//   tau_ik = exptau sa,   mu_ik = (-lambda_ik + exptau (se + x_ik sb)) / tau_ik
+//   (x', var') = the truncated normal's moments (tn_moments_f32);   e_ij += (x_ik - x') E_jk
+// columns in order k = 0 .. K - 1; the V half sweep is the same on the column lists.
+//
+// obs_vb_sweep_kernel: one 64-lane wave per unit, kObsWaves units per block, lane l the unit's entries l, l + 64, ... in list
+// order; the register form with S = 1, 2, 4, 8 slots per lane and the long form through escratch, as obs_sweep_kernel has them
+// (a slot without an entry gathers the zero word behind the columns of both transposed operands).  Every per-lane sum runs in
+// entry order, every wave sum is the butterfly, fmaf is explicit and contraction is off: a unit's result does not depend on
+// the form.  The wave-uniform results of a column -- mu, tau, var, sa, sb; the expectation replaces x in the unit's row -- are
+// parked in LDS (every lane stores the same value and reads back its own store); behind the column loop lane k mod 64 forms the
+// fp64 pieces of column k: the four sums elbo() needs of q(x) (quad, log erfc, log tau, lambda E: kernel_sweep.hip's pieces) and,
+// in the V half sweep, q2 = (var + E^2) sa and q3 = E^2 sb, whose difference summed over all (unit, column) is the variance
+// part of exp_square_diff over the observed entries.  A lane's columns in order, the butterfly, the block's waves in wave
+// order; obs_vb_finish_kernel folds the blocks' partials in obs_fold's order.  No floating-point atomics anywhere.
+//
+// obs_vb_esd_kernel: exp_square_diff of the state the device holds, fp64 over the row list (a block's rows b, b + grid, ...; a
+// thread's entries in list order; a tree; the fold).
+#include "obs_common.h"
+#include "device_rng.h"
+
+namespace bnmtf {
+
+namespace {
+
+constexpr int kVbParked = 5;           // mu, tau, var, sa, sb of every column, beside the unit's row and its prior rates
+constexpr int kVbSums = 10;            // quad, log erfc, log tau, lambda E, q2, q3; SSE, sum P, sum P^2, sum R P
+
+// One unit.  S > 0: the register form with S slots per lane; S == 0: the long form.  xs / ls: the unit's expectations and prior
+// rates in LDS, pk: the parked column results.  sums (part != null): the lane's share of SSE, sum P, sum P^2, sum R P in sums[6 .. 9].
+template <int S>
+__device__ __forceinline__ void obs_vb_unit(const ObsVbSweepArgs& a, int u, int lane, float* xs, const float* ls, float* pk, double* sums) {
+#pragma clang fp contract(off)
+  constexpr int SS = S > 0 ? S : 1;
+  const uint32_t beg = a.ptr[u], cnt = a.ptr[u + 1] - beg;
+  const uint32_t* idx = a.idx + beg;
+  const float* val = a.val + beg;
+  float* es = a.escratch + beg;
+  const int K = a.K, KP = a.KP;
+  float* mus = pk; float* tps = pk + kObsMaxRank; float* vrs = pk + 2 * kObsMaxRank; float* sas = pk + 3 * kObsMaxRank; float* sbs = pk + 4 * kObsMaxRank;
+  float e[SS], v[SS];
+  uint32_t jj[SS];
+
+  // ---- phase 1: the residual of every entry
+  if (S > 0) {
+#pragma unroll
+    for (int s = 0; s < SS; ++s) {
+      const uint32_t t = (uint32_t)(s * 64 + lane);
+      e[s] = 0.f; v[s] = 0.f; jj[s] = (uint32_t)a.m;                 // (a slot without an entry: the zero word behind the other factor's columns)
+      if (t < cnt) { jj[s] = idx[t]; e[s] = obs_residual(xs, a.Xo, KP, jj[s], val[t]); }
+    }
+  } else {
+    for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) es[t] = obs_residual(xs, a.Xo, KP, idx[t], val[t]);
+  }
+
+  // ---- phase 2: the columns
+  const float exptau = *a.tau;
+  const int only = a.only_k;
+  const int kbeg = only >= 0 ? only : 0, kend = only >= 0 ? only + 1 : K;
+  for (int k = kbeg; k < kend; ++k) {
+    const float* vcol = a.XoT + (size_t)k * a.ldT_o;
+    const float* wcol = a.S2oT + (size_t)k * a.ldT_o;
+    float se = 0.f, sb = 0.f, sa = 0.f;
+    if (S > 0) {
+#pragma unroll
+      for (int s = 0; s < SS; ++s) { v[s] = vcol[jj[s]]; const float w = wcol[jj[s]]; se = fmaf(e[s], v[s], se); sb = fmaf(v[s], v[s], sb); sa += w; }
+    } else {
+      for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) { const uint32_t j = idx[t]; const float vv = vcol[j], w = wcol[j]; se = fmaf(es[t], vv, se); sb = fmaf(vv, vv, sb); sa += w; }
+    }
+    se = wave_sum(se); sb = wave_sum(sb); sa = wave_sum(sa);
+    const float xk = xs[k];
+    const float tau_p = exptau * sa;
+    const float numer = fmaf(exptau, fmaf(xk, sb, se), -ls[k]);
+    const float mu = numer / tau_p;
+    float ef = xk, vf = 0.f;
+    if (only < 0 || a.moments) tn_moments_f32(mu, tau_p, &ef, &vf);
+    if (only >= 0) {                        // update_U(k) / update_V(k): mu and tau of the column -- and its moments when asked for
+      if (lane == 0) {
+        const size_t at = (size_t)u * KP + k;
+        a.mu[at] = mu; a.tauq[at] = tau_p;
+        if (a.moments) { a.var[at] = vf; a.X[at] = ef; a.XT[(size_t)k * a.ldT + u] = ef; a.S2T[(size_t)k * a.ldT + u] = fmaf(ef, ef, vf); }
+      }
+      return;
+    }
+    mus[k] = mu; tps[k] = tau_p; vrs[k] = vf; sas[k] = sa; sbs[k] = sb;      // (every lane stores the same value, and reads back its own store)
+    xs[k] = ef;
+    const float nd = xk - ef;                   // e -= (x' - x) v
+    if (S > 0) {
+#pragma unroll
+      for (int s = 0; s < SS; ++s) e[s] = fmaf(nd, v[s], e[s]);
+    } else {
+      for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) es[t] = fmaf(nd, vcol[idx[t]], es[t]);
+    }
+  }
+
+  // ---- end of the iteration: the lane's sums over its entries, in entry order
+  if (a.part) {
+    double sse = 0.0, sp = 0.0, spp = 0.0, srp = 0.0;
+    if (S > 0) {
+#pragma unroll
+      for (int s = 0; s < SS; ++s) {
+        const uint32_t t = (uint32_t)(s * 64 + lane);
+        if (t < cnt) {
+          const double ed = (double)e[s], r = (double)val[t], p = r - ed;
+          sse = fma(ed, ed, sse); sp += p; spp = fma(p, p, spp); srp = fma(r, p, srp);
+        }
+      }
+    } else {
+      for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) {
+        const double ed = (double)es[t], r = (double)val[t], p = r - ed;
+        sse = fma(ed, ed, sse); sp += p; spp = fma(p, p, spp); srp = fma(r, p, srp);
+      }
+    }
+    sums[6] = sse; sums[7] = sp; sums[8] = spp; sums[9] = srp;
+  }
+}
+
+// The unit's new q -- row major, the expectation and S2 transposed -- and the fp64 pieces of the lane's columns, in column order.
+// One copy behind the forms, with none of their registers live.
+__device__ __forceinline__ void obs_vb_pieces(const ObsVbSweepArgs& a, int u, int lane, const float* xs, const float* ls, const float* pk, double* sums) {
+#pragma clang fp contract(off)
+  const int K = a.K, KP = a.KP;
+  const float* mus = pk; const float* tps = pk + kObsMaxRank; const float* vrs = pk + 2 * kObsMaxRank; const float* sas = pk + 3 * kObsMaxRank; const float* sbs = pk + 4 * kObsMaxRank;
+  double quad = 0.0, lerfc = 0.0, ltau = 0.0, lamx = 0.0, q2 = 0.0, q3 = 0.0;
+  for (int k = lane; k < KP; k += 64) {
+    const size_t at = (size_t)u * KP + k;
+    if (k < K) {
+      const float ef = xs[k], vf = vrs[k], mu = mus[k], tau_p = tps[k];
+      a.X[at] = ef; a.mu[at] = mu; a.tauq[at] = tau_p; a.var[at] = vf;
+      a.XT[(size_t)k * a.ldT + u] = ef;
+      a.S2T[(size_t)k * a.ldT + u] = fmaf(ef, ef, vf);
+      // pieces of elbo() (bnmf_vb_optimised.py:163-177) and of exp_square_diff (:185-187) for this (unit, k)
+      const double e_ = (double)ef, v_ = (double)vf, dm = e_ - (double)mu;
+      quad += 0.5 * (double)tau_p * (v_ + dm * dm);
+      lerfc += log(0.5 * erfc(-(double)mu * sqrt((double)tau_p) * 0.7071067811865476));
+      ltau += log((double)tau_p);
+      lamx += (double)ls[k] * e_;
+      if (a.part) {
+        q2 += (v_ + e_ * e_) * (double)sas[k];                      // sum_obs S2self_k S2other_k
+        q3 += e_ * e_ * (double)sbs[k];                             // sum_obs exp_self_k^2 exp_other_k^2
+      }
+    } else {
+      a.X[at] = 0.f; a.mu[at] = 0.f; a.tauq[at] = 0.f; a.var[at] = 0.f;
+    }
+  }
+  sums[0] = quad; sums[1] = lerfc; sums[2] = ltau; sums[3] = lamx; sums[4] = q2; sums[5] = q3;
+}
+
+__global__ __launch_bounds__(kObsWaves * 64) void obs_vb_sweep_kernel(ObsVbSweepArgs a) {
+  __shared__ float xsh[kObsWaves][kObsMaxRank];
+  __shared__ float lsh[kObsWaves][kObsMaxRank];
+  __shared__ float pkh[kObsWaves][kVbParked * kObsMaxRank];
+  __shared__ double red[kObsWaves][kVbSums];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int u = blockIdx.x * kObsWaves + wave;
+  const bool ok = u < a.n;
+  float* xs = xsh[wave];
+  float* ls = lsh[wave];
+  if (ok)
+    for (int k = lane; k < a.KP; k += 64) {
+      xs[k] = k < a.K ? a.X[(size_t)u * a.KP + k] : 0.f;
+      ls[k] = k < a.K ? a.lambda[(size_t)u * a.KP + k] : 0.f;
+    }
+  __syncthreads();
+  double sums[kVbSums];
+#pragma unroll
+  for (int m = 0; m < kVbSums; ++m) sums[m] = 0.0;
+  if (ok) {
+    const uint32_t cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.ptr[u + 1] - a.ptr[u]));
+    if (a.force_long || cnt > (uint32_t)kObsMaxSlots * 64u) obs_vb_unit<0>(a, u, lane, xs, ls, pkh[wave], sums);
+    else if (cnt <= 64u) obs_vb_unit<1>(a, u, lane, xs, ls, pkh[wave], sums);
+    else if (cnt <= 128u) obs_vb_unit<2>(a, u, lane, xs, ls, pkh[wave], sums);
+    else if (cnt <= 256u) obs_vb_unit<4>(a, u, lane, xs, ls, pkh[wave], sums);
+    else obs_vb_unit<8>(a, u, lane, xs, ls, pkh[wave], sums);
+    if (a.only_k < 0) obs_vb_pieces(a, u, lane, xs, ls, pkh[wave], sums);
+  }
+  if (a.stat) {                      // (wave-uniform, and the same in every wave: all of them reach the barrier)
+    const int nsum = a.part ? kVbSums : 4;
+#pragma unroll
+    for (int m = 0; m < kVbSums; ++m)
+      if (m < nsum) sums[m] = wave_sum_d(sums[m]);
+    if (lane == 0)
+      for (int m = 0; m < kVbSums; ++m) red[wave][m] = sums[m];
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < nsum) {
+      double s = 0.0;
+      for (int w = 0; w < kObsWaves; ++w) s += red[w][t];
+      if (!a.part) a.stat[(size_t)blockIdx.x * 4 + t] = s;                   // the U half sweep: the four ELBO sums
+      else if (t < 6) a.stat[(size_t)blockIdx.x * 6 + t] = s;                // the V half sweep: those, q2 and q3 ...
+      else a.part[(size_t)blockIdx.x * 4 + (t - 6)] = s;                     // ... and the residual's four sums
+    }
+  }
+}
+
+// exptau and the iteration's record from the two half sweeps' sums (kernel_misc.hip vb_finish_body: the same rules and the same
+// record), with exp_square_diff = SSE + sum (q2 - q3) of the V half sweep, which saw the final U
+__global__ __launch_bounds__(256) void obs_vb_finish_kernel(ObsVbFinishArgs a) {
+  double su[4], sv[6], t[4];
+  obs_fold<4>(a.stat_r, a.nb_r, su);
+  __syncthreads();
+  obs_fold<6>(a.stat_c, a.nb_c, sv);
+  __syncthreads();
+  obs_fold<4>(a.part, a.nb_c, t);
+  if (threadIdx.x == 0) {
+    const double sse = t[0], sp = t[1], spp = t[2], srp = t[3], n = a.n_obs;
+    const double esd = sse + (sv[4] - sv[5]);
+    const double alpha_s = a.alpha + 0.5 * n, beta_s = a.beta + 0.5 * esd;
+    const double exptau = alpha_s / beta_s;
+    *a.tau_d = exptau; *a.tau_f = (float)exptau;
+    const double ss_tot = a.sumR2 - a.sumR * a.sumR / n;
+    const double cov = srp - a.sumR * sp / n, vp = spp - sp * sp / n;
+    a.rec[0] = exptau; a.rec[1] = sse / n;
+    a.rec[2] = ss_tot != 0.0 ? 1.0 - sse / ss_tot : __longlong_as_double(0x7ff0000000000000LL);
+    a.rec[3] = cov / (sqrt(ss_tot) * sqrt(vp));
+    a.rec[4] = esd; a.rec[5] = beta_s;
+    for (int c = 0; c < 4; ++c) { a.rec[6 + c] = su[c]; a.rec[10 + c] = sv[c]; }
+  }
+}
+
+// sum over the observed entries of (R_ij - E_i . E_j)^2 + sum_k [(var + E^2)_ik (var + E^2)_jk - E_ik^2 E_jk^2], fp64
+__global__ __launch_bounds__(256) void obs_vb_esd_kernel(ObsVbEsdArgs a) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  for (int u = blockIdx.x; u < a.n; u += gridDim.x) {
+    const float* xr = a.X + (size_t)u * a.KP;
+    const float* vr = a.var + (size_t)u * a.KP;
+    for (uint32_t t = a.ptr[u] + (uint32_t)tid; t < a.ptr[u + 1]; t += 256) {
+      const size_t j = a.idx[t];
+      const float* xo = a.Xo + j * a.KP;
+      const float* vo = a.varo + j * a.KP;
+      double p = 0.0, vs = 0.0;
+      for (int k = 0; k < a.K; ++k) {
+        const double x = (double)xr[k], y = (double)xo[k], x2 = x * x, y2 = y * y;
+        p = fma(x, y, p);
+        vs += ((double)vr[k] + x2) * ((double)vo[k] + y2) - x2 * y2;
+      }
+      const double d = (double)a.val[t] - p;
+      s += d * d + vs;
+    }
+  }
+  red[tid] = s;
+  __syncthreads();
+  for (int w = 128; w >= 1; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) a.part[blockIdx.x] = red[0];
+}
+__global__ __launch_bounds__(256) void obs_vb_esd_fold_kernel(const double* part, int nb, double* out) {
+  double t[1];
+  obs_fold<1>(part, nb, t);
+  if (threadIdx.x == 0) out[0] = t[0];
+}
+
+}  // namespace
+
+void launch_obs_vb_sweep(const ObsVbSweepArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(obs_vb_sweep_kernel, dim3(obs_sweep_blocks(a.n)), dim3(kObsWaves * 64), 0, st, a);
+}
+
+void launch_obs_vb_finish(const ObsVbFinishArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(obs_vb_finish_kernel, dim3(1), dim3(256), 0, st, a);
+}
+
+void launch_obs_vb_esd(const ObsVbEsdArgs& a, double* out, hipStream_t st) {
+  const int nb = obs_vb_esd_blocks(a.n);
+  hipLaunchKernelGGL(obs_vb_esd_kernel, dim3(nb), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(obs_vb_esd_fold_kernel, dim3(1), dim3(256), 0, st, a.part, nb, out);
+}
+
+}  // namespace bnmtf

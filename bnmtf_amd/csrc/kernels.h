@@ -601,4 +601,39 @@ void launch_obs_sweep(const ObsSweepArgs& a, hipStream_t st);
 void launch_obs_finish(const ObsFinishArgs& a, hipStream_t st);
 void launch_obs_metric(const ObsMetricArgs& a, double* out8, hipStream_t st);   // out8: n, sum R, sum R^2, sum P, sum P^2, sum R P, 0, 0
 
+// The variational two-factor model on the same lists (kernel_obs_vb.hip): q = (mu, tau, var) beside the expectation X, and
+// S2 = var + X^2 transposed beside XT for the other direction's second gather
+struct ObsVbSweepArgs {
+  const uint32_t* ptr; const uint32_t* idx; const float* val;     // as ObsSweepArgs
+  int n, m, K, KP;
+  int only_k;                        // >= 0: update_U(k) / update_V(k) -- mu and tau of this column only
+  int moments;                       // only_k >= 0: also the column's expectation and variance (0: they stay)
+  int force_long;
+  const float* lambda;               // [n][KP]
+  float* X; float* XT; float* S2T; int ldT;       // this direction's expectation [n][KP], and with S2 transposed [K][ldT]
+  float* mu; float* tauq; float* var;             // [n][KP]
+  const float* Xo; const float* XoT; const float* S2oT; int ldT_o;   // the other factor [m][KP], [K][ldT_o] twice; ldT_o > m: word m of every column is zero
+  float* escratch;                   // [entries]
+  const float* tau;                  // device scalar: exptau
+  double* stat;                      // null (the hooks), or the blocks' sums of quad, log erfc, log tau, lambda E [blocks][4] -- with part: and of q2, q3 [blocks][6]
+  double* part;                      // null, or [blocks][4]: SSE, sum P, sum P^2, sum R P of the final residual (the V half sweep)
+};
+struct ObsVbFinishArgs {
+  const double* stat_r; int nb_r;    // the U half sweep's [nb_r][4]
+  const double* stat_c; const double* part; int nb_c;   // the V half sweep's [nb_c][6] and [nb_c][4]
+  double n_obs, sumR, sumR2, alpha, beta;
+  double* tau_d; float* tau_f;
+  double* rec;                       // [14]: exptau, MSE, R^2, Rp, exp_square_diff, beta_s, the four sums of U, the four of V
+};
+struct ObsVbEsdArgs {
+  const uint32_t* ptr; const uint32_t* idx; const float* val; int n;     // the row list
+  int K, KP;
+  const float* X; const float* var; const float* Xo; const float* varo;  // rows' and columns' expectation and variance [.][KP]
+  double* part;                      // [obs_vb_esd_blocks(n)]
+};
+inline int obs_vb_esd_blocks(int n) { return n < 1 ? 1 : (n > 1024 ? 1024 : n); }
+void launch_obs_vb_sweep(const ObsVbSweepArgs& a, hipStream_t st);
+void launch_obs_vb_finish(const ObsVbFinishArgs& a, hipStream_t st);
+void launch_obs_vb_esd(const ObsVbEsdArgs& a, double* out, hipStream_t st);
+
 }  // namespace bnmtf

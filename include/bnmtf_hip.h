@@ -427,6 +427,26 @@ BNMTF_API int bnmf_obs_cond_params(bnmtf_handle h, int which, int k, double* num
 BNMTF_API int bnmf_obs_metric_sums(bnmtf_handle h, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values,
                          const double* A, const double* B, double sums_out[6]);
 
+/* ---- the variational two-factor model on the observed-entry layout (class bnmf_vb_observed) -----
+ * The calls of bnmf_vb_* above with the same arguments and the same meaning, on a handle of bnmtf_obs_create: the iteration is two
+ * half sweeps over the entry lists and an end-of-iteration kernel (csrc/kernel_obs_vb.hip), cost and memory proportional to the
+ * number of observed entries.  The q parameters' buffers are allocated by the first bnmf_vbo_set_state: a handle that only
+ * samples holds none.  A null handle or one of bnmtf_create is refused with BNMTF_EINVAL, a call ahead of bnmf_vbo_set_state
+ * with BNMTF_ESTATE.  Fixed summation order: the same call gives the same bits, run(a) then run(b) those of run(a + b). */
+/* all eight q-parameter matrices ([I][K] four times, [J][K] four times) and exptau; none may be null */
+BNMTF_API int bnmf_vbo_set_state(bnmtf_handle h, const double* muU, const double* tauU, const double* expU, const double* varU,
+                       const double* muV, const double* tauV, const double* expV, const double* varV, double exptau);
+/* any pointer may be null */
+BNMTF_API int bnmf_vbo_get_state(bnmtf_handle h, double* muU, double* tauU, double* expU, double* varU,
+                       double* muV, double* tauV, double* expV, double* varV);
+/* run(n_iter) with the outputs of bnmf_vb_run: exptau_out [n], perf_out [n][3] (MSE, R^2, Rp on the observed entries),
+ * elbo_terms_out [n][10] (exp_square_diff, beta_s, the four sums of U, the four of V), times_out [n]; any may be null */
+BNMTF_API int bnmf_vbo_run(bnmtf_handle h, int n_iter, double* exptau_out, double* perf_out, double* elbo_terms_out, double* times_out);
+/* update_U(k) (which = 0) or update_V(k) (which = 1): mu and tau of column k; moments != 0: also its expectation and variance */
+BNMTF_API int bnmf_vbo_update(bnmtf_handle h, int which, int k, int moments);
+/* exp_square_diff() of the state the device holds, fp64 over the observed entries */
+BNMTF_API int bnmf_vbo_exp_square_diff(bnmtf_handle h, double* out);
+
 #ifdef __cplusplus
 }
 #endif
