@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "model.h"
+#include "slot_layout.h"
 #include "comm.h"
 #include "many.h"
 #include "device_rng.h"
@@ -57,6 +58,14 @@ template <typename T>
 static void dfree(T*& p) {
   if (p) (void)hipFree(p);
   p = nullptr;
+}
+// a host table onto the device, in an allocation of its own (at least one element); returns with the copy done
+template <typename T>
+static int upload(T** dst, const std::vector<T>& src, hipStream_t st) {
+  CHK(dalloc(dst, src.size(), false));
+  if (!src.empty()) HIPCHK(hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));            // (src is the caller's local)
+  return BNMTF_OK;
 }
 
 // a handle of bnmtf_obs_create (the observed-entry layout, api_obs.inc) holds none of what the other entry points work on
@@ -142,48 +151,12 @@ struct DevBuf {
   ~DevBuf() { dfree(p); }
 };
 
-// Host threads for the O(I*J) layout passes of bnmtf_create (a cross-validation driver pays them once per model):
-// fn(begin, end) over fixed-size chunks of [0, n), so results never depend on the thread count.
-template <typename Fn>
-static void parallel_chunks(int n, int chunk, Fn fn) {
-  const int nchunks = (n + chunk - 1) / chunk;
-  int nt = (int)std::thread::hardware_concurrency();
-  if (const char* e = getenv("BNMTF_HOST_THREADS")) nt = atoi(e);
-  nt = std::max(1, std::min({nt, 32, nchunks}));
-  if ((size_t)n * (size_t)chunk < 4096) nt = 1;           // (a few thousand rows: starting the threads costs more than the pass)
-  std::atomic<int> next{0};
-  auto work = [&]() {
-    for (int c = next.fetch_add(1); c < nchunks; c = next.fetch_add(1)) fn(c * chunk, std::min(n, (c + 1) * chunk));
-  };
-  if (nt == 1) { work(); return; }
-  // nt - 1 helpers and the calling thread.  A thread that cannot be had (EAGAIN: the user's process / thread limit -- a long test
-  // session with worker pools, three ranks building their layouts at once) must not leave this function as an exception: it
-  // would cross the C ABI and end the process (std::terminate).  The chunks are claimed one by one, so whoever is there does them.
-  std::vector<std::thread> ts;
-  ts.reserve(nt);
-  for (int t = 0; t + 1 < nt; ++t) {
-    try { ts.emplace_back(work); } catch (const std::system_error&) { break; }
-  }
-  work();
-  for (auto& t : ts) t.join();
-}
-
-// BNMTF_CREATE_TIMING=1: wall-clock laps of bnmtf_create's phases on stderr
-struct CreateLaps {
-  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-  bool on = getenv("BNMTF_CREATE_TIMING") != nullptr;
-  void lap(const char* what) {
-    const auto now = std::chrono::steady_clock::now();
-    if (on) fprintf(stderr, "bnmtf_create: %-44s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-    t = now;
-  }
-};
 // ------------------------------------------------------------------ layout
-// Fill one direction.  get(u, r) returns (observed, value) of unit u (global) at
-// inner index r.
+// Fill one direction: the contraction's split geometry, the I x J passes on the device (kernel_layout.hip: masked / transposed
+// contraction operand, missing lists) and their download, the slot layout from the downloaded lists (one call into
+// slot_layout.hip: host code), the uploads and the remaining allocations.
 // dR / dM: the data and the mask on the device ([I][J] row major); by_rows: a unit is a row of R (else a column); obs: observed
-// entries per unit (global).  The I x J passes -- masked / transposed contraction operand, missing lists -- run on the device
-// (kernel_layout.hip); the slot layout below is built on the host from the downloaded lists.
+// entries per unit (global).
 static int build_dir(Dir& d, int nglob, int m, int W, int rank, int world, const double* lambda,
                      const float* dR, const uint8_t* dM, int I, int J, bool by_rows, const std::vector<uint32_t>& obs, hipStream_t st) {
   d.nglob = nglob; d.m = m; d.W = W; d.KP = W <= 32 ? 32 : 64;
@@ -233,277 +206,44 @@ static int build_dir(Dir& d, int nglob, int m, int W, int rank, int world, const
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
   laps.lap("  build_dir: R~ operand + missing lists (device)");
-  auto miss_begin = [&](int ul) { return idx.data() + ptr[ul]; };
-  auto miss_end = [&](int ul) { return idx.data() + ptr[ul] + ((uint32_t)m - obs[d.n0 + ul]); };
-
-  // fast layout: a unit owns a 32-lane half wave.  Lane r prefers the entries with j mod 32 == r (bank-conflict-free
-  // LDS gathers).  Residue classes are binomially unbalanced, so instead of padding every lane to the fullest class
-  // a unit gets E = ceil(cnt / 32) slots per lane (rounded up to even) and the entries of over-full classes are
-  // parked in lanes with room.  A parked entry shares its row's LDS read with the entry of its own residue lane (a
-  // 2-way bank conflict: one extra LDS cycle for that row); parked entries are packed into the last rows, distinct
-  // residues per row, so that few rows pay it.  BNMTF_BALANCE=0 restores the padded conflict-free layout.
-  d.mz = round_up(m, 32);
-  d.pw = round_up(d.mz + 32, 256);
-  // an inner extent that does not fit one LDS panel is cut in two chunks (kernel_sweep_fast.hip: sweep_two_chunks_plan); a
-  // unit's entries are then laid out chunk by chunk, with inner indices local to the chunk
-  d.nch = 1; d.mh = 0; d.pw_chunk = d.pw; d.pw1 = 0;
-  if (!sweep_fast_supported(d.KP, d.pw) && !getenv("BNMTF_NO_CHUNKS") && sweep_two_chunks_plan(d.KP, m, &d.mh, &d.pw_chunk, &d.pw1)) d.nch = 2;
-  const int nch = d.nch;
+  // the slot layout of the on-chip sweeps and the choice of their block shape: host arithmetic on the downloaded lists
+  // (slot_layout.hip; the environment's switches are read there, once, now)
+  SlotLayout lay;
   {
-#ifdef BNMTF_EXPERIMENTS
-    const bool balance = !(getenv("BNMTF_BALANCE") && atoi(getenv("BNMTF_BALANCE")) == 0);
-#else
-    constexpr bool balance = true;
-#endif
-    const uint32_t kNone = 0xFFFFFFFFu;
-    std::vector<int> Eu(d.n, 0);
-    std::vector<std::vector<uint32_t>> lanes((size_t)d.n * 32 * nch);     // per unit, per chunk, per lane: slot contents (kNone = empty), chunk-local inner indices
-    // E slots per lane for the 32 lane lists of one half wave (L[r]: the entries of residue class r, `cnt` in all), balanced:
-    // E = ceil(cnt / 32) rounded up to even, the entries of over-full classes parked in lanes with room (see above)
-    auto balance_lanes = [&](std::vector<uint32_t>* L, size_t cnt, std::vector<std::vector<uint32_t>>& over) -> int {
-      int emax = 0;
-      for (int r = 0; r < 32; ++r) emax = std::max(emax, (int)L[r].size());
-      int E = std::max(2, (emax + 1) & ~1);
-      const int Eb = std::max(2, ((int)((cnt + 31) / 32) + 1) & ~1);
-      if (balance && Eb < E) {
-        E = Eb;
-        size_t nover = 0;
-        for (int r = 0; r < 32; ++r) {
-          over[r].clear();
-          while ((int)L[r].size() > E) { over[r].push_back(L[r].back()); L[r].pop_back(); ++nover; }
-        }
-        std::vector<int> own(32);
-        for (int r = 0; r < 32; ++r) { own[r] = (int)L[r].size(); L[r].resize(E, kNone); }
-        // last rows first; in a row every free lane takes a parked entry of a residue not yet parked in that row
-        int rr = 0;
-        for (int row = E - 1; row >= 0 && nover > 0; --row) {
-          uint32_t used = 0;
-          for (int lane = 0; lane < 32 && nover > 0; ++lane) {
-            if (own[lane] > row) continue;
-            int pick = -1;
-            for (int t = 0; t < 32; ++t) { const int r = (rr + t) & 31; if (!over[r].empty() && !((used >> r) & 1u)) { pick = r; break; } }
-            if (pick < 0) break;
-            L[lane][row] = over[pick].back(); over[pick].pop_back(); --nover;
-            used |= 1u << pick; rr = (pick + 1) & 31;
-          }
-        }
-        for (int row = E - 1; row >= 0 && nover > 0; --row)      // leftovers (same residue twice in a row): any free slot
-          for (int lane = 0; lane < 32 && nover > 0; ++lane) {
-            if (L[lane][row] != kNone) continue;
-            for (int r = 0; r < 32; ++r) if (!over[r].empty()) { L[lane][row] = over[r].back(); over[r].pop_back(); --nover; break; }
-          }
-      }
-      return E;
-    };
-    parallel_chunks(d.n, 64, [&](int ua, int ub) {
-    std::vector<std::vector<uint32_t>> over(32);
-    for (int ul = ua; ul < ub; ++ul) {
-      int ehalf = 0;
-      for (int ch = 0; ch < nch; ++ch) {
-      std::vector<uint32_t>* L = &lanes[((size_t)ul * nch + ch) * 32];
-      const uint32_t lo = ch == 0 ? 0u : (uint32_t)d.mh, hi = (nch == 2 && ch == 0) ? (uint32_t)d.mh : 0xFFFFFFFFu;
-      size_t cnt = 0;
-      {   // one allocation per lane instead of a doubling chain (32 lanes x 8192 units: the layout pass was mostly malloc)
-        const size_t guess = (size_t)(miss_end(ul) - miss_begin(ul)) / (32 * (size_t)nch) + 8;
-        for (int r = 0; r < 32; ++r) L[r].reserve(guess);
-      }
-      for (const uint32_t* pj = miss_begin(ul); pj != miss_end(ul); ++pj) { const uint32_t j = *pj; if (j >= lo && j < hi) { L[(j - lo) & 31].push_back(j - lo); ++cnt; } }
-      const int E = balance_lanes(L, cnt, over);
-      ehalf = std::max(ehalf, E);
-      }
-      Eu[ul] = nch * ehalf;                  // two chunks: each gets half of the unit's slot rows (a multiple of 4 in all)
-    }
-    });
-    laps.lap("    layout: lanes filled and balanced");
-    auto res = [&](int ul, int ch, int r) -> const std::vector<uint32_t>& { return lanes[((size_t)ul * nch + ch) * 32 + r]; };
-    std::vector<int> order(d.n);
-    for (int i = 0; i < d.n; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return Eu[x] > Eu[y]; });
-    // Units pair up in descending slot-count order.  The 2/4/8-wave blocks take the pairs in that order.  The on-chip
-    // kernel picks the slot class per WAVE, so for the 16-wave shape the pairs are dealt to the
-    // blocks boustrophedon (and to the four SIMDs of a block likewise): every block, and every SIMD, gets the same mix
-    // of full and light units, and one round of blocks ends together.
-    const int npairs_real = (d.n + 1) / 2;
-    const int emax_all = d.n > 0 ? Eu[order[0]] : 0;
-    const int wide_blocks = (npairs_real + 15) / 16;
-    const bool wide_can = nch == 1 && sweep_wide_supported(d.KP, d.pw) && emax_all <= kWideMaxSlots && d.n > 0;
-    d.wide_can = wide_can;
-    d.use_wide = wide_can && wide_blocks >= 192;
-    if (const char* e = getenv("BNMTF_WIDE")) d.use_wide = wide_can && atoi(e) != 0;      // 0: never, 1: whenever it can run
-    if (const char* e = getenv("BNMTF_VB_PATH")) d.vb_path = !strcmp(e, "masked") ? 1 : !strcmp(e, "pairs") ? 2 : 0;
-    d.use_turns = false;
-#ifdef BNMTF_EXPERIMENTS
-    if (const char* e = getenv("BNMTF_TURNS")) d.use_turns = d.use_wide && sweep_turns_supported(d.KP, d.pw) && atoi(e) != 0;
-#endif
-    d.f_npairs = d.use_wide ? wide_blocks * 16 : npairs_real;
-    auto slot_of = [&](int pi) {
-      if (!d.use_wide) return pi;
-      const int r = pi / wide_blocks, c = pi % wide_blocks;
-      const int blk = (r & 1) ? wide_blocks - 1 - c : c;
-      // rank 0 = the pairs with the most slots.  The lightest quarter goes to waves 0-3, the waves of the sampler window (sampler
-      // and table filler: sweep_chip.inc, RL) -- their role needs registers the heaviest slot class does not have, and a light
-      // wave reaches the column's first barrier early, with the word-only half of its candidate done by the time the others arrive
-      const int t = r >> 2, sx = r & 3;
-      return blk * 16 + 4 * (3 - t) + ((t & 1) ? 3 - sx : sx);
-    };
-    std::vector<int> umap((size_t)d.f_npairs * 2, -1);
-    std::vector<uint32_t> pE(d.f_npairs, 0u), pB(d.f_npairs, 0u);
-    d.f_emax = 0;
-    for (int pi = 0; pi < npairs_real; ++pi) {
-      int e = 0;
-      const int sl = slot_of(pi);
-      for (int hh = 0; hh < 2; ++hh) {
-        const int pos = 2 * pi + hh;
-        if (pos < d.n) { umap[2 * sl + hh] = order[pos]; e = std::max(e, Eu[order[pos]]); }
-      }
-      pE[sl] = (uint32_t)e;
-      d.f_emax = std::max(d.f_emax, e);
-    }
-    size_t rows_total = 0;
-    for (int sl = 0; sl < d.f_npairs; ++sl) { pB[sl] = (uint32_t)rows_total; rows_total += pE[sl]; }
-    std::vector<uint32_t> off(std::max<size_t>(rows_total, 1) * 64);
-    parallel_chunks(d.f_npairs, 64, [&](int pa, int pb) {
-    for (int pi = pa; pi < pb; ++pi)
-      for (int hh = 0; hh < 2; ++hh) {
-        const int ul = umap[2 * pi + hh];
-        for (uint32_t sidx = 0; sidx < pE[pi]; ++sidx) {
-          // two chunks: the pair's first pE / 2 rows are chunk 0 (zero words behind index mh), the rest chunk 1 (behind mz - mh)
-          const int ch = (nch == 2 && sidx >= pE[pi] / 2) ? 1 : 0;
-          const uint32_t sl = sidx - (uint32_t)ch * (pE[pi] / 2);
-          const uint32_t sent0 = nch == 2 ? (uint32_t)(ch ? d.mz - d.mh : d.mh) : (uint32_t)d.mz;
-          for (int r = 0; r < 32; ++r) {
-            uint32_t v = sent0 + (uint32_t)r;
-            if (ul >= 0) { const auto& lst = res(ul, ch, r); if (sl < lst.size() && lst[sl] != kNone) v = lst[sl]; }
-            off[((size_t)pB[pi] + sidx) * 64 + hh * 32 + r] = v;
-          }
-        }
-      }
-    });
-    d.f_slots = rows_total;
-    laps.lap("    layout: slot table filled");
-    CHK(dalloc(&d.f_unit_map, umap.size(), false));
-    HIPCHK(hipMemcpy(d.f_unit_map, umap.data(), umap.size() * sizeof(int), hipMemcpyHostToDevice));
-    CHK(dalloc(&d.f_pair_E, pE.size(), false));
-    HIPCHK(hipMemcpy(d.f_pair_E, pE.data(), pE.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    CHK(dalloc(&d.f_pair_base, pB.size(), false));
-    HIPCHK(hipMemcpy(d.f_pair_base, pB.data(), pB.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    CHK(dalloc(&d.f_off, off.size(), false));
-    HIPCHK(hipMemcpy(d.f_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    {   // 16-bit packed slot pairs (two inner indices per word): the slot table the on-chip kernels load
-      d.pair_ok = d.mz + 32 < 65536;
-      std::vector<uint32_t> off16(std::max<size_t>(rows_total / 2, 1) * 64, 0);
-      if (d.pair_ok)
-        parallel_chunks((int)(rows_total / 2), 4096, [&](int ra, int rb) {
-          for (size_t r2 = (size_t)ra; r2 < (size_t)rb; ++r2)
-            for (int l = 0; l < 64; ++l) off16[r2 * 64 + l] = (off[(2 * r2) * 64 + l] & 0xFFFFu) | (off[(2 * r2 + 1) * 64 + l] << 16);
-        });
-      CHK(dalloc(&d.f_off16, off16.size(), false));
-      HIPCHK(hipMemcpy(d.f_off16, off16.data(), off16.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    // pairs with more slots per lane than the block shape holds (kFastMaxSlots; the 16-wave shape is only chosen when
-    // every pair fits) are left to the generic kernel: their waves idle in the on-chip kernel
-    {
-      std::vector<int> gen;
-      // waves per block: 8 when there are enough units for >= 256 blocks, else 4 or 2 (multi-GPU shards, small problems)
-      d.f_nw = d.f_npairs >= 8 * 256 ? 8 : (d.f_npairs >= 4 * 256 ? 4 : (d.f_npairs >= 2 * 64 ? 2 : 8));
-      if (const char* e = getenv("BNMTF_FAST_NW")) d.f_nw = atoi(e) == 2 ? 2 : (atoi(e) == 4 ? 4 : 8);
-      if (d.use_wide) d.f_nw = 16;
-      // the twin shape (BNMTF_TWIN=1): the 16-wave layout run by 8-wave blocks, two to a CU (sweep_chip.inc, TW = 1)
-      d.use_twin = false;
-#ifdef BNMTF_EXPERIMENTS
-      if (const char* e = getenv("BNMTF_TWIN")) d.use_twin = d.use_wide && !d.use_turns && world == 1 && d.pw <= kTwinPanelStride && atoi(e) != 0;
-#endif
-      if (d.use_twin) d.f_nw = 8;
-      if (nch == 2) d.f_nw = 8;                       // the two-chunk variant is an 8-wave kernel
-      for (int pi = 0; pi < d.f_npairs && !d.use_wide; ++pi)
-        if ((int)pE[pi] > kFastMaxSlots)
-          for (int t = 2 * pi; t < 2 * pi + 2; ++t) if (umap[t] >= 0) gen.push_back(umap[t]);
-      d.fast_ok = true;
-      d.f_gen_count = (int)gen.size();
-      CHK(dalloc(&d.f_gen_units, std::max<size_t>(gen.size(), 1), false));
-      if (!gen.empty()) HIPCHK(hipMemcpy(d.f_gen_units, gen.data(), gen.size() * sizeof(int), hipMemcpyHostToDevice));
-      d.stats_blocks = std::max((d.f_npairs + d.f_nw - 1) / d.f_nw, sweep_vb_blocks(d.f_npairs)) + 2;   // the VB sweep writes its own block count of rows
-      // the block of every slot row: what build_handover needs beside the layout itself (one GPU, the 16-wave shape or the
-      // plain 8-wave shape, every unit on the on-chip kernel)
-      if (world == 1 && !d.use_turns && d.pair_ok && d.f_gen_count == 0 && nch == 1 && (d.f_nw == 16 || d.f_nw == 8) && d.f_npairs / d.f_nw < 65535) {
-        d.ho_ppb = d.f_nw;
-        std::vector<uint16_t> row_blk(std::max<size_t>(rows_total, 1), 0);
-        for (int pi = 0; pi < d.f_npairs; ++pi)
-          for (uint32_t sidx = 0; sidx < pE[pi]; ++sidx) row_blk[pB[pi] + sidx] = (uint16_t)(pi / d.ho_ppb);
-        CHK(dalloc(&d.f_row_blk, row_blk.size(), false));
-        HIPCHK(hipMemcpy(d.f_row_blk, row_blk.data(), row_blk.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-      }
-    }
-    // ---- the unit-per-wave layout (kernel_sweep_unit.hip, round 6): few units per CU -- a shard of a multi-GPU run, a small
-    // problem.  A pair's two halves belong to the SAME unit: residue class r of the unit's missing entries is dealt in turn to
-    // lanes r and r + 32 (each half of a 64-lane LDS read touches 32 distinct banks), each half balanced like a 32-lane unit.
-    // Pair p = local unit p (no sorting: a block's waves do not share slot work).  Beside the layout above (the variational
-    // sweeps keep it), a few MB at these sizes.
-    d.uw_ok = false;
-    // (a test that forces another block shape -- BNMTF_WIDE, BNMTF_FAST_NW -- gets that shape; BNMTF_UNIT=0 switches this one off)
-    if (d.n > 0 && d.n <= kUnitMaxUnits && nch == 1 && d.pair_ok && sweep_unit_supported(d.KP, d.pw) && !getenv("BNMTF_WIDE") && !getenv("BNMTF_FAST_NW") &&
-        !(getenv("BNMTF_UNIT") && atoi(getenv("BNMTF_UNIT")) == 0)) {
-      std::vector<std::vector<uint32_t>> ul((size_t)d.n * 64);
-      std::vector<uint32_t> uE(d.n, 0u), uB(d.n, 0u);
-      parallel_chunks(d.n, 64, [&](int ua, int ub) {
-        std::vector<std::vector<uint32_t>> over(32);
-        for (int u = ua; u < ub; ++u) {
-          std::vector<uint32_t>* L = &ul[(size_t)u * 64];
-          size_t cnt[2] = {0, 0};
-          uint8_t turn[32] = {};
-          for (const uint32_t* pj = miss_begin(u); pj != miss_end(u); ++pj) {
-            const int r = (int)(*pj & 31u), hh = turn[r]; turn[r] ^= 1;
-            L[hh * 32 + r].push_back(*pj); ++cnt[hh];
-          }
-          const int e0 = balance_lanes(L, cnt[0], over), e1 = balance_lanes(L + 32, cnt[1], over);
-          uE[u] = (uint32_t)std::max(e0, e1);
-        }
-      });
-      size_t rows = 0; uint32_t emax = 0;
-      for (int u = 0; u < d.n; ++u) { uB[u] = (uint32_t)rows; rows += uE[u]; emax = std::max(emax, uE[u]); }
-      if ((int)emax <= kUnitMaxSlots) {
-        std::vector<uint32_t> o16(std::max<size_t>(rows / 2, 1) * 64, 0);
-        parallel_chunks(d.n, 64, [&](int ua, int ub) {
-          for (int u = ua; u < ub; ++u)
-            for (uint32_t sidx = 0; sidx < uE[u]; ++sidx)
-              for (int l = 0; l < 64; ++l) {
-                const auto& lst = ul[(size_t)u * 64 + l];
-                uint32_t v = (uint32_t)d.mz + (uint32_t)(l & 31);
-                if (sidx < lst.size() && lst[sidx] != kNone) v = lst[sidx];
-                uint32_t& w = o16[((size_t)(uB[u] + sidx) / 2) * 64 + l];
-                w = ((uB[u] + sidx) & 1u) ? (w & 0xFFFFu) | (v << 16) : (w & 0xFFFF0000u) | v;
-              }
-        });
-        std::vector<int> um((size_t)d.n * 2);
-        for (int u = 0; u < d.n; ++u) um[2 * u] = um[2 * u + 1] = u;
-        CHK(dalloc(&d.u_unit_map, um.size(), false));
-        HIPCHK(hipMemcpy(d.u_unit_map, um.data(), um.size() * sizeof(int), hipMemcpyHostToDevice));
-        CHK(dalloc(&d.u_pair_E, uE.size(), false));
-        HIPCHK(hipMemcpy(d.u_pair_E, uE.data(), uE.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        CHK(dalloc(&d.u_pair_base, uB.size(), false));
-        HIPCHK(hipMemcpy(d.u_pair_base, uB.data(), uB.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        CHK(dalloc(&d.u_off16, o16.size(), false));
-        HIPCHK(hipMemcpy(d.u_off16, o16.data(), o16.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        d.u_nw = d.n <= 4 * 256 ? 4 : 8;
-        if (const char* e = getenv("BNMTF_UNIT_NW")) d.u_nw = atoi(e) == 8 ? 8 : 4;
-        d.u_emax = (int)emax;
-        d.uw_ok = true;
-        d.stats_blocks = std::max(d.stats_blocks, (d.n + d.u_nw - 1) / d.u_nw + 2);
-      }
-      laps.lap("    layout: unit-per-wave tables");
-    }
-    CHK(dalloc(&d.stats, (size_t)d.stats_blocks * 4));
-    laps.lap("    layout: tables uploaded");
+    std::vector<MissingView> miss(d.n);
+    for (int ul = 0; ul < d.n; ++ul) miss[ul] = {idx.data() + ptr[ul], (uint32_t)m - obs[d.n0 + ul]};
+    SlotLayoutInput in;
+    in.n = d.n; in.m = m; in.KP = d.KP; in.world = world; in.miss = miss.data(); in.sw = LayoutSwitches::from_env();
+    build_slot_layout(in, lay, &laps);
   }
-
+  d.mz = lay.mz; d.pw = lay.pw; d.nch = lay.nch; d.mh = lay.mh; d.pw_chunk = lay.pw_chunk; d.pw1 = lay.pw1; d.pair_ok = lay.pair_ok;
+  d.wide_can = lay.wide_can; d.use_wide = lay.use_wide; d.use_turns = lay.use_turns; d.use_twin = lay.use_twin;
+  d.f_nw = lay.f_nw; d.vb_path = lay.vb_path; d.ho_ppb = lay.ho_ppb; d.stats_blocks = lay.stats_blocks;
+  d.f_npairs = lay.npairs; d.f_emax = lay.emax; d.f_slots = lay.slots; d.f_gen_count = (int)lay.gen_units.size();
+  d.uw_ok = lay.uw_ok; d.u_nw = lay.u_nw; d.u_emax = lay.u_emax;
+  d.fast_ok = true;
+  CHK(upload(&d.f_unit_map, lay.unit_map, st));
+  CHK(upload(&d.f_pair_E, lay.pair_E, st));
+  CHK(upload(&d.f_pair_base, lay.pair_base, st));
+  CHK(upload(&d.f_off, lay.off, st));
+  CHK(upload(&d.f_off16, lay.off16, st));
+  CHK(upload(&d.f_gen_units, lay.gen_units, st));
+  if (d.ho_ppb > 0) CHK(upload(&d.f_row_blk, lay.row_blk, st));       // (what build_handover needs beside the layout itself)
+  if (d.uw_ok) {
+    CHK(upload(&d.u_unit_map, lay.u_unit_map, st));
+    CHK(upload(&d.u_pair_E, lay.u_pair_E, st));
+    CHK(upload(&d.u_pair_base, lay.u_pair_base, st));
+    CHK(upload(&d.u_off16, lay.u_off16, st));
+  }
+  CHK(dalloc(&d.stats, (size_t)d.stats_blocks * 4));
+  laps.lap("    layout: tables uploaded");
   laps.lap("  build_dir: slot layout + its uploads");
   CHK(dalloc(&d.slabs, (size_t)d.split * d.n_pad * d.KP));
   CHK(dalloc(&d.q, idx.size()));
   std::vector<float> lam((size_t)std::max(d.n, 1) * d.KP, 0.0f);
   for (int ul = 0; ul < d.n; ++ul)
     for (int k = 0; k < W; ++k) lam[(size_t)ul * d.KP + k] = (float)lambda[(size_t)(d.n0 + ul) * W + k];
-  CHK(dalloc(&d.lambda, lam.size(), false));
-  HIPCHK(hipMemcpy(d.lambda, lam.data(), lam.size() * sizeof(float), hipMemcpyHostToDevice));
+  CHK(upload(&d.lambda, lam, st));
   // C64 | colsum | colsum2 in one piece: what a multi-GPU run sums over the ranks with ONE all-reduce (exchange_factor)
   CHK(dalloc(&d.C64, (size_t)64 * 64 + 128));
   d.colsum = d.C64 + 64 * 64; d.colsum2 = d.colsum + 64; d.gram_packed = true;
@@ -1128,6 +868,40 @@ int bnmtf_shard_range(int64_t n, int rank, int world, int64_t* first, int64_t* c
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
+int bnmtf_slot_layout(int n, int m, int KP, int world, const uint32_t* miss_ptr, const uint32_t* miss_idx, int64_t* info,
+                      int32_t* unit_map, uint32_t* pair_E, uint32_t* pair_base, uint32_t* off, uint32_t* off16, int32_t* gen_units,
+                      uint16_t* row_blk, int32_t* u_unit_map, uint32_t* u_pair_E, uint32_t* u_pair_base, uint32_t* u_off16) try {
+  if (!miss_ptr || !info) { set_error("bnmtf_slot_layout: null argument"); return BNMTF_EINVAL; }
+  if (n < 1 || m < 1 || (KP != 32 && KP != 64) || world < 1) { set_error("bnmtf_slot_layout: unsupported shape n=%d m=%d KP=%d world=%d (KP 32 or 64)", n, m, KP, world); return BNMTF_EINVAL; }
+  if (miss_ptr[0] != 0) { set_error("bnmtf_slot_layout: miss_ptr[0] must be 0"); return BNMTF_EINVAL; }
+  std::vector<MissingView> miss(n);
+  for (int u = 0; u < n; ++u) {
+    if (miss_ptr[u + 1] < miss_ptr[u] || miss_ptr[u + 1] - miss_ptr[u] > (uint32_t)m) { set_error("bnmtf_slot_layout: unit %d: bad list bounds", u); return BNMTF_EINVAL; }
+    if (miss_ptr[u + 1] > miss_ptr[u] && !miss_idx) { set_error("bnmtf_slot_layout: null argument"); return BNMTF_EINVAL; }
+    miss[u] = {miss_idx + miss_ptr[u], miss_ptr[u + 1] - miss_ptr[u]};
+    for (uint32_t e = 0; e < miss[u].count; ++e)
+      if (miss[u].idx[e] >= (uint32_t)m || (e && miss[u].idx[e] <= miss[u].idx[e - 1])) {
+        set_error("bnmtf_slot_layout: unit %d: the missing indices must ascend and lie below m=%d (entry %u is %u)", u, m, e, miss[u].idx[e]);
+        return BNMTF_EINVAL;
+      }
+  }
+  SlotLayoutInput in;
+  in.n = n; in.m = m; in.KP = KP; in.world = world; in.miss = miss.data(); in.sw = LayoutSwitches::from_env();
+  SlotLayout L;
+  build_slot_layout(in, L);
+  const int64_t scalars[BNMTF_SLOT_INFO_LEN] = {
+      L.mz, L.pw, L.nch, L.mh, L.pw_chunk, L.pw1, L.pair_ok, L.wide_can, L.use_wide, L.use_turns, L.use_twin, L.f_nw, L.vb_path, L.uw_ok, L.u_nw,
+      L.ho_ppb, L.stats_blocks, L.npairs, L.emax, (int64_t)L.slots, L.u_emax,
+      (int64_t)L.unit_map.size(), (int64_t)L.pair_E.size(), (int64_t)L.pair_base.size(), (int64_t)L.off.size(), (int64_t)L.off16.size(),
+      (int64_t)L.gen_units.size(), (int64_t)L.row_blk.size(), (int64_t)L.u_unit_map.size(), (int64_t)L.u_pair_E.size(),
+      (int64_t)L.u_pair_base.size(), (int64_t)L.u_off16.size()};
+  memcpy(info, scalars, sizeof(scalars));
+  auto put = [](auto* dst, const auto& src) { if (dst && !src.empty()) memcpy(dst, src.data(), src.size() * sizeof(src[0])); };
+  put(unit_map, L.unit_map); put(pair_E, L.pair_E); put(pair_base, L.pair_base); put(off, L.off); put(off16, L.off16); put(gen_units, L.gen_units);
+  put(row_blk, L.row_blk); put(u_unit_map, L.u_unit_map); put(u_pair_E, L.u_pair_E); put(u_pair_base, L.u_pair_base); put(u_off16, L.u_off16);
+  return BNMTF_OK;
+} BNMTF_ABI_GUARD
+
 int bnmtf_create(const bnmtf_problem* p, bnmtf_handle* out) try {
   *out = nullptr;
   if (!p || !p->R || !p->M || !p->lambda_rows || !p->lambda_cols) { set_error("bnmtf_create: null argument"); return BNMTF_EINVAL; }
@@ -1241,44 +1015,41 @@ static int build_standard(bnmtf_model* h, const double* lambda_S, const uint8_t*
   const auto t_create0 = std::chrono::steady_clock::now();
   const int I = h->I, J = h->J;
   const int Wr = h->K, Wc = h->L > 0 ? h->L : h->K;
-  struct { int K, L, rank, world; const uint8_t* comm_id; const double* lambda_S; uint64_t seed; } pv{h->K, h->L, h->rank, h->world, comm_id, lambda_S, h->seed};
-  auto* p = &pv;
-  auto fail = [&](int rc) { return rc; };
   CreateLaps laps;
   int rcode;
   const std::vector<uint32_t> rc = h->rows.obs_count, cc = h->cols.obs_count;
-  rcode = build_dir(h->rows, I, J, Wr, p->rank, p->world, h->lam_rows.data(), h->Rfull, h->Mtrain, I, J, true, rc, h->stream);
-  if (rcode) return fail(rcode);
-  rcode = build_dir(h->cols, J, I, Wc, p->rank, p->world, h->lam_cols.data(), h->Rfull, h->Mtrain, I, J, false, cc, h->stream);
-  if (rcode) return fail(rcode);
+  rcode = build_dir(h->rows, I, J, Wr, h->rank, h->world, h->lam_rows.data(), h->Rfull, h->Mtrain, I, J, true, rc, h->stream);
+  if (rcode) return rcode;
+  rcode = build_dir(h->cols, J, I, Wc, h->rank, h->world, h->lam_cols.data(), h->Rfull, h->Mtrain, I, J, false, cc, h->stream);
+  if (rcode) return rcode;
   laps.lap("both directions built (total)");
   h->rows.obs_count = rc; h->cols.obs_count = cc;
-  if ((rcode = alloc_factor(h->rows, h->cols.inner_pad))) return fail(rcode);
-  if ((rcode = alloc_factor(h->cols, h->rows.inner_pad))) return fail(rcode);
+  if ((rcode = alloc_factor(h->rows, h->cols.inner_pad))) return rcode;
+  if ((rcode = alloc_factor(h->cols, h->rows.inner_pad))) return rcode;
 
   laps.lap("factor buffers");
-  if (!h->Ad && (rcode = dalloc(&h->Ad, (size_t)I * 64))) return fail(rcode);
-  if (!h->Bd && (rcode = dalloc(&h->Bd, (size_t)J * 64))) return fail(rcode);
-  if (p->L > 0 && (rcode = dalloc(&h->S, (size_t)p->K * p->L))) return fail(rcode);
-  if (p->L > 0 && (rcode = bnmtf_alloc_extras(h, p->lambda_S))) return fail(rcode);
+  if (!h->Ad && (rcode = dalloc(&h->Ad, (size_t)I * 64))) return rcode;
+  if (!h->Bd && (rcode = dalloc(&h->Bd, (size_t)J * 64))) return rcode;
+  if (h->L > 0 && (rcode = dalloc(&h->S, (size_t)h->K * h->L))) return rcode;
+  if (h->L > 0 && (rcode = bnmtf_alloc_extras(h, lambda_S))) return rcode;
 
-  if (p->world > 1) {
-    if ((rcode = comm_create(&h->comm, p->comm_id, p->rank, p->world, h->stream))) return fail(rcode);
+  if (h->world > 1) {
+    if ((rcode = comm_create(&h->comm, comm_id, h->rank, h->world, h->stream))) return rcode;
     // every rank must hold the same Philox key (same draws, same tau variates): compare through the communicator
-    const double mine[4] = {(double)(uint32_t)p->seed, (double)(uint32_t)(p->seed >> 32), -(double)(uint32_t)p->seed, -(double)(uint32_t)(p->seed >> 32)};
+    const double mine[4] = {(double)(uint32_t)h->seed, (double)(uint32_t)(h->seed >> 32), -(double)(uint32_t)h->seed, -(double)(uint32_t)(h->seed >> 32)};
     double got[4];
-    if (hipMemcpy(h->acc, mine, sizeof(mine), hipMemcpyHostToDevice) != hipSuccess) { set_error("seed check: copy failed"); return fail(BNMTF_EHIP); }
-    if ((rcode = comm_allreduce_max(h->comm, h->acc, 4, h->stream))) return fail(rcode);
-    if (hipStreamSynchronize(h->stream) != hipSuccess || hipMemcpy(got, h->acc, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) { set_error("seed check: copy failed"); return fail(BNMTF_EHIP); }
+    if (hipMemcpy(h->acc, mine, sizeof(mine), hipMemcpyHostToDevice) != hipSuccess) { set_error("seed check: copy failed"); return BNMTF_EHIP; }
+    if ((rcode = comm_allreduce_max(h->comm, h->acc, 4, h->stream))) return rcode;
+    if (hipStreamSynchronize(h->stream) != hipSuccess || hipMemcpy(got, h->acc, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) { set_error("seed check: copy failed"); return BNMTF_EHIP; }
     (void)hipMemset(h->acc, 0, 4 * sizeof(double));
     if (memcmp(mine, got, sizeof(mine)) != 0) {
-      set_error("bnmtf_create: the ranks were given different seeds (this rank %llu): a sharded model needs one shared seed", (unsigned long long)p->seed);
-      return fail(BNMTF_EINVAL);
+      set_error("bnmtf_create: the ranks were given different seeds (this rank %llu): a sharded model needs one shared seed", (unsigned long long)h->seed);
+      return BNMTF_EINVAL;
     }
   } else if (getenv("BNMTF_FORCE_COMM")) {     // test hook: run the RCCL exchange path with a 1-rank communicator
     uint8_t id[128];
-    if ((rcode = comm_unique_id(id))) return fail(rcode);
-    if ((rcode = comm_create(&h->comm, id, 0, 1, h->stream))) return fail(rcode);
+    if ((rcode = comm_unique_id(id))) return rcode;
+    if ((rcode = comm_create(&h->comm, id, 0, 1, h->stream))) return rcode;
   }
 
   // q hand-over tables (BNMF on one GPU, both directions on the 16-wave or the plain 8-wave kernel).  By default only for
@@ -1287,7 +1058,7 @@ static int build_standard(bnmtf_model* h, const double* lambda_S, const uint8_t*
   {
     const char* e = getenv("BNMTF_HANDOVER");
     auto blocks = [](const Dir& d) { return d.ho_ppb > 0 ? d.f_npairs / d.ho_ppb : 0; };
-    const bool want = p->L == 0 && !h->comm && (e ? atoi(e) != 0 : std::min(blocks(h->rows), blocks(h->cols)) >= 64);
+    const bool want = h->L == 0 && !h->comm && (e ? atoi(e) != 0 : std::min(blocks(h->rows), blocks(h->cols)) >= 64);
     const auto t_ho0 = std::chrono::steady_clock::now();
     if (want && build_handover(h, h->rows, h->cols) && build_handover(h, h->cols, h->rows)) h->rows.ho_ready = h->cols.ho_ready = h->ho_enabled = true;
     if (const char* r = getenv("BNMTF_HANDOVER_REFRESH")) h->ho_refresh = (uint64_t)std::max(1, atoi(r));
@@ -1300,14 +1071,12 @@ static int build_standard(bnmtf_model* h, const double* lambda_S, const uint8_t*
 }
 static void describe_model(bnmtf_model* h) {
   const int I = h->I, J = h->J;
-  struct { int K, L, rank, world; } pv{h->K, h->L, h->rank, h->world};
-  auto* p = &pv;
   const double n_obs = h->n_obs;
   char buf[1024];
   snprintf(buf, sizeof(buf),
            "I=%d J=%d K=%d L=%d rank=%d/%d rows[n=%d n_pad=%d split=%d ipw=%d inner_pad=%d nmiss=%zu nslots=%zu sweep_nw=%d turns=%d twin=%d handover=%d emax=%d generic_units=%d] "
            "cols[n=%d n_pad=%d split=%d ipw=%d inner_pad=%d nmiss=%zu nslots=%zu sweep_nw=%d turns=%d emax=%d generic_units=%d] n_obs=%.0f create_ms=%.0f",
-           I, J, p->K, p->L, p->rank, p->world, h->rows.n, h->rows.n_pad, h->rows.split, h->rows.ipw, h->rows.inner_pad,
+           I, J, h->K, h->L, h->rank, h->world, h->rows.n, h->rows.n_pad, h->rows.split, h->rows.ipw, h->rows.inner_pad,
            h->rows.nmiss, h->rows.nslots, h->rows.f_nw, (int)h->rows.use_turns, (int)h->rows.use_twin, (int)h->ho_enabled, h->rows.f_emax, h->rows.f_gen_count, h->cols.n, h->cols.n_pad, h->cols.split,
            h->cols.ipw, h->cols.inner_pad, h->cols.nmiss, h->cols.nslots, h->cols.f_nw, (int)h->cols.use_turns, h->cols.f_emax, h->cols.f_gen_count, n_obs, h->create_ms);
   h->description = buf;

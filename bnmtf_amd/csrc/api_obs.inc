@@ -105,26 +105,18 @@ static int obs_lists(int I, int J, uint64_t n, const int32_t* rows, const int32_
   return BNMTF_OK;
 }
 
-template <typename T>
-static int obs_upload(T** dst, const std::vector<T>& src, hipStream_t st) {
-  CHK(dalloc(dst, src.size(), false));
-  if (!src.empty()) HIPCHK(hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));            // (src is the caller's local)
-  return BNMTF_OK;
-}
-
 static int obs_build_dir(bnmtf_model* h, ObsList& d, int n, const std::vector<uint32_t>& ptr, const std::vector<uint32_t>& idx,
                          const std::vector<float>& val, const double* lambda) {
   ObsState* s = h->obs;
   const int K = h->K, KP = s->KP;
   d.n = n; d.ldT = round_up(n + 1, 64);          // (a zero behind every column of XT: the sweep's empty slots gather it)
-  CHK(obs_upload(&d.ptr, ptr, h->stream));
-  CHK(obs_upload(&d.idx, idx, h->stream));
-  CHK(obs_upload(&d.val, val, h->stream));
+  CHK(upload(&d.ptr, ptr, h->stream));
+  CHK(upload(&d.idx, idx, h->stream));
+  CHK(upload(&d.val, val, h->stream));
   std::vector<float> lam((size_t)n * KP, 0.f);
   for (int u = 0; u < n; ++u)
     for (int k = 0; k < K; ++k) lam[(size_t)u * KP + k] = (float)lambda[(size_t)u * K + k];
-  CHK(obs_upload(&d.lambda, lam, h->stream));
+  CHK(upload(&d.lambda, lam, h->stream));
   CHK(dalloc(&d.X, (size_t)n * KP));
   CHK(dalloc(&d.XT, (size_t)K * d.ldT));
   CHK(dalloc(&d.numer, (size_t)n, false));

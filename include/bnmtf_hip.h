@@ -88,6 +88,23 @@ BNMTF_API int bnmtf_comm_unique_id(uint8_t out[128]);
 BNMTF_API int bnmtf_create(const bnmtf_problem* p, bnmtf_handle* out);
 BNMTF_API int bnmtf_destroy(bnmtf_handle h);
 BNMTF_API int bnmtf_sync(bnmtf_handle h);
+/* A TEST HOOK, not an interface to build on (it changes with the handle's layout): the host half of bnmtf_create's work on one
+ * direction -- the slot layout of the on-chip sweeps and the choice of their block shape (csrc/slot_layout.hip) -- on its own, so
+ * that the tables every sweep kernel gathers through can be tested without a GPU (tests/test_slot_layout_cpu.py).  No handle, no
+ * device call; deterministic, with the BNMTF_* layout switches of the environment applied as bnmtf_create applies them.
+ * n local units of inner extent m, KP = 32 or 64 (the factor width's padding), world ranks; unit u's missing inner indices,
+ * ascending, are miss_idx[miss_ptr[u] .. miss_ptr[u + 1]) (miss_ptr [n + 1]).
+ * info [BNMTF_SLOT_INFO_LEN]: mz, pw, nch, mh, pw_chunk, pw1, pair_ok, wide_can, use_wide, use_turns, use_twin, f_nw, vb_path,
+ * uw_ok, u_nw, ho_ppb, stats_blocks, npairs, emax, slots, u_emax, then the element counts of the eleven tables in argument
+ * order.  A table is copied where its pointer is not NULL: a first call with NULL tables gives the sizes, a second one fills
+ * the caller's buffers.  unit_map [2 npairs], pair_E / pair_base [npairs], off [max(slots, 1)][64], off16
+ * [max(slots / 2, 1)][64], gen_units (the units left to the generic kernel), row_blk [max(slots, 1)] when ho_ppb > 0, else
+ * empty; the unit-per-wave tables u_* when uw_ok, else empty. */
+#define BNMTF_SLOT_INFO_LEN 32
+BNMTF_API int bnmtf_slot_layout(int n, int m, int KP, int world, const uint32_t* miss_ptr, const uint32_t* miss_idx, int64_t* info,
+                                int32_t* unit_map, uint32_t* pair_E, uint32_t* pair_base, uint32_t* off, uint32_t* off16,
+                                int32_t* gen_units, uint16_t* row_blk, int32_t* u_unit_map, uint32_t* u_pair_E,
+                                uint32_t* u_pair_base, uint32_t* u_off16);
 
 /* size_Omega and the per-row / per-column observed counts (bit-exact integers;
  * size_Omega = M.sum(), bnmf_gibbs_optimised.py:65; counts :83-84).

@@ -1,7 +1,7 @@
 // Test infrastructure (CPU box only): drives the C ABI of the library's HOST side, linked against hip_stub.cpp instead of the
 // HIP runtime, under AddressSanitizer + UBSan (`make asan`) or ThreadSanitizer (`make tsan`).  Kernels do not run, so no number
 // that comes back means anything; what is checked is the host code the calls go through: bnmtf_create's layout passes (worker
-// threads, slot tables, shard ranges, the hand-over table sizes), the arenas and pools of created / destroyed models, every
+// threads, slot tables -- also on their own, from a real mask --, shard ranges, the hand-over table sizes), the arenas and pools of created / destroyed models, every
 // host<->"device" copy's extent (device memory is heap memory here), the sample ring of run(), run_many's batching and lock-step walks, and the
 // in-process multi-rank rendezvous of comm.hip with one host thread per rank.
 #include <cstdio>
@@ -93,6 +93,30 @@ static void bnmf_round_trip(const Data& d, int K, int iters, bool samples) {
   char buf[2048];
   OK(bnmtf_describe(h, buf, sizeof buf));
   OK(bnmtf_destroy(h));
+}
+
+// the slot layout's host half on its own (bnmtf_slot_layout; csrc/slot_layout.hip) on a REAL random mask -- under the stub no kernel
+// runs, so the lists bnmtf_create "downloads" are whatever the heap held --: balancing, parking and the threaded fills, into
+// buffers of exactly the sizes the first call reports
+static void slot_layout_walk(int n, int m, int KP, double missing, unsigned seed) {
+  std::mt19937 g(seed);
+  std::uniform_real_distribution<double> p(0.0, 1.0);
+  std::vector<uint32_t> ptr(n + 1, 0), idx;
+  for (int u = 0; u < n; ++u) {
+    const double frac = missing * 2.0 * p(g);                   // ragged: several slot classes, over-full residue classes
+    for (int j = 0; j < m; ++j) if (p(g) < frac) idx.push_back((uint32_t)j);
+    ptr[u + 1] = (uint32_t)idx.size();
+  }
+  int64_t info[BNMTF_SLOT_INFO_LEN], again[BNMTF_SLOT_INFO_LEN];
+  OK(bnmtf_slot_layout(n, m, KP, 1, ptr.data(), idx.data(), info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+  const int64_t* sz = info + BNMTF_SLOT_INFO_LEN - 11;
+  std::vector<int32_t> unit_map(sz[0]), gen(sz[5]), u_unit_map(sz[7]);
+  std::vector<uint32_t> pair_E(sz[1]), pair_base(sz[2]), off(sz[3]), off16(sz[4]), u_pair_E(sz[8]), u_pair_base(sz[9]), u_off16(sz[10]);
+  std::vector<uint16_t> row_blk(sz[6]);
+  OK(bnmtf_slot_layout(n, m, KP, 1, ptr.data(), idx.data(), again, unit_map.data(), pair_E.data(), pair_base.data(), off.data(), off16.data(), gen.data(),
+                       row_blk.data(), u_unit_map.data(), u_pair_E.data(), u_pair_base.data(), u_off16.data()));
+  if (memcmp(info, again, sizeof info) != 0) { fprintf(stderr, "slot layout: two calls, two answers\n"); exit(2); }
+  EXPECT_ERR(bnmtf_slot_layout(n, m, 48, 1, ptr.data(), idx.data(), info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
 }
 
 // a C++ exception inside an entry point comes back as a status with its message; the handle is still good afterwards
@@ -411,6 +435,8 @@ int main(int argc, char** argv) {
   tri_vb_round_trip(make_data(90, 70, 0.1, 15), 4, 5, 3);
   tri_vb_round_trip(make_data(1200, 1100, 0.1, 16), 12, 9, 2);         // the on-chip F / G sweeps' host side, the blocked chain's (K L >= 64)
   batches();
+  slot_layout_walk(37, 77, 32, 0.3, 41);
+  slot_layout_walk(900, 700, 64, 0.3, 42);                               // enough units for the helper threads of the layout passes
   exception_stays_inside(make_data(515, 389, 0.12, 27), 24);
   vb_many(make_data(300, 120, 0.15, 21), make_data(210, 150, 0.1, 22), 12, "vb_many");
   tri_vb_many(make_data(300, 120, 0.15, 31), make_data(210, 150, 0.1, 32), true, "tri_vb_many");

@@ -1,6 +1,6 @@
 """Host-side limits the library must survive without taking the process down.
 
-bnmtf_create forms its O(I J) layouts with helper threads (csrc/api.hip: parallel_chunks).  When no thread can be had -- the user's
+bnmtf_create forms its O(I J) layouts with helper threads (csrc/slot_layout.h: parallel_chunks).  When no thread can be had -- the user's
 process limit, a container's pids limit in a long session with worker pools and three ranks building at once -- std::thread
 throws; that exception used to cross the C ABI: std::terminate, 'Fatal Python error: Aborted' (seen once in a whole-suite run,
 profiles/r06e_gpu_suite.txt).  Now whoever is there does the chunks.  The probe runs in a child process: it lowers ITS limit."""
