@@ -225,8 +225,8 @@ class DeviceModel(HeldoutMixin):
         return int(tot.value), row, col
 
     def describe(self):
-        buf = C.create_string_buffer(1024)
-        _lib.check(_lib.lib().bnmtf_describe(self._handle(), buf, 1024))
+        buf = C.create_string_buffer(2048)
+        _lib.check(_lib.lib().bnmtf_describe(self._handle(), buf, 2048))
         return buf.value.decode()
 
     def set_profiling(self, enable=True, kernel=None, every=1):

@@ -255,6 +255,20 @@ class bnmf_vb_optimised(DeviceModel):
         _lib.check(_lib.lib().bnmf_vb_masked_sums(self._handle(), int(which), asq.ctypes.data, vsq.ctypes.data))
         return asq, vsq
 
+    def column_maxima(self, which):
+        """Hook (tests), read-only: the column maxima of [S2 | exp^2] of U (which = 0) or V (which = 1) -- the fixed-point grid of the
+        masked product's digit planes -- as fp32 bit patterns: (posted, own, was_posted), [2][K] uint32 each (row 0: S2 = var + exp^2,
+        row 1: exp^2).  posted: what the factor's last relayout left; was_posted: whether the next on-chip half sweep takes them as
+        they are; own: a pass of the fall-back kernel over the factor."""
+        assert self._blocks is None, "column_maxima is a hook of the single-block model (K <= %d)" % BLOCK
+        self._push()
+        KP = 32 if self.K <= 32 else 64
+        posted = np.zeros(2 * KP, dtype=np.uint32); own = np.zeros(2 * KP, dtype=np.uint32)
+        flag = C.c_int(-1)
+        _lib.check(_lib.lib().bnmf_vb_column_maxima(self._handle(), int(which), posted.ctypes.data, own.ctypes.data, C.byref(flag)))
+        assert not posted.reshape(2, KP)[:, self.K:].any() and not own.reshape(2, KP)[:, self.K:].any(), "a padding column has a maximum"
+        return posted.reshape(2, KP)[:, :self.K].copy(), own.reshape(2, KP)[:, :self.K].copy(), bool(flag.value)
+
     def exp_square_diff(self):
         """:185-187 (fp64 on the device)."""
         for n in ("muU", "tauU", "muV", "tauV"):          # the test-suite sets exp/var only

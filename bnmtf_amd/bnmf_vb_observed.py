@@ -97,6 +97,9 @@ class bnmf_vb_observed(bnmf_vb_optimised):
     def masked_sums(self, which):
         _observed.refuse(self, "masked_sums", "the sums over the missing entries belong to the dense layout's matrix-core product")
 
+    def column_maxima(self, which):
+        _observed.refuse(self, "column_maxima", "the fixed-point grid belongs to the dense layout's matrix-core product")
+
     def set_sweep_path(self, fast=True):
         _observed.refuse(self, "set_sweep_path", "it has one sweep kernel; BNMTF_OBS_LONG=1 forces its long form")
 

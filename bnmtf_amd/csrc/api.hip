@@ -1256,7 +1256,12 @@ int bnmtf_describe(bnmtf_handle h, char* buf, size_t buflen) try {
   // (+ the held-out mask's entries, bnmtf_set_heldout; a model of the one-launch kind runs the multi-launch path while it has one)
   char held[64] = "";
   if (h->held_n) snprintf(held, sizeof(held), " heldout=%zu%s", h->held_n, h->small ? " run_path=multi-launch" : "");
-  snprintf(buf, buflen, "%s%s%s%s", h->description.c_str(), kVbPath[h->last_vb_path & 3], kTriPath[h->last_tri_path & 3], held);
+  // (+ the masked product's inner slices and a slice's inner rows, per direction, once a variational model has built them:
+  // ensure_vb in api_models.inc, kernel_maskgemm.hip)
+  char mprod[96] = "";
+  if (h->vb_ready && h->rows.mslabs && h->cols.mslabs)
+    snprintf(mprod, sizeof(mprod), " masked_product[row_units=%d/%d col_units=%d/%d]", h->rows.msplit, h->rows.mipw, h->cols.msplit, h->cols.mipw);
+  snprintf(buf, buflen, "%s%s%s%s%s", h->description.c_str(), kVbPath[h->last_vb_path & 3], kTriPath[h->last_tri_path & 3], held, mprod);
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 

@@ -728,6 +728,33 @@ int bnmf_vb_masked_sums(bnmtf_handle h, int which, double* asq, double* vsq) try
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
+// Hook (tests), read-only: the column maxima of [S2 | E^2] of one FACTOR (which = 0: U, 1: V) -- the fixed-point grid of the
+// masked product's digit planes -- as the factor's last relayout left them (xb_umax, *was_posted = xb_umax_posted: gram_reduce_kernel's
+// maxima block) and by a pass of vb_colmax_kernel into a scratch buffer.  The model's maxima and their flag stay as they are; the
+// pass goes through launch_vb_planes, whose other outputs (the digit planes and their exponents) are derived data that every
+// product rebuilds ahead of its launch.
+int bnmf_vb_column_maxima(bnmtf_handle h, int which, uint32_t* posted, uint32_t* own, int* was_posted) try {
+  CHK(refuse_obs(h, "bnmf_vb_column_maxima"));
+  if (!h->vb_ready || !h->have_state) { set_error("no VB state set"); return BNMTF_ESTATE; }
+  if (which != 0 && which != 1) { set_error("which = 0 (the factor U) or 1 (V)"); return BNMTF_EINVAL; }
+  HIPCHK(hipSetDevice(h->device));
+  Dir& o = which == 0 ? h->rows : h->cols;
+  if (!(o.XB && o.xb_umax && o.xb_cexp)) { set_error("this model has no masked-sum operands (no mask on the device)"); return BNMTF_ESTATE; }
+  const size_t ncol = (size_t)2 * o.KP;
+  if (posted) HIPCHK(hipMemcpyAsync(posted, o.xb_umax, ncol * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  if (own) {
+    DevBuf<unsigned> scratch;
+    CHK(scratch.alloc(ncol));
+    launch_vb_planes(o.S2, o.X, o.nglob, o.xb_rows, o.KP, scratch.p, false, o.xb_cexp, o.XB, h->stream);
+    HIPCHK(hipMemcpyAsync(own, scratch.p, ncol * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));            // (before the scratch buffer goes)
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipGetLastError());
+  if (was_posted) *was_posted = o.xb_umax_posted ? 1 : 0;
+  return BNMTF_OK;
+} BNMTF_ABI_GUARD
+
 // One variational iteration (bnmf_vb_optimised.py:121-153 + :181-187) of a model on h->stream -- or, while a Recorder is installed
 // (many.h; api_many.inc: the caller has checked vb_batchable), into its records: `recording` leaves the record's index to the
 // list-form end-of-iteration kernel.

@@ -243,6 +243,12 @@ BNMTF_API int bnmf_vb_exp_square_diff(bnmtf_handle h, double* out);
  *   vsq[u][k] = sum_{r: M = 0} expO[r][k]^2                     (the unit's own term of the numerator of muU)
  * for the rank's local units, [n][K] doubles each. */
 BNMTF_API int bnmf_vb_masked_sums(bnmtf_handle h, int which, double* asq, double* vsq);
+/* Hook (tests), read-only: the column maxima of [S2 | E^2] of the factor U (which = 0) or V (which = 1) that fix the fixed-point
+ * grid of the masked product's digit planes, as fp32 bit patterns, 2 KP words each (KP = 32 for K <= 32, else 64; columns
+ * [0, K) of S2 = var + exp^2, then [KP, KP + K) of exp^2, padding columns zero): posted = what the factor's last relayout left
+ * (its Gram blocks see every row), *was_posted = 1 when the next on-chip half sweep would take them as they are; own = a pass of
+ * the fall-back kernel over the factor into a scratch buffer.  The model's state is left as it is.  Any pointer may be NULL. */
+BNMTF_API int bnmf_vb_column_maxima(bnmtf_handle h, int which, uint32_t* posted, uint32_t* own, int* was_posted);
 /* run(iterations) (:121-153).  exptau_out[n_iter] (all_exp_tau), perf_out[n_iter][3], times_out[n_iter],
  * elbo_terms_out[n_iter][10] = the O(I*J) / O((I+J)K) pieces of elbo() (:163-177) that live on the device:
  *   {exp_square_diff, beta_s,

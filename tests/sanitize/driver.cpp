@@ -346,6 +346,13 @@ static void column_blocks(const Data& d) {
   OK(bnmf_set_residual_data(b, &a, 1)); OK(bnmf_vb_half_sweep(b, 0)); OK(bnmf_vb_half_sweep(b, 1));
   double t2[2];
   OK(bnmf_vb_esd_terms(b, t2));
+  {   // the read-only hook on the column maxima of the masked product's grid: both factors, every pointer optional
+    uint32_t posted[128], own[128];
+    int was = -1;
+    OK(bnmf_vb_column_maxima(b, 0, posted, own, &was)); OK(bnmf_vb_column_maxima(a, 1, posted, own, &was));
+    OK(bnmf_vb_column_maxima(a, 0, nullptr, own, nullptr)); OK(bnmf_vb_column_maxima(a, 0, posted, nullptr, nullptr));
+    EXPECT_ERR(bnmf_vb_column_maxima(b, 2, posted, own, &was));
+  }
   OK(bnmtf_destroy(a)); OK(bnmtf_destroy(b));
 }
 

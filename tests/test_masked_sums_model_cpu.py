@@ -2,32 +2,11 @@
 bnmf_vb_optimised.py:189-199): per-column fixed-point grid, balanced base-256 digits, integer accumulation, one rounding at the
 end.  Checks the statements the kernel's header makes -- digit ranges (int8 operands), exact reconstruction, the accumulators'
 range (int32), the error bound against the fp64 sum -- without a GPU; tests/test_bnmf_vb_gpu.py holds the device against the
-same bound through bnmf_vb_masked_sums."""
+same bound through bnmf_vb_masked_sums, and tests/test_masked_product_exact_gpu.py to the bits of the model (planes, masked_sums and
+their slab-aware form: tests/_masked_product_cases.py)."""
 import numpy as np
 
-
-def planes(x):
-    """vb_colmax_kernel + vb_planes_kernel: x [rows][cols] non-negative fp32 -> (e[cols], d0, d1, d2 int8-range arrays)."""
-    x = np.asarray(x, dtype=np.float32)
-    mx = x.max(0)
-    bits = mx.view(np.uint32)
-    e = np.where(bits != 0, ((bits >> 23) & 255).astype(np.int64) - 126, 0)           # 2^e > max (exponent field + 1)
-    n = np.rint(np.ldexp(x.astype(np.float64), (22 - e)[None, :])).astype(np.int64)  # 0 .. 2^22 (ldexpf + v_cvt_i32_f32, RNE)
-    d2 = ((n + 128) & 255) - 128
-    n1 = (n - d2) >> 8
-    d1 = ((n1 + 128) & 255) - 128
-    d0 = (n1 - d1) >> 8
-    return e, d0, d1, d2, n
-
-
-def masked_sums(miss, x):
-    """maskgemm_kernel: integer sums per digit plane, combined as fmaf(d0, 65536, fmaf(d1, 256, d2)) in fp32, scaled by 2^(e - 22)."""
-    e, d0, d1, d2, _ = planes(x)
-    mi = miss.astype(np.int64)
-    D0, D1, D2 = mi @ d0, mi @ d1, mi @ d2
-    inner = (np.float32(256.0) * D1.astype(np.float32) + D2.astype(np.float32)).astype(np.float32)        # exact products, one rounding
-    tot = (D0.astype(np.float64) * 65536.0 + inner.astype(np.float64)).astype(np.float32)                  # the outer FMA: one rounding
-    return np.ldexp(tot.astype(np.float64), (e - 22)[None, :]).astype(np.float32), (D0, D1, D2)
+from _masked_product_cases import masked_sums, planes     # (the model, shared with the exact tests of the product: test_masked_product_*)
 
 
 def test_digit_planes_are_int8_and_exact():

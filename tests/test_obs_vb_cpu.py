@@ -96,7 +96,7 @@ def test_M_test_is_refused_before_any_device_call(no_device):
 
 def test_the_dense_layouts_hooks_and_switches_are_refused(no_device):
     m = _model()
-    for call, name in ((lambda: m.masked_sums(0), "masked_sums"), (lambda: m.set_sweep_path(False), "set_sweep_path"),
+    for call, name in ((lambda: m.masked_sums(0), "masked_sums"), (lambda: m.column_maxima(0), "column_maxima"), (lambda: m.set_sweep_path(False), "set_sweep_path"),
                        (lambda: m.set_small_path(False), "set_small_path"), (lambda: m.set_profiling(True), "set_profiling")):
         with pytest.raises(bnmtf_amd.BnmtfError) as e:
             call()
