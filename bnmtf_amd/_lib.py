@@ -122,6 +122,12 @@ _SIGS = {
     "bnmf_vbo_run": ([_P, C.c_int, _P, _P, _P, _P], C.c_int),
     "bnmf_vbo_update": ([_P, C.c_int, C.c_int, C.c_int], C.c_int),
     "bnmf_vbo_exp_square_diff": ([_P, C.POINTER(C.c_double)], C.c_int),
+    "bnmtf_otri_create": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, _P, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_uint64, C.c_int, C.POINTER(_P)], C.c_int),
+    "bnmtf_otri_set_state": ([_P, _P, _P, _P, C.c_double], C.c_int),
+    "bnmtf_otri_get_state": ([_P, _P, _P, _P, C.POINTER(C.c_double)], C.c_int),
+    "bnmtf_otri_run": ([_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P], C.c_int),
+    "bnmtf_otri_cond_params": ([_P, C.c_int, C.c_int, C.c_int, _P, _P], C.c_int),
+    "bnmtf_otri_metric_sums": ([_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 

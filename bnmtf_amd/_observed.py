@@ -1,9 +1,9 @@
-"""layout='observed' of bnmf_gibbs_optimised / nmf_icm, and bnmf_vb_observed: the host side of the observed-entry layout
-(DESIGN.md section 2.7).
+"""layout='observed' of bnmf_gibbs_optimised / nmf_icm and of bnmtf_gibbs_optimised / nmtf_icm, and bnmf_vb_observed: the host
+side of the observed-entry layout.
 
 The device keeps the residual R_ij - U_i.V_j on the OBSERVED entries (csrc/kernel_obs.hip, kernel_obs_vb.hip), so cost and device memory follow the
 number of observed entries: the layout for matrices that are mostly missing.  R and M stay dense NumPy arrays at the Python
-boundary; this module turns the mask into the entry lists the library takes, owns the bnmtf_obs_create handle of a model and
+boundary; this module turns the mask into the entry lists the library takes, owns the bnmtf_obs_create / bnmtf_otri_create handle of a model and
 states what the layout does not run."""
 import ctypes as C
 
@@ -13,6 +13,7 @@ from . import _lib
 
 LAYOUTS = ('dense', 'observed')
 MAX_RANK = 256          # BNMTF_OBS_MAX_RANK: nothing ties a rank to a lane, one handle takes them all
+MAX_RANK_TRI = 32       # BNMTF_OTRI_MAX_RANK: the tri-factorisation's S step is the dense K.L x K.L system, one 32 x 32 tile per column Gram
 
 
 def check_layout(layout):
@@ -28,6 +29,17 @@ def check_constructor(model, world):
     if not (1 <= int(model.K) <= MAX_RANK):
         raise _lib.BnmtfError("%s: K = %s is outside what layout='observed' runs (1 <= K <= %d on one handle; DESIGN.md section 2.7, limits)"
                               % (type(model).__name__, model.K, MAX_RANK))
+    if world != 1:
+        refuse(model, "world = %s" % world, "the observed-entry layout runs on one GPU: world = 1")
+
+
+def check_constructor_tri(model, world):
+    """The same for the tri-factorisation: K and L within the dense S system's one tile per Gram (no blocks of S on this layout)."""
+    for name, v in (("K", model.K), ("L", model.L)):
+        if not (1 <= int(v) <= MAX_RANK_TRI):
+            raise _lib.BnmtfError("%s: %s = %s is outside what layout='observed' runs (1 <= K, L <= %d: the S step is the dense K.L x K.L "
+                                  "system, one 32 x 32 tile per column Gram, and this layout has no blocks of S; DESIGN.md section 2.7, limits)"
+                                  % (type(model).__name__, name, v, MAX_RANK_TRI))
     if world != 1:
         refuse(model, "world = %s" % world, "the observed-entry layout runs on one GPU: world = 1")
 
@@ -68,16 +80,48 @@ def create_handle(model):
     return h
 
 
+def create_tri_handle(model):
+    """The bnmtf_otri_create handle of a tri-factorisation (its R, M, priors, seed, device)."""
+    Mb = model.M != 0
+    assert (model.M == Mb).all(), "The indicator matrix M must contain only 0 and 1."
+    rows, cols, vals = entry_list(model.R, Mb)
+    model._train_list = (rows, cols, vals)
+    lf, ls, lg = _lib.f64(model.lambdaF), _lib.f64(model.lambdaS), _lib.f64(model.lambdaG)
+    h = C.c_void_p()
+    _lib.check(_lib.lib().bnmtf_otri_create(int(model.I), int(model.J), int(model.K), int(model.L), C.c_uint64(len(rows)), _lib.ptr(rows),
+                                            _lib.ptr(cols), _lib.ptr(vals), _lib.ptr(lf), _lib.ptr(ls), _lib.ptr(lg), float(model.alpha),
+                                            float(model.beta), C.c_uint64(model._seed & (2 ** 64 - 1)), int(model._device), C.byref(h)))
+    return h
+
+
+def _pred_list(model, M_pred):
+    """The entry list of M_pred (None: the training entries) for the metric calls."""
+    if M_pred is None:
+        return model._train_list
+    Mp = np.asarray(M_pred)
+    assert ((Mp == 0) | (Mp == 1)).all(), "The indicator matrix M_pred must contain only 0 and 1."
+    assert Mp.shape == model.R.shape, "Input matrix R is not of the same size as the indicator matrix M_pred: %s and %s respectively." % (model.R.shape, Mp.shape)
+    return entry_list(model.R, Mp)
+
+
+def tri_metric_sums(model, M_pred, F, S, G):
+    """The six sums of metrics_from_sums of (F.S).G^T over the entries of M_pred (None: the training entries): F.S and the dot
+    products in fp64 (bnmtf_otri_metric_sums), never the sweeps' fp32 effective factor."""
+    h = model._handle()
+    rows, cols, vals = _pred_list(model, M_pred)
+    out = np.zeros(6)
+    if len(rows) == 0:                      # (an empty mask: the dense layout's sums of nothing)
+        return out
+    F, S, G = _lib.f64(F), _lib.f64(S), _lib.f64(G)
+    _lib.check(_lib.lib().bnmtf_otri_metric_sums(h, C.c_uint64(len(rows)), _lib.ptr(rows), _lib.ptr(cols), _lib.ptr(vals), _lib.ptr(F), _lib.ptr(S),
+                                                 _lib.ptr(G), _lib.ptr(out)))
+    return out
+
+
 def metric_sums(model, M_pred, A, B):
     """The six sums of metrics_from_sums of A.B^T over the entries of M_pred (None: the training entries), on the device in fp64."""
     h = model._handle()
-    if M_pred is None:
-        rows, cols, vals = model._train_list
-    else:
-        Mp = np.asarray(M_pred)
-        assert ((Mp == 0) | (Mp == 1)).all(), "The indicator matrix M_pred must contain only 0 and 1."
-        assert Mp.shape == model.R.shape, "Input matrix R is not of the same size as the indicator matrix M_pred: %s and %s respectively." % (model.R.shape, Mp.shape)
-        rows, cols, vals = entry_list(model.R, Mp)
+    rows, cols, vals = _pred_list(model, M_pred)
     out = np.zeros(6)
     if len(rows) == 0:                      # (an empty mask: the dense layout's sums of nothing)
         return out

@@ -4,13 +4,17 @@ for Bayesian non-negative matrix tri-factorisation R ~ F.S.G^T on an MI355X.
     BNMTF = bnmtf_gibbs_optimised(R, M, K, L, priors)
     BNMTF.initialise(init_S, init_FG)      # init_S: 'random'|'exp'; init_FG: 'random'|'exp'|'kmeans'
     BNMTF.run(iterations)                  # -> (all_F, all_S, all_G, all_tau)
+
+layout='observed' (keyword only, default 'dense') keeps the per-entry state on the OBSERVED entries (DESIGN.md section 2.7;
+_observed.py): cost and device memory follow the number of observed entries, the layout for matrices that are mostly missing.
+Same update order and Philox keying, so the same seed gives the dense layout's chain up to fp32 rounding.  K, L <= 32, one GPU.
 """
 import ctypes as C
 import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _observed
 from ._base import DeviceModel, broadcast_lambda, check_rank, check_R_M, metrics_from_sums
 from .kmeans import KMeans
 from ._blocked import BLOCK, MAX_BLOCKS, TriBlocks
@@ -19,13 +23,18 @@ MAX_RANK_BLOCKED = BLOCK * MAX_BLOCKS      # 256: K or L above 64 run as blocks 
 
 
 class bnmtf_gibbs_optimised(DeviceModel):
-    def __init__(self, R, M, K, L, priors, *, seed=None, device=0, verbose=True, rank=0, world=1, comm_id=None):
+    def __init__(self, R, M, K, L, priors, *, seed=None, device=0, verbose=True, rank=0, world=1, comm_id=None, layout='dense'):
+        _observed.check_layout(layout)
+        self._layout = layout
         self.R = np.array(R, dtype=float)
         self.M = np.array(M, dtype=float)
         self.K = K
         self.L = L
         check_R_M(self.R, self.M)
-        check_rank("bnmtf_gibbs_optimised", MAX_RANK_BLOCKED, K=self.K, L=self.L)
+        if layout == 'observed':
+            _observed.check_constructor_tri(self, world)
+        else:
+            check_rank("bnmtf_gibbs_optimised", MAX_RANK_BLOCKED, K=self.K, L=self.L)
         (self.I, self.J) = self.R.shape
         self.size_Omega = self.M.sum()
         self.alpha, self.beta = float(priors['alpha']), float(priors['beta'])
@@ -53,6 +62,12 @@ class bnmtf_gibbs_optimised(DeviceModel):
         if getattr(self, "_blocks", None) is not None:       # shape-only entry points (omega_counts, ...): the first F block's handle
             self._blocks._prepare()
             return self._blocks.Fch[0]._handle()
+        if self._layout == 'observed':
+            if self._h is None:
+                if self._seed is None:      # follow NumPy's global seeding like the reference's samplers do
+                    self._seed = int(np.random.randint(0, 2 ** 62))
+                self._h = _observed.create_tri_handle(self)
+            return self._h
         return super(bnmtf_gibbs_optimised, self)._handle()
 
     def describe(self):
@@ -102,12 +117,13 @@ class bnmtf_gibbs_optimised(DeviceModel):
                 and np.array_equal(self.S, held[2]) and np.array_equal(self.G, held[3])):
             return
         self._device_state = None
-        _lib.check(_lib.lib().bnmtf_set_state(self._handle(), _lib.ptr(_lib.f64(self.F)), _lib.ptr(_lib.f64(self.S)),
-                                              _lib.ptr(_lib.f64(self.G)), tau))
+        set_state = _lib.lib().bnmtf_otri_set_state if self._layout == 'observed' else _lib.lib().bnmtf_set_state
+        _lib.check(set_state(self._handle(), _lib.ptr(_lib.f64(self.F)), _lib.ptr(_lib.f64(self.S)), _lib.ptr(_lib.f64(self.G)), tau))
 
     def _pull(self):
         F = np.zeros((self.I, self.K)); S = np.zeros((self.K, self.L)); G = np.zeros((self.J, self.L)); tau = C.c_double()
-        _lib.check(_lib.lib().bnmtf_get_state(self._handle(), _lib.ptr(F), _lib.ptr(S), _lib.ptr(G), C.byref(tau)))
+        get_state = _lib.lib().bnmtf_otri_get_state if self._layout == 'observed' else _lib.lib().bnmtf_get_state
+        _lib.check(get_state(self._handle(), _lib.ptr(F), _lib.ptr(S), _lib.ptr(G), C.byref(tau)))
         self.F, self.S, self.G, self.tau = F, S, G, tau.value
         self._device_state = (self._h, F.copy(), S.copy(), G.copy(), tau.value)
 
@@ -116,6 +132,9 @@ class bnmtf_gibbs_optimised(DeviceModel):
         M_test (a 0/1 matrix shaped like R; it may overlap M): the held-out MSE / R^2 / Rp of the state
         every iteration ends with are computed on the device and kept in all_performances_test; without it no
         such attribute exists after the call."""
+        if self._layout == 'observed':
+            bufs = self._run_observed(iterations, _lib.UPDATE_MODE if update == 'mode' else _lib.UPDATE_DRAW, store_samples, expectation, M_test)
+            return self._run_finish(bufs, store_samples)
         Mt = self._check_heldout(M_test)
         if self._blocks is not None:
             return self._run_blocked(iterations, _lib.UPDATE_MODE if update == 'mode' else _lib.UPDATE_DRAW, store_samples, expectation)
@@ -126,6 +145,51 @@ class bnmtf_gibbs_optimised(DeviceModel):
                                               _lib.ptr(F_out), _lib.ptr(S_out), _lib.ptr(G_out), _lib.ptr(taus), _lib.ptr(perf), _lib.ptr(times)))
         self._finish_heldout(it)
         return self._run_finish(bufs, store_samples)
+
+    def _run_observed(self, iterations, update, store_samples, expectation, M_test):
+        """run() with layout='observed': one device call (bnmtf_otri_run) runs all iterations -- per iteration the F half sweep
+        against G.S^T, the dense S system from the column list, the G half sweep against F.S and the end-of-iteration kernel;
+        samples, tau, metrics and times come back as from bnmtf_gibbs_run."""
+        if M_test is not None:
+            _observed.refuse(self, "run(M_test=)", "held-out curves are kept by the dense layout only; use predict(M_test) after the run")
+        if expectation is not None:
+            _observed.refuse(self, "run(expectation=)", "the posterior sums on the device belong to the dense layout; approx_expectation averages the stored samples")
+        it = int(iterations)
+        self._push()
+        self._dev_expect = None
+        keep = store_samples and update != _lib.UPDATE_ICM
+        F_out = _lib.sample_buffer((it, self.I, self.K)) if keep else None
+        S_out = _lib.sample_buffer((it, self.K, self.L)) if keep else None
+        G_out = _lib.sample_buffer((it, self.J, self.L)) if keep else None
+        bufs = (it, F_out, S_out, G_out, np.zeros(it), np.zeros((it, 3)), np.zeros(it))
+        _lib.check(_lib.lib().bnmtf_otri_run(self._handle(), it, int(update), _lib.ptr(F_out), _lib.ptr(S_out), _lib.ptr(G_out),
+                                             _lib.ptr(bufs[4]), _lib.ptr(bufs[5]), _lib.ptr(bufs[6])))
+        return bufs
+
+    # the dense layout's switches and device facts: refused for the observed-entry layout before any device call
+    def set_sweep_path(self, fast=True):
+        if self._layout == 'observed':
+            _observed.refuse(self, "set_sweep_path", "it has one sweep kernel; BNMTF_OBS_LONG=1 forces its long form")
+        return super(bnmtf_gibbs_optimised, self).set_sweep_path(fast)
+
+    def set_small_path(self, on='auto'):
+        if self._layout == 'observed':
+            _observed.refuse(self, "set_small_path", "the one-launch path belongs to the dense layout")
+        return super(bnmtf_gibbs_optimised, self).set_small_path(on)
+
+    def set_profiling(self, enable=True, kernel=None, every=1):
+        if self._layout == 'observed':
+            _observed.refuse(self, "set_profiling", "the per-kernel event brackets belong to the dense layout")
+        return super(bnmtf_gibbs_optimised, self).set_profiling(enable, kernel, every)
+
+    def is_small(self):
+        return False if self._layout == 'observed' else super(bnmtf_gibbs_optimised, self).is_small()
+
+    def omega_counts(self):
+        if self._layout == 'observed':
+            Mb = self.M != 0
+            return int(Mb.sum()), Mb.sum(axis=1).astype(np.uint32), Mb.sum(axis=0).astype(np.uint32)
+        return super(bnmtf_gibbs_optimised, self).omega_counts()
 
     def _run_blocked(self, iterations, update, store_samples, expectation, minimum_TN=0.0, icm=False):
         """run() of a model with K or L above 64 (_blocked.py: TriBlocks): tau by the update rule's own law -- a Gamma(alpha_s,
@@ -186,6 +250,8 @@ class bnmtf_gibbs_optimised(DeviceModel):
         return super(bnmtf_gibbs_optimised, self)._device_expectation(burn_in, thinning)
 
     def _metric_sums(self, M_pred, A, S, B):
+        if self._layout == 'observed':          # the list-metric kernel on (F.S, G), F.S formed in fp64: the host turns the mask into a list
+            return _observed.tri_metric_sums(self, M_pred, self.F if A is None else A, self.S if S is None else S, self.G if B is None else B)
         if self._blocks is not None:
             if M_pred is not None:
                 Mp_ = np.asarray(M_pred)
@@ -195,6 +261,8 @@ class bnmtf_gibbs_optimised(DeviceModel):
 
     # run() in two halves, so that bnmtf_amd.run_many can put many models' device part into one call
     def _run_prepare(self, iterations, store_samples, expectation):
+        if self._layout == 'observed':
+            _observed.refuse(self, "run_many", "batched launches take models of the dense layout")
         it = int(iterations)
         self._push()
         self._set_expectation(expectation, it)
@@ -230,7 +298,7 @@ class bnmtf_gibbs_optimised(DeviceModel):
 
     def beta_s(self):
         """:192-193."""
-        if self._blocks is not None:           # from the full-width masked SSE
+        if self._blocks is not None or self._layout == 'observed':           # from the full-width masked SSE
             s = self._metric_sums(None, self.F, self.S, self.G)
             return self.beta + 0.5 * (s[2] - 2.0 * s[5] + s[4])
         self._push()
@@ -243,7 +311,8 @@ class bnmtf_gibbs_optimised(DeviceModel):
             return self._blocks.cond(which, k, l, self.F, self.S, self.G, float(getattr(self, "tau", 1.0)))
         self._push()
         numer = np.zeros(n); tauk = np.zeros(n)
-        _lib.check(_lib.lib().bnmtf_cond_params(self._handle(), which, int(k), int(l), _lib.ptr(numer), _lib.ptr(tauk)))
+        cond_params = _lib.lib().bnmtf_otri_cond_params if self._layout == 'observed' else _lib.lib().bnmtf_cond_params
+        _lib.check(cond_params(self._handle(), which, int(k), int(l), _lib.ptr(numer), _lib.ptr(tauk)))
         return numer, tauk
 
     def tauF(self, k):

@@ -178,6 +178,7 @@ static void enqueue_s_prepare(bnmtf_model* h) {
 extern "C" {
 
 int bnmtf_set_state(bnmtf_handle h, const double* F, const double* S, const double* G, double tau) try {
+  CHK(refuse_obs(h, "bnmtf_set_state"));
   if (h->L == 0) { set_error("bnmtf_set_state on a BNMF handle"); return BNMTF_ESTATE; }
   HIPCHK(hipSetDevice(h->device));
   h->std_cur = false; h->small_cur = false;
@@ -199,6 +200,7 @@ int bnmtf_set_state(bnmtf_handle h, const double* F, const double* S, const doub
 } BNMTF_ABI_GUARD
 
 int bnmtf_get_state(bnmtf_handle h, double* F, double* S, double* G, double* tau) try {
+  CHK(refuse_obs(h, "bnmtf_get_state"));
   if (!h->have_state) { set_error("no state set"); return BNMTF_ESTATE; }
   HIPCHK(hipSetDevice(h->device));
   if (h->small && h->small_cur) CHK(small_download_state(h, F, G, S));
@@ -261,6 +263,7 @@ int bnmtf_cond_params(bnmtf_handle h, int which, int k, int l, double* numer_out
 // draws of its entries are keyed by their place in the wide S (L_wide columns), its S step runs row by row (bnmtf_s_rows), never
 // on the one-launch path or the dense system (whose candidate records are keyed by the handle's own K L).
 int bnmtf_set_s_block(bnmtf_handle h, int row0, int col0, int L_wide) try {
+  CHK(refuse_obs(h, "bnmtf_set_s_block"));
   if (h->L == 0 || h->comm) { set_error("bnmtf_set_s_block: BNMTF handles on one GPU"); return BNMTF_ESTATE; }
   if (row0 < 0 || col0 < 0 || L_wide < col0 + h->L) { set_error("bnmtf_set_s_block: the block does not lie inside a K x %d matrix", L_wide); return BNMTF_EINVAL; }
   h->s_word0 = (uint32_t)row0 * (uint32_t)L_wide + (uint32_t)col0;

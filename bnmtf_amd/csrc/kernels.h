@@ -636,4 +636,32 @@ void launch_obs_vb_sweep(const ObsVbSweepArgs& a, hipStream_t st);
 void launch_obs_vb_finish(const ObsVbFinishArgs& a, hipStream_t st);
 void launch_obs_vb_esd(const ObsVbEsdArgs& a, double* out, hipStream_t st);
 
+
+// ---------------------------------------------------------------------------
+// The tri-factorisation on the observed-entry layout (kernel_obs_tri.hip): the effective factors the two
+// half sweeps of obs_sweep_kernel run against, and the S system's per-column inputs from the column list; K, L <= 32, every
+// row-major factor [.][32]
+// ---------------------------------------------------------------------------
+constexpr int kObsTriStride = 32;      // row stride of F, G, both effective factors and Pv: what kernel_ssys.hip's launchers read
+struct ObsTriEffArgs {      // out = X . S (transposeS = 0: inner K, width L) or X . S^T (transposeS = 1: inner L, width K), row by row
+  const float* X; int n;             // [n][32], padding columns zero
+  const float* S; int K, L;          // [K][L] unpadded
+  int transposeS;
+  float* out;                        // [n][32], padding columns zero
+  float* outT; int ldT;              // [width][ldT], ldT > n: the words behind column n are never written (they stay zero)
+};
+struct ObsTriGramArgs {     // per column j of the column list: W_j = sum_{i in Omega_j} F_i F_i^T (packed), Pv_j = sum_{i in Omega_j} R_ij F_i
+  const uint32_t* ptr; const uint32_t* idx; const float* val;   // the column list: [n + 1], rows ascending within a column, values
+  int n, K;
+  const float* F;                    // [I][32]
+  float* Wc;                         // [n + 2][tri_padded(K)], tri_pos order (pads and the two extra rows are never written)
+  float* Pv;                         // [n][32]: the layout launch_ssys_b reads with split = 1, n_pad = n
+};
+constexpr int kObsTriGramWaves = 4;    // columns (waves) per block of the column-Gram kernel
+constexpr int kObsTriEffRows = 64;     // rows per block of the effective-factor kernel
+inline int obs_tri_gram_blocks(int n) { return (n + kObsTriGramWaves - 1) / kObsTriGramWaves; }
+inline int obs_tri_eff_blocks(int n) { return (n + kObsTriEffRows - 1) / kObsTriEffRows; }
+void launch_obs_tri_eff(const ObsTriEffArgs& a, hipStream_t st);
+void launch_obs_tri_gram(const ObsTriGramArgs& a, hipStream_t st);
+
 }  // namespace bnmtf

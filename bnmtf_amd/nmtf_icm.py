@@ -7,7 +7,7 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _observed
 from ._base import metrics_from_sums
 from .bnmtf_gibbs import bnmtf_gibbs_optimised
 from .nmf_icm import gamma_mode
@@ -21,6 +21,12 @@ class nmtf_icm(bnmtf_gibbs_optimised):
 
     def run(self, iterations, minimum_TN=0., *, M_test=None):
         """:132-173; returns None like the reference.  M_test: see nmf_icm.run."""
+        if self._layout == 'observed':          # (DESIGN.md section 2.7: the ICM rules on the observed-entry kernels)
+            if M_test is not None:
+                _observed.refuse(self, "run(M_test=)", "held-out curves are kept by the dense layout only; use predict(M_test) after the run")
+            _lib.check(_lib.lib().bnmtf_set_minimum_tn(self._handle(), float(minimum_TN)))
+            it, _, _, _, taus, perf, times = self._run_observed(iterations, _lib.UPDATE_ICM, False, None, None)
+            return self._finish_icm(it, taus, perf, times)
         Mt = self._check_heldout(M_test)
         it = int(iterations)
         if self._blocks is not None:           # K or L above 64: blocks (_blocked.py), the same updates with the Gamma mode for tau
@@ -33,6 +39,10 @@ class nmtf_icm(bnmtf_gibbs_optimised):
         _lib.check(L.bnmtf_set_minimum_tn(self._handle(), float(minimum_TN)))
         _lib.check(L.bnmtf_gibbs_run(self._handle(), it, _lib.UPDATE_ICM, None, None, None, _lib.ptr(taus), _lib.ptr(perf), _lib.ptr(times)))
         self._finish_heldout(it)
+        return self._finish_icm(it, taus, perf, times)
+
+    def _finish_icm(self, it, taus, perf, times):
+        """Behind the device call of run(), either layout: the point estimate and the per-iteration records."""
         self._pull()
         self.all_tau = taus
         self.all_times = list(times)

@@ -470,6 +470,33 @@ BNMTF_API int bnmf_vbo_update(bnmtf_handle h, int which, int k, int moments);
 /* exp_square_diff() of the state the device holds, fp64 over the observed entries */
 BNMTF_API int bnmf_vbo_exp_square_diff(bnmtf_handle h, double* out);
 
+/* ---- the tri-factorisation on the observed-entry layout (bnmtf_gibbs_optimised / nmtf_icm, layout='observed') ----
+ * A handle of its own kind again: the entry lists of bnmtf_obs_create (same arguments, same refusals), F [I][K], S [K][L] and
+ * G [J][L] in fp32, the two effective factors G S^T and F S, and the buffers of the dense K.L x K.L system of the S step; cost and
+ * memory are proportional to the number of observed entries and nothing of size I x J exists.  1 <= K, L <= BNMTF_OTRI_MAX_RANK (one
+ * 32 x 32 tile per column Gram), one GPU.  The iteration is bnmtf_gibbs_run's -- F columns, S row-major, G columns, tau -- with the
+ * same Philox keying, so the same seed gives the dense layout's chain up to fp32 rounding.  Such a handle takes the calls below,
+ * bnmtf_set_minimum_tn, bnmtf_set_iteration / bnmtf_get_iteration, bnmtf_sync, bnmtf_describe and bnmtf_destroy; every other call
+ * refuses it, and these refuse every other handle.  BNMTF_OBS_LONG=1 at creation: as for bnmtf_obs_create. */
+#define BNMTF_OTRI_MAX_RANK 32
+BNMTF_API int bnmtf_otri_create(int I, int J, int K, int L, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values,
+                      const double* lambda_F, const double* lambda_S, const double* lambda_G, double alpha, double beta,
+                      uint64_t seed, int device, bnmtf_handle* out);
+/* F [I][K], S [K][L], G [J][L], tau; get: any pointer may be null */
+BNMTF_API int bnmtf_otri_set_state(bnmtf_handle h, const double* F, const double* S, const double* G, double tau);
+BNMTF_API int bnmtf_otri_get_state(bnmtf_handle h, double* F, double* S, double* G, double* tau);
+/* run(n_iter) with the arguments of bnmtf_gibbs_run: update = BNMTF_UPDATE_*; F_out [n][I][K], S_out [n][K][L], G_out [n][J][L]
+ * (fp32 samples), tau_out [n], perf_out [n][3] (MSE, R^2, Rp on the observed entries), times_out [n]; any output may be null */
+BNMTF_API int bnmtf_otri_run(bnmtf_handle h, int n_iter, int update, float* F_out, float* S_out, float* G_out, double* tau_out,
+                   double* perf_out, double* times_out);
+/* as bnmtf_cond_params: which = 0: column k of F, numerator and precision for every row; 1: entry (k, l) of S, one value each;
+ * 2: column l of G, for every column of R.  The state is left as it is. */
+BNMTF_API int bnmtf_otri_cond_params(bnmtf_handle h, int which, int k, int l, double* numer_out, double* tau_out);
+/* the six sums of metrics_from_sums over a list of entries (any order; they need not be observed ones) with P = (F S)_i . G_j:
+ * F [I][K], S [K][L], G [J][L] in fp64, F S formed in fp64 too; fp64 throughout, fixed summation order */
+BNMTF_API int bnmtf_otri_metric_sums(bnmtf_handle h, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values,
+                           const double* F, const double* S, const double* G, double sums_out[6]);
+
 #ifdef __cplusplus
 }
 #endif
