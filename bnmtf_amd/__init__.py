@@ -9,10 +9,11 @@ from .bnmtf_gibbs import bnmtf_gibbs_optimised, bnmtf_gibbs
 from .bnmf_vb import bnmf_vb_optimised, bnmf_vb
 from .bnmf_vb_observed import bnmf_vb_observed
 from .bnmtf_vb import bnmtf_vb_optimised, bnmtf_vb
+from .bnmtf_vb_observed import bnmtf_vb_observed
 from .nmf_icm import nmf_icm
 from .nmtf_icm import nmtf_icm
 from .nmf_np import NMF
 from .nmtf_np import NMTF
 from .batch import run_many
 
-__all__ = ["bnmf_gibbs_optimised", "bnmf_gibbs", "bnmtf_gibbs_optimised", "bnmtf_gibbs", "bnmf_vb_optimised", "bnmf_vb", "bnmf_vb_observed", "bnmtf_vb_optimised", "bnmtf_vb", "nmf_icm", "nmtf_icm", "NMF", "NMTF", "run_many", "device_count", "BnmtfError", "lib", "LIB_PATH", "EXPORTS"]
+__all__ = ["bnmf_gibbs_optimised", "bnmf_gibbs", "bnmtf_gibbs_optimised", "bnmtf_gibbs", "bnmf_vb_optimised", "bnmf_vb", "bnmf_vb_observed", "bnmtf_vb_optimised", "bnmtf_vb", "bnmtf_vb_observed", "nmf_icm", "nmtf_icm", "NMF", "NMTF", "run_many", "device_count", "BnmtfError", "lib", "LIB_PATH", "EXPORTS"]

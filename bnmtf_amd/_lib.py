@@ -128,6 +128,11 @@ _SIGS = {
     "bnmtf_otri_run": ([_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P], C.c_int),
     "bnmtf_otri_cond_params": ([_P, C.c_int, C.c_int, C.c_int, _P, _P], C.c_int),
     "bnmtf_otri_metric_sums": ([_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "bnmtf_otvb_set_state": ([_P] * 13 + [C.c_double], C.c_int),
+    "bnmtf_otvb_get_state": ([_P] * 13, C.c_int),
+    "bnmtf_otvb_update": ([_P, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
+    "bnmtf_otvb_exp_square_diff": ([_P, C.POINTER(C.c_double)], C.c_int),
+    "bnmtf_otvb_run": ([_P, C.c_int, _P, _P, _P, _P, _P], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 

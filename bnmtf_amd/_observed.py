@@ -1,5 +1,5 @@
-"""layout='observed' of bnmf_gibbs_optimised / nmf_icm and of bnmtf_gibbs_optimised / nmtf_icm, and bnmf_vb_observed: the host
-side of the observed-entry layout.
+"""layout='observed' of bnmf_gibbs_optimised / nmf_icm and of bnmtf_gibbs_optimised / nmtf_icm, bnmf_vb_observed and
+bnmtf_vb_observed: the host side of the observed-entry layout.
 
 The device keeps the residual R_ij - U_i.V_j on the OBSERVED entries (csrc/kernel_obs.hip, kernel_obs_vb.hip), so cost and device memory follow the
 number of observed entries: the layout for matrices that are mostly missing.  R and M stay dense NumPy arrays at the Python

@@ -131,9 +131,13 @@ class bnmtf_vb_optimised(DeviceModel):
         self._push()
         self._set_heldout(Mt)
         exptau = np.zeros(it); perf = np.zeros((it, 3)); terms = np.zeros((it, 10)); times = np.zeros(it)
-        _lib.check(_lib.lib().bnmtf_vb_run(self._handle(), it, _lib.ptr(orders), _lib.ptr(exptau), _lib.ptr(perf), _lib.ptr(terms), _lib.ptr(times)))
+        self._run_device(it, orders, exptau, perf, terms, times)
         self._finish_heldout(it)
         self._run_finish(it, exptau, perf, terms, times)
+
+    def _run_device(self, it, orders, exptau, perf, terms, times):
+        """The device call of run() (bnmtf_vb_observed: the observed-entry layout's)."""
+        _lib.check(_lib.lib().bnmtf_vb_run(self._handle(), it, _lib.ptr(orders), _lib.ptr(exptau), _lib.ptr(perf), _lib.ptr(terms), _lib.ptr(times)))
 
     def _run_finish(self, it, exptau, perf, terms, times):
         """What run() does behind the device call (batch.run_many: behind the call that ran this model among others)."""

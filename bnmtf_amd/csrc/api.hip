@@ -1704,4 +1704,5 @@ int bnmtf_gamma_sample(double alpha, double beta, uint64_t seed, uint64_t it, in
 #include "api_np.inc"
 #include "api_obs.inc"
 #include "api_obs_tri.inc"
+#include "api_obs_trivb.inc"
 #include "api_many.inc"

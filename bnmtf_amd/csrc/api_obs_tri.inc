@@ -22,6 +22,12 @@ struct ObsTriState {
   double* scal = nullptr;          // tau_d, tau_f and out8 of the metric sums (one allocation)
   double* out8 = nullptr;
   bool force_long = false;
+  // the variational model on this handle (api_obs_trivb.inc): allocated by the first bnmtf_otvb_set_state.  q(F), q(G) live in
+  // rows / cols {mu, tauq, var} beside the expectation X; q(S) in the model's muS, tauS, varS beside S
+  bool vb_alloc = false, vb_state = false;   // the variational buffers exist; the handle holds the state of a bnmtf_otvb_set_state / run
+  float* ceffS2 = nullptr; float* ceffS2T = nullptr;    // second moment of G S^T: [J][32] and [K][cols.ldT]
+  float* reffS2 = nullptr; float* reffS2T = nullptr;    // second moment of F S:   [I][32] and [L][rows.ldT]
+  double* esd_part = nullptr;      // [obs_vb_esd_blocks(I)]
 };
 
 static void otri_free(bnmtf_model* h) {
@@ -29,7 +35,9 @@ static void otri_free(bnmtf_model* h) {
   if (!s) return;
   for (ObsList* d : {&s->rows, &s->cols}) {
     dfree(d->ptr); dfree(d->idx); dfree(d->val); dfree(d->X); dfree(d->XT); dfree(d->lambda); dfree(d->numer); dfree(d->taup);
+    dfree(d->mu); dfree(d->tauq); dfree(d->var); dfree(d->vstat);
   }
+  dfree(s->ceffS2); dfree(s->ceffS2T); dfree(s->reffS2); dfree(s->reffS2T); dfree(s->esd_part);
   dfree(s->ceffX); dfree(s->ceffXT); dfree(s->reffX); dfree(s->reffXT); dfree(s->Pv);
   dfree(s->escratch); dfree(s->part); dfree(s->scal);
   h->tau_d = nullptr; h->tau_f = nullptr;
@@ -40,6 +48,10 @@ static void otri_free(bnmtf_model* h) {
 static int otri_check(bnmtf_model* h, bool need_state) {
   if (!h || !h->otri) { set_error("not a handle of bnmtf_otri_create"); return BNMTF_EINVAL; }
   if (need_state && !h->have_state) { set_error("bnmtf_otri_set_state has not been called"); return BNMTF_ESTATE; }
+  if (need_state && h->otri->vb_state) {
+    set_error("the handle holds a variational state (bnmtf_otvb_set_state): it runs the bnmtf_otvb_* calls until bnmtf_otri_set_state replaces it");
+    return BNMTF_ESTATE;
+  }
   HIPCHK(hipSetDevice(h->device));
   return BNMTF_OK;
 }
@@ -215,6 +227,7 @@ int bnmtf_otri_set_state(bnmtf_handle h, const double* F, const double* S, const
   HIPCHK(hipStreamSynchronize(h->stream));
   CHK(set_tau(h, tau));
   h->have_state = true;
+  h->otri->vb_state = false;          // (the factors were replaced: a variational state ends here)
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 

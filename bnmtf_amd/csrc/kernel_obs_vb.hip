@@ -17,6 +17,9 @@
 // part of exp_square_diff over the observed entries.  A lane's columns in order, the butterfly, the block's waves in wave
 // order; obs_vb_finish_kernel folds the blocks' partials in obs_fold's order.  No floating-point atomics anywhere.
 //
+// obs_trivb_sweep_kernel: the same body with the tri-factorisation's covariance term and column order (template parameter COV;
+// bnmtf_vb_observed, api_obs_trivb.inc).  obs_vb_sweep_kernel is the COV = false instantiation and compiles to the code it had.
+//
 // obs_vb_esd_kernel: exp_square_diff of the state the device holds, fp64 over the row list (a block's rows b, b + grid, ...; a
 // thread's entries in list order; a tree; the fold).
 #include "obs_common.h"
@@ -31,7 +34,11 @@ constexpr int kVbSums = 10;            // quad, log erfc, log tau, lambda E, q2,
 
 // One unit.  S > 0: the register form with S slots per lane; S == 0: the long form.  xs / ls: the unit's expectations and prior
 // rates in LDS, pk: the parked column results.  sums (part != null): the lane's share of SSE, sum P, sum P^2, sum R P in sums[6 .. 9].
-template <int S>
+// COV: the tri-factorisation's F / G half sweep against an effective factor (bnmtf_vb_optimised.py:241-250 / :264-273): the columns in
+// the order handed over, and the numerator less  sum_t S(k,t) mv_t (fs_t - x_k S(k,t)),  lane t holding mv_t (the other factor's
+// variance summed over the unit's entries: fixed for the half sweep) and fs_t = sum_c x_c S(c,t) (from the unit's current row; one
+// fmaf per new expectation).  The term is the butterfly's sum, whatever the form: the forms still give the same bits.
+template <int S, bool COV>
 __device__ __forceinline__ void obs_vb_unit(const ObsVbSweepArgs& a, int u, int lane, float* xs, const float* ls, float* pk, double* sums) {
 #pragma clang fp contract(off)
   constexpr int SS = S > 0 ? S : 1;
@@ -60,7 +67,14 @@ __device__ __forceinline__ void obs_vb_unit(const ObsVbSweepArgs& a, int u, int 
   const float exptau = *a.tau;
   const int only = a.only_k;
   const int kbeg = only >= 0 ? only : 0, kend = only >= 0 ? only + 1 : K;
-  for (int k = kbeg; k < kend; ++k) {
+  float fs = 0.f, mvl = 0.f;
+  const bool cov_lane = COV && lane < a.cov_n;
+  if (COV) {
+    for (int c = 0; c < K; ++c) fs = fmaf(xs[c], cov_lane ? a.cov_S[c * a.cov_sc + lane * a.cov_st] : 0.f, fs);
+    mvl = cov_lane ? a.cov_mv[(size_t)u * 32 + lane] : 0.f;
+  }
+  for (int kk = kbeg; kk < kend; ++kk) {
+    const int k = (COV && a.order && only < 0) ? a.order[kk] : kk;
     const float* vcol = a.XoT + (size_t)k * a.ldT_o;
     const float* wcol = a.S2oT + (size_t)k * a.ldT_o;
     float se = 0.f, sb = 0.f, sa = 0.f;
@@ -73,7 +87,12 @@ __device__ __forceinline__ void obs_vb_unit(const ObsVbSweepArgs& a, int u, int 
     se = wave_sum(se); sb = wave_sum(sb); sa = wave_sum(sa);
     const float xk = xs[k];
     const float tau_p = exptau * sa;
-    const float numer = fmaf(exptau, fmaf(xk, sb, se), -ls[k]);
+    float sc = 0.f, cov = 0.f;
+    if (COV) {
+      sc = cov_lane ? a.cov_S[k * a.cov_sc + lane * a.cov_st] : 0.f;
+      cov = wave_sum(sc * mvl * fmaf(-xk, sc, fs));
+    }
+    const float numer = COV ? fmaf(exptau, fmaf(xk, sb, se) - cov, -ls[k]) : fmaf(exptau, fmaf(xk, sb, se), -ls[k]);
     const float mu = numer / tau_p;
     float ef = xk, vf = 0.f;
     if (only < 0 || a.moments) tn_moments_f32(mu, tau_p, &ef, &vf);
@@ -81,13 +100,17 @@ __device__ __forceinline__ void obs_vb_unit(const ObsVbSweepArgs& a, int u, int 
       if (lane == 0) {
         const size_t at = (size_t)u * KP + k;
         a.mu[at] = mu; a.tauq[at] = tau_p;
-        if (a.moments) { a.var[at] = vf; a.X[at] = ef; a.XT[(size_t)k * a.ldT + u] = ef; a.S2T[(size_t)k * a.ldT + u] = fmaf(ef, ef, vf); }
+        if (a.moments) {
+          a.var[at] = vf; a.X[at] = ef;
+          if (!COV) { a.XT[(size_t)k * a.ldT + u] = ef; a.S2T[(size_t)k * a.ldT + u] = fmaf(ef, ef, vf); }
+        }
       }
       return;
     }
     mus[k] = mu; tps[k] = tau_p; vrs[k] = vf; sas[k] = sa; sbs[k] = sb;      // (every lane stores the same value, and reads back its own store)
     xs[k] = ef;
     const float nd = xk - ef;                   // e -= (x' - x) v
+    if (COV) fs = fmaf(-nd, sc, fs);
     if (S > 0) {
 #pragma unroll
       for (int s = 0; s < SS; ++s) e[s] = fmaf(nd, v[s], e[s]);
@@ -120,6 +143,7 @@ __device__ __forceinline__ void obs_vb_unit(const ObsVbSweepArgs& a, int u, int 
 
 // The unit's new q -- row major, the expectation and S2 transposed -- and the fp64 pieces of the lane's columns, in column order.
 // One copy behind the forms, with none of their registers live.
+template <bool COV>
 __device__ __forceinline__ void obs_vb_pieces(const ObsVbSweepArgs& a, int u, int lane, const float* xs, const float* ls, const float* pk, double* sums) {
 #pragma clang fp contract(off)
   const int K = a.K, KP = a.KP;
@@ -130,8 +154,10 @@ __device__ __forceinline__ void obs_vb_pieces(const ObsVbSweepArgs& a, int u, in
     if (k < K) {
       const float ef = xs[k], vf = vrs[k], mu = mus[k], tau_p = tps[k];
       a.X[at] = ef; a.mu[at] = mu; a.tauq[at] = tau_p; a.var[at] = vf;
-      a.XT[(size_t)k * a.ldT + u] = ef;
-      a.S2T[(size_t)k * a.ldT + u] = fmaf(ef, ef, vf);
+      if (!COV) {
+        a.XT[(size_t)k * a.ldT + u] = ef;
+        a.S2T[(size_t)k * a.ldT + u] = fmaf(ef, ef, vf);
+      }
       // pieces of elbo() (bnmf_vb_optimised.py:163-177) and of exp_square_diff (:185-187) for this (unit, k)
       const double e_ = (double)ef, v_ = (double)vf, dm = e_ - (double)mu;
       quad += 0.5 * (double)tau_p * (v_ + dm * dm);
@@ -149,7 +175,8 @@ __device__ __forceinline__ void obs_vb_pieces(const ObsVbSweepArgs& a, int u, in
   sums[0] = quad; sums[1] = lerfc; sums[2] = ltau; sums[3] = lamx; sums[4] = q2; sums[5] = q3;
 }
 
-__global__ __launch_bounds__(kObsWaves * 64) void obs_vb_sweep_kernel(ObsVbSweepArgs a) {
+template <bool COV>
+__device__ __forceinline__ void obs_vb_sweep_body(const ObsVbSweepArgs& a) {
   __shared__ float xsh[kObsWaves][kObsMaxRank];
   __shared__ float lsh[kObsWaves][kObsMaxRank];
   __shared__ float pkh[kObsWaves][kVbParked * kObsMaxRank];
@@ -170,12 +197,12 @@ __global__ __launch_bounds__(kObsWaves * 64) void obs_vb_sweep_kernel(ObsVbSweep
   for (int m = 0; m < kVbSums; ++m) sums[m] = 0.0;
   if (ok) {
     const uint32_t cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.ptr[u + 1] - a.ptr[u]));
-    if (a.force_long || cnt > (uint32_t)kObsMaxSlots * 64u) obs_vb_unit<0>(a, u, lane, xs, ls, pkh[wave], sums);
-    else if (cnt <= 64u) obs_vb_unit<1>(a, u, lane, xs, ls, pkh[wave], sums);
-    else if (cnt <= 128u) obs_vb_unit<2>(a, u, lane, xs, ls, pkh[wave], sums);
-    else if (cnt <= 256u) obs_vb_unit<4>(a, u, lane, xs, ls, pkh[wave], sums);
-    else obs_vb_unit<8>(a, u, lane, xs, ls, pkh[wave], sums);
-    if (a.only_k < 0) obs_vb_pieces(a, u, lane, xs, ls, pkh[wave], sums);
+    if (a.force_long || cnt > (uint32_t)kObsMaxSlots * 64u) obs_vb_unit<0, COV>(a, u, lane, xs, ls, pkh[wave], sums);
+    else if (cnt <= 64u) obs_vb_unit<1, COV>(a, u, lane, xs, ls, pkh[wave], sums);
+    else if (cnt <= 128u) obs_vb_unit<2, COV>(a, u, lane, xs, ls, pkh[wave], sums);
+    else if (cnt <= 256u) obs_vb_unit<4, COV>(a, u, lane, xs, ls, pkh[wave], sums);
+    else obs_vb_unit<8, COV>(a, u, lane, xs, ls, pkh[wave], sums);
+    if (a.only_k < 0) obs_vb_pieces<COV>(a, u, lane, xs, ls, pkh[wave], sums);
   }
   if (a.stat) {                      // (wave-uniform, and the same in every wave: all of them reach the barrier)
     const int nsum = a.part ? kVbSums : 4;
@@ -195,6 +222,9 @@ __global__ __launch_bounds__(kObsWaves * 64) void obs_vb_sweep_kernel(ObsVbSweep
     }
   }
 }
+
+__global__ __launch_bounds__(kObsWaves * 64) void obs_vb_sweep_kernel(ObsVbSweepArgs a) { obs_vb_sweep_body<false>(a); }
+__global__ __launch_bounds__(kObsWaves * 64) void obs_trivb_sweep_kernel(ObsVbSweepArgs a) { obs_vb_sweep_body<true>(a); }
 
 // exptau and the iteration's record from the two half sweeps' sums (kernel_misc.hip vb_finish_body: the same rules and the same
 // record), with exp_square_diff = SSE + sum (q2 - q3) of the V half sweep, which saw the final U
@@ -261,6 +291,10 @@ __global__ __launch_bounds__(256) void obs_vb_esd_fold_kernel(const double* part
 
 void launch_obs_vb_sweep(const ObsVbSweepArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(obs_vb_sweep_kernel, dim3(obs_sweep_blocks(a.n)), dim3(kObsWaves * 64), 0, st, a);
+}
+
+void launch_obs_trivb_sweep(const ObsVbSweepArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(obs_trivb_sweep_kernel, dim3(obs_sweep_blocks(a.n)), dim3(kObsWaves * 64), 0, st, a);
 }
 
 void launch_obs_vb_finish(const ObsVbFinishArgs& a, hipStream_t st) {

@@ -617,6 +617,11 @@ struct ObsVbSweepArgs {
   const float* tau;                  // device scalar: exptau
   double* stat;                      // null (the hooks), or the blocks' sums of quad, log erfc, log tau, lambda E [blocks][4] -- with part: and of q2, q3 [blocks][6]
   double* part;                      // null, or [blocks][4]: SSE, sum P, sum P^2, sum R P of the final residual (the V half sweep)
+  // launch_obs_trivb_sweep only (the tri-factorisation's F / G half sweeps against an effective factor; all of it unread otherwise):
+  const int* order;                  // device: the column order of a whole half sweep (null: 0 .. K - 1)
+  const float* cov_S;                // E[S]; element (column c of this factor, inner t) at cov_S[c * cov_sc + t * cov_st]
+  const float* cov_mv;               // [n][32] masked variance sums of the other factor over the unit's entries (mvG / mvF)
+  int cov_sc, cov_st, cov_n;         // strides and inner extent (L for the F half sweep, K for the G half sweep; <= 32)
 };
 struct ObsVbFinishArgs {
   const double* stat_r; int nb_r;    // the U half sweep's [nb_r][4]
@@ -635,6 +640,9 @@ inline int obs_vb_esd_blocks(int n) { return n < 1 ? 1 : (n > 1024 ? 1024 : n); 
 void launch_obs_vb_sweep(const ObsVbSweepArgs& a, hipStream_t st);
 void launch_obs_vb_finish(const ObsVbFinishArgs& a, hipStream_t st);
 void launch_obs_vb_esd(const ObsVbEsdArgs& a, double* out, hipStream_t st);
+// the same sweep with the tri-factorisation's covariance term and column order (kernel_obs_vb.hip: obs_trivb_sweep_kernel, a second
+// instantiation of the body; XT / S2T are not written -- nothing gathers F or G themselves)
+void launch_obs_trivb_sweep(const ObsVbSweepArgs& a, hipStream_t st);
 
 
 // ---------------------------------------------------------------------------
@@ -657,11 +665,47 @@ struct ObsTriGramArgs {     // per column j of the column list: W_j = sum_{i in 
   float* Wc;                         // [n + 2][tri_padded(K)], tri_pos order (pads and the two extra rows are never written)
   float* Pv;                         // [n][32]: the layout launch_ssys_b reads with split = 1, n_pad = n
 };
+struct ObsTriGramVbArgs {   // launch_obs_tri_gram_vb: W~_j = W_j + diag(mv_j), mv_jk = sum_{i in Omega_j} varF_ik (the second moments' column Gram)
+  const float* varF;                 // [I][32]
+  float* mv;                         // [n][32]
+};
 constexpr int kObsTriGramWaves = 4;    // columns (waves) per block of the column-Gram kernel
 constexpr int kObsTriEffRows = 64;     // rows per block of the effective-factor kernel
 inline int obs_tri_gram_blocks(int n) { return (n + kObsTriGramWaves - 1) / kObsTriGramWaves; }
 inline int obs_tri_eff_blocks(int n) { return (n + kObsTriEffRows - 1) / kObsTriEffRows; }
 void launch_obs_tri_eff(const ObsTriEffArgs& a, hipStream_t st);
 void launch_obs_tri_gram(const ObsTriGramArgs& a, hipStream_t st);
+
+// The variational tri-factorisation on the same handle (kernel_obs_trivb.hip)
+struct ObsTriVbEffArgs {    // the effective factor's mean m = X . S (or X . S^T) and second moment S2e = S2X . S2S - X^2 . S^2 + m^2, S2 = var + E^2
+  const float* X; const float* varX; int n;       // [n][32] twice, padding columns zero
+  const float* S; const float* varS; int K, L;    // [K][L] unpadded
+  int transposeS;
+  float* out; float* out2;           // mean and S2e [n][32], padding columns zero
+  float* outT; float* out2T; int ldT;   // transposed [width][ldT], ldT > n: the words behind column n are never written (they stay zero)
+};
+struct ObsMvArgs {          // out[u][c] = sum over the unit's entries e of V[idx[e]][c], in list order per half wave
+  const uint32_t* ptr; const uint32_t* idx; int n;
+  const float* V;                    // [m][32]
+  float* out;                        // [n][32]
+};
+struct ObsTriVbFinishArgs {
+  ObsVbFinishArgs f;                 // as obs_vb_finish_kernel's; rec[4] = SSE + sum (q2 - q3) + third
+  const double* third; int n_third;  // launch_tri_third's partial sums
+};
+struct ObsTriVbEsdArgs {
+  const uint32_t* ptr; const uint32_t* idx; const float* val; int n;     // the row list
+  int K, L;
+  const float* F; const float* varF; const float* G; const float* varG;  // [.][32]
+  const float* S; const float* varS;                                    // [K][L]
+  double* part;                      // [obs_vb_esd_blocks(n)]
+};
+constexpr int kObsMvWaves = 4;
+inline int obs_mv_blocks(int n) { return (n + kObsMvWaves - 1) / kObsMvWaves; }
+void launch_obs_tri_gram_vb(const ObsTriGramArgs& a, const ObsTriGramVbArgs& vb, hipStream_t st);      // obs_tri_gram_kernel's loop, Wc with the variance sums on its diagonal
+void launch_obs_trivb_eff(const ObsTriVbEffArgs& a, hipStream_t st);
+void launch_obs_mv(const ObsMvArgs& a, hipStream_t st);
+void launch_obs_trivb_finish(const ObsTriVbFinishArgs& a, hipStream_t st);
+void launch_obs_trivb_esd(const ObsTriVbEsdArgs& a, double* out, hipStream_t st);
 
 }  // namespace bnmtf

@@ -497,6 +497,33 @@ BNMTF_API int bnmtf_otri_cond_params(bnmtf_handle h, int which, int k, int l, do
 BNMTF_API int bnmtf_otri_metric_sums(bnmtf_handle h, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values,
                            const double* F, const double* S, const double* G, double sums_out[6]);
 
+/* ---- the variational tri-factorisation on the observed-entry layout (class bnmtf_vb_observed) -----
+ * The calls of bnmtf_vb_* above with the same arguments and the same meaning, on a handle of bnmtf_otri_create (K, L <= 32, one GPU):
+ * per iteration the S entries on the second-moment K.L x K.L system, then the F and the G half sweep over the entry lists with the
+ * covariance term, in the orders handed over (csrc/kernel_obs_trivb.hip, kernel_obs_vb.hip, kernel_obs_tri.hip); cost and memory
+ * proportional to the number of observed entries.  The variational buffers are allocated by the first bnmtf_otvb_set_state.  A
+ * handle holds a sampler's state or a variational one: bnmtf_otvb_set_state ends the state of bnmtf_otri_set_state and the reverse,
+ * and bnmtf_otri_run / _get_state / _cond_params refuse a variational state as these refuse a sampler's (BNMTF_ESTATE);
+ * bnmtf_otri_metric_sums takes its factors as arguments and serves both.  Fixed summation order, no atomics: the same call gives
+ * the same bits, run(a) then run(b) those of run(a + b).  (The names: bnmtf_otri_* is the closed set of the sampler's calls.) */
+/* all twelve q-parameter matrices ([I][K] x 4, [K][L] x 4, [J][L] x 4) and exptau; none may be null */
+BNMTF_API int bnmtf_otvb_set_state(bnmtf_handle h, const double* muF, const double* tauF, const double* expF, const double* varF,
+                         const double* muS, const double* tauS, const double* expS, const double* varS,
+                         const double* muG, const double* tauG, const double* expG, const double* varG, double exptau);
+/* any pointer may be null */
+BNMTF_API int bnmtf_otvb_get_state(bnmtf_handle h, double* muF, double* tauF, double* expF, double* varF,
+                         double* muS, double* tauS, double* expS, double* varS,
+                         double* muG, double* tauG, double* expG, double* varG);
+/* update_F(k) (which = 0), update_S(k, l) (1), update_G(l) (2): mu and tau of the target; moments != 0: also its expectation and variance */
+BNMTF_API int bnmtf_otvb_update(bnmtf_handle h, int which, int k, int l, int moments);
+/* exp_square_diff() of the state the device holds: fp64, all four terms per observed entry */
+BNMTF_API int bnmtf_otvb_exp_square_diff(bnmtf_handle h, double* out);
+/* run(n_iter) with the arguments of bnmtf_vb_run: orders [n][K L + K + L] (S entries k L + l, F columns, G columns; required, every
+ * index in range), exptau_out [n], perf_out [n][3], elbo_terms_out [n][10] (exp_square_diff, beta_s, the four sums of F, the four of
+ * G), times_out [n]; any output may be null */
+BNMTF_API int bnmtf_otvb_run(bnmtf_handle h, int n_iter, const int32_t* orders, double* exptau_out, double* perf_out,
+                   double* elbo_terms_out, double* times_out);
+
 #ifdef __cplusplus
 }
 #endif
