@@ -20,8 +20,92 @@ def check_layout(layout):
     assert layout in LAYOUTS, "Unknown layout: %s. Should be 'dense' or 'observed'." % (layout,)
 
 
-def refuse(model, what, why):
-    raise _lib.BnmtfError("%s: %s is not available with layout='observed' (%s)" % (type(model).__name__, what, why))
+# what the layout does not run -> why: every refusal's one text
+REFUSALS = {
+    "set_sweep_path": "it has one sweep kernel; BNMTF_OBS_LONG=1 forces its long form",
+    "set_small_path": "the one-launch path belongs to the dense layout",
+    "set_profiling": "the per-kernel event brackets belong to the dense layout",
+    "masked_sums": "the sums over the missing entries belong to the dense layout's matrix-core product",
+    "column_maxima": "the fixed-point grid belongs to the dense layout's matrix-core product",
+    "run(M_test=)": "held-out curves are kept by the dense layout only; use predict(M_test) after the run",
+    "run(expectation=)": "the posterior sums on the device belong to the dense layout; approx_expectation averages the stored samples",
+    "run_many": "batched launches take models of the dense layout",
+}
+
+
+def refuse(model, what, why=None):
+    raise _lib.BnmtfError("%s: %s is not available with layout='observed' (%s)" % (type(model).__name__, what, REFUSALS[what] if why is None else why))
+
+
+class ObservedLayout(object):
+    """What a model on the layout answers without the device, and what it refuses before any device call.  Ahead of the dense
+    class in the MRO of every class that can run layout='observed': a method answers when self._layout == 'observed' and hands on
+    to the dense class otherwise (the Gibbs / ICM classes take either layout; the two *_vb_observed classes only this one)."""
+
+    def _refuse_if_observed(self, what):
+        if self._layout == 'observed':
+            refuse(self, what)
+
+    def set_sweep_path(self, fast=True):
+        self._refuse_if_observed("set_sweep_path")
+        return super(ObservedLayout, self).set_sweep_path(fast)
+
+    def set_small_path(self, on='auto'):
+        self._refuse_if_observed("set_small_path")
+        return super(ObservedLayout, self).set_small_path(on)
+
+    def set_profiling(self, enable=True, kernel=None, every=1):
+        self._refuse_if_observed("set_profiling")
+        return super(ObservedLayout, self).set_profiling(enable, kernel, every)
+
+    def is_small(self):
+        return False if self._layout == 'observed' else super(ObservedLayout, self).is_small()
+
+    def omega_counts(self):
+        if self._layout != 'observed':
+            return super(ObservedLayout, self).omega_counts()
+        Mb = self.M != 0
+        return int(Mb.sum()), Mb.sum(axis=1).astype(np.uint32), Mb.sum(axis=0).astype(np.uint32)
+
+    def _check_heldout(self, M_test):
+        if self._layout != 'observed':
+            return super(ObservedLayout, self)._check_heldout(M_test)
+        if M_test is not None:
+            refuse(self, "run(M_test=)")
+        return None
+
+
+class ObservedVB(ObservedLayout):
+    """... and of the two variational classes: the q parameters' hand-off, written over the class's _NAMES, _shapes() and the
+    names of its two state calls (_SET_STATE, _GET_STATE), and the hooks of the dense layout's masked product."""
+    _SET_STATE = _GET_STATE = None      # the subclass names them; _shapes() is the dense class's or the subclass's own
+
+    def _push(self):
+        # the state the device holds already (nothing touched the q parameters or exptau since the last device call pulled
+        # them): no upload -- run(a); run(b) is the trajectory of run(a + b)
+        exptau = float(getattr(self, "exptau", 1.0))
+        held = getattr(self, "_device_state", None)
+        if held is not None and held[0] is self._h and held[1] == exptau and all(np.array_equal(getattr(self, n), a) for n, a in zip(self._NAMES, held[2])):
+            return
+        self._device_state = None
+        arrs = [_lib.f64(getattr(self, n)) for n in self._NAMES]
+        _lib.check(getattr(_lib.lib(), self._SET_STATE)(self._handle(), *[_lib.ptr(a) for a in arrs], exptau))
+        self._device_state = (self._h, exptau, [np.array(a, dtype=float) for a in arrs])
+
+    def _pull(self):
+        arrs = [np.zeros(s) for s in self._shapes()]
+        _lib.check(getattr(_lib.lib(), self._GET_STATE)(self._handle(), *[_lib.ptr(a) for a in arrs]))
+        held = getattr(self, "_device_state", None)
+        for n, a in zip(self._NAMES, arrs):
+            setattr(self, n, a)
+        # (exptau: the hooks leave the device's as it was pushed; run() fills in the one formed from the device's beta_s)
+        self._device_state = (self._h, None if held is None else held[1], [a.copy() for a in arrs])
+
+    def masked_sums(self, which):
+        refuse(self, "masked_sums")
+
+    def column_maxima(self, which):
+        refuse(self, "column_maxima")
 
 
 def check_constructor(model, world):
@@ -66,32 +150,28 @@ def entry_list(R, Mask):
             np.ascontiguousarray(np.asarray(R)[Mb], dtype=np.float32))
 
 
-def create_handle(model):
-    """The bnmtf_obs_create handle of a model (its R, M, priors, seed, device)."""
+def _create(model, create, ranks, lambdas):
+    """The handle `create` gives for a model's R, M, seed and device, with its ranks and prior rates."""
     Mb = model.M != 0
     assert (model.M == Mb).all(), "The indicator matrix M must contain only 0 and 1."
     rows, cols, vals = entry_list(model.R, Mb)
     model._train_list = (rows, cols, vals)
-    lr, lc = _lib.f64(model.lambdaU), _lib.f64(model.lambdaV)
+    lams = [_lib.f64(l) for l in lambdas]
     h = C.c_void_p()
-    _lib.check(_lib.lib().bnmtf_obs_create(int(model.I), int(model.J), int(model.K), C.c_uint64(len(rows)), _lib.ptr(rows), _lib.ptr(cols),
-                                           _lib.ptr(vals), _lib.ptr(lr), _lib.ptr(lc), float(model.alpha), float(model.beta),
-                                           C.c_uint64(model._seed & (2 ** 64 - 1)), int(model._device), C.byref(h)))
+    _lib.check(create(int(model.I), int(model.J), *ranks, C.c_uint64(len(rows)), _lib.ptr(rows), _lib.ptr(cols), _lib.ptr(vals),
+                      *[_lib.ptr(l) for l in lams], float(model.alpha), float(model.beta), C.c_uint64(model._seed & (2 ** 64 - 1)),
+                      int(model._device), C.byref(h)))
     return h
+
+
+def create_handle(model):
+    """The bnmtf_obs_create handle of a model (its R, M, priors, seed, device)."""
+    return _create(model, _lib.lib().bnmtf_obs_create, (int(model.K),), (model.lambdaU, model.lambdaV))
 
 
 def create_tri_handle(model):
     """The bnmtf_otri_create handle of a tri-factorisation (its R, M, priors, seed, device)."""
-    Mb = model.M != 0
-    assert (model.M == Mb).all(), "The indicator matrix M must contain only 0 and 1."
-    rows, cols, vals = entry_list(model.R, Mb)
-    model._train_list = (rows, cols, vals)
-    lf, ls, lg = _lib.f64(model.lambdaF), _lib.f64(model.lambdaS), _lib.f64(model.lambdaG)
-    h = C.c_void_p()
-    _lib.check(_lib.lib().bnmtf_otri_create(int(model.I), int(model.J), int(model.K), int(model.L), C.c_uint64(len(rows)), _lib.ptr(rows),
-                                            _lib.ptr(cols), _lib.ptr(vals), _lib.ptr(lf), _lib.ptr(ls), _lib.ptr(lg), float(model.alpha),
-                                            float(model.beta), C.c_uint64(model._seed & (2 ** 64 - 1)), int(model._device), C.byref(h)))
-    return h
+    return _create(model, _lib.lib().bnmtf_otri_create, (int(model.K), int(model.L)), (model.lambdaF, model.lambdaS, model.lambdaG))
 
 
 def _pred_list(model, M_pred):
@@ -104,27 +184,24 @@ def _pred_list(model, M_pred):
     return entry_list(model.R, Mp)
 
 
-def tri_metric_sums(model, M_pred, F, S, G):
-    """The six sums of metrics_from_sums of (F.S).G^T over the entries of M_pred (None: the training entries): F.S and the dot
-    products in fp64 (bnmtf_otri_metric_sums), never the sweeps' fp32 effective factor."""
+def _list_metric(model, M_pred, call, factors):
+    """The six sums `call` gives for the factors (fp64) over the entries of M_pred (None: the training entries)."""
     h = model._handle()
     rows, cols, vals = _pred_list(model, M_pred)
     out = np.zeros(6)
     if len(rows) == 0:                      # (an empty mask: the dense layout's sums of nothing)
         return out
-    F, S, G = _lib.f64(F), _lib.f64(S), _lib.f64(G)
-    _lib.check(_lib.lib().bnmtf_otri_metric_sums(h, C.c_uint64(len(rows)), _lib.ptr(rows), _lib.ptr(cols), _lib.ptr(vals), _lib.ptr(F), _lib.ptr(S),
-                                                 _lib.ptr(G), _lib.ptr(out)))
+    factors = [_lib.f64(f) for f in factors]
+    _lib.check(call(h, C.c_uint64(len(rows)), _lib.ptr(rows), _lib.ptr(cols), _lib.ptr(vals), *[_lib.ptr(f) for f in factors], _lib.ptr(out)))
     return out
+
+
+def tri_metric_sums(model, M_pred, F, S, G):
+    """The six sums of metrics_from_sums of (F.S).G^T over the entries of M_pred (None: the training entries): F.S and the dot
+    products in fp64 (bnmtf_otri_metric_sums), never the sweeps' fp32 effective factor."""
+    return _list_metric(model, M_pred, _lib.lib().bnmtf_otri_metric_sums, (F, S, G))
 
 
 def metric_sums(model, M_pred, A, B):
     """The six sums of metrics_from_sums of A.B^T over the entries of M_pred (None: the training entries), on the device in fp64."""
-    h = model._handle()
-    rows, cols, vals = _pred_list(model, M_pred)
-    out = np.zeros(6)
-    if len(rows) == 0:                      # (an empty mask: the dense layout's sums of nothing)
-        return out
-    A, B = _lib.f64(A), _lib.f64(B)
-    _lib.check(_lib.lib().bnmf_obs_metric_sums(h, C.c_uint64(len(rows)), _lib.ptr(rows), _lib.ptr(cols), _lib.ptr(vals), _lib.ptr(A), _lib.ptr(B), _lib.ptr(out)))
-    return out
+    return _list_metric(model, M_pred, _lib.lib().bnmf_obs_metric_sums, (A, B))

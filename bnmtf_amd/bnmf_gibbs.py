@@ -33,7 +33,7 @@ from ._blocked import BLOCK, MAX_BLOCKS, ColumnBlocks
 MAX_RANK_BLOCKED = BLOCK * MAX_BLOCKS      # 256: ranks above 64 run as column blocks (_blocked.py)
 
 
-class bnmf_gibbs_optimised(DeviceModel):
+class bnmf_gibbs_optimised(_observed.ObservedLayout, DeviceModel):
     def __init__(self, R, M, K, priors, *, seed=None, device=0, verbose=True, rank=0, world=1, comm_id=None, layout='dense'):
         _observed.check_layout(layout)
         self._layout = layout
@@ -147,10 +147,9 @@ class bnmf_gibbs_optimised(DeviceModel):
     def _run_observed(self, iterations, update, store_samples, expectation, M_test):
         """run() with layout='observed': one device call (bnmf_obs_run) runs all iterations -- per iteration the two half sweeps on
         the entry lists and the end-of-iteration kernel; samples, tau, metrics and times come back as from bnmf_gibbs_run."""
-        if M_test is not None:
-            _observed.refuse(self, "run(M_test=)", "held-out curves are kept by the dense layout only; use predict(M_test) after the run")
+        self._check_heldout(M_test)
         if expectation is not None:
-            _observed.refuse(self, "run(expectation=)", "the posterior sums on the device belong to the dense layout; approx_expectation averages the stored samples")
+            _observed.refuse(self, "run(expectation=)")
         it = int(iterations)
         self._push()
         self._dev_expect = None
@@ -238,35 +237,9 @@ class bnmf_gibbs_optimised(DeviceModel):
             return "column blocks %s: " % (self._blocks.ranges,) + " | ".join(ch.describe() for ch in self._blocks.children)
         return super(bnmf_gibbs_optimised, self).describe()
 
-    # the dense layout's switches and device facts: refused for the observed-entry layout before any device call
-    def set_sweep_path(self, fast=True):
-        if self._layout == 'observed':
-            _observed.refuse(self, "set_sweep_path", "it has one sweep kernel; BNMTF_OBS_LONG=1 forces its long form")
-        return super(bnmf_gibbs_optimised, self).set_sweep_path(fast)
-
-    def set_small_path(self, on='auto'):
-        if self._layout == 'observed':
-            _observed.refuse(self, "set_small_path", "the one-launch path belongs to the dense layout")
-        return super(bnmf_gibbs_optimised, self).set_small_path(on)
-
-    def set_profiling(self, enable=True, kernel=None, every=1):
-        if self._layout == 'observed':
-            _observed.refuse(self, "set_profiling", "the per-kernel event brackets belong to the dense layout")
-        return super(bnmf_gibbs_optimised, self).set_profiling(enable, kernel, every)
-
-    def is_small(self):
-        return False if self._layout == 'observed' else super(bnmf_gibbs_optimised, self).is_small()
-
-    def omega_counts(self):
-        if self._layout == 'observed':
-            Mb = self.M != 0
-            return int(Mb.sum()), Mb.sum(axis=1).astype(np.uint32), Mb.sum(axis=0).astype(np.uint32)
-        return super(bnmf_gibbs_optimised, self).omega_counts()
-
     def _run_prepare(self, iterations, store_samples, expectation):
         """State on the device, expectation switch, output arrays of one run() call (also used by bnmtf_amd.run_many)."""
-        if self._layout == 'observed':
-            _observed.refuse(self, "run_many", "batched launches take models of the dense layout")
+        self._refuse_if_observed("run_many")
         it = int(iterations)
         self._push()
         self._set_expectation(expectation, it)

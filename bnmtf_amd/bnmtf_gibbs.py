@@ -22,7 +22,7 @@ from ._blocked import BLOCK, MAX_BLOCKS, TriBlocks
 MAX_RANK_BLOCKED = BLOCK * MAX_BLOCKS      # 256: K or L above 64 run as blocks of S (_blocked.py: TriBlocks)
 
 
-class bnmtf_gibbs_optimised(DeviceModel):
+class bnmtf_gibbs_optimised(_observed.ObservedLayout, DeviceModel):
     def __init__(self, R, M, K, L, priors, *, seed=None, device=0, verbose=True, rank=0, world=1, comm_id=None, layout='dense'):
         _observed.check_layout(layout)
         self._layout = layout
@@ -150,10 +150,9 @@ class bnmtf_gibbs_optimised(DeviceModel):
         """run() with layout='observed': one device call (bnmtf_otri_run) runs all iterations -- per iteration the F half sweep
         against G.S^T, the dense S system from the column list, the G half sweep against F.S and the end-of-iteration kernel;
         samples, tau, metrics and times come back as from bnmtf_gibbs_run."""
-        if M_test is not None:
-            _observed.refuse(self, "run(M_test=)", "held-out curves are kept by the dense layout only; use predict(M_test) after the run")
+        self._check_heldout(M_test)
         if expectation is not None:
-            _observed.refuse(self, "run(expectation=)", "the posterior sums on the device belong to the dense layout; approx_expectation averages the stored samples")
+            _observed.refuse(self, "run(expectation=)")
         it = int(iterations)
         self._push()
         self._dev_expect = None
@@ -165,31 +164,6 @@ class bnmtf_gibbs_optimised(DeviceModel):
         _lib.check(_lib.lib().bnmtf_otri_run(self._handle(), it, int(update), _lib.ptr(F_out), _lib.ptr(S_out), _lib.ptr(G_out),
                                              _lib.ptr(bufs[4]), _lib.ptr(bufs[5]), _lib.ptr(bufs[6])))
         return bufs
-
-    # the dense layout's switches and device facts: refused for the observed-entry layout before any device call
-    def set_sweep_path(self, fast=True):
-        if self._layout == 'observed':
-            _observed.refuse(self, "set_sweep_path", "it has one sweep kernel; BNMTF_OBS_LONG=1 forces its long form")
-        return super(bnmtf_gibbs_optimised, self).set_sweep_path(fast)
-
-    def set_small_path(self, on='auto'):
-        if self._layout == 'observed':
-            _observed.refuse(self, "set_small_path", "the one-launch path belongs to the dense layout")
-        return super(bnmtf_gibbs_optimised, self).set_small_path(on)
-
-    def set_profiling(self, enable=True, kernel=None, every=1):
-        if self._layout == 'observed':
-            _observed.refuse(self, "set_profiling", "the per-kernel event brackets belong to the dense layout")
-        return super(bnmtf_gibbs_optimised, self).set_profiling(enable, kernel, every)
-
-    def is_small(self):
-        return False if self._layout == 'observed' else super(bnmtf_gibbs_optimised, self).is_small()
-
-    def omega_counts(self):
-        if self._layout == 'observed':
-            Mb = self.M != 0
-            return int(Mb.sum()), Mb.sum(axis=1).astype(np.uint32), Mb.sum(axis=0).astype(np.uint32)
-        return super(bnmtf_gibbs_optimised, self).omega_counts()
 
     def _run_blocked(self, iterations, update, store_samples, expectation, minimum_TN=0.0, icm=False):
         """run() of a model with K or L above 64 (_blocked.py: TriBlocks): tau by the update rule's own law -- a Gamma(alpha_s,
@@ -261,8 +235,7 @@ class bnmtf_gibbs_optimised(DeviceModel):
 
     # run() in two halves, so that bnmtf_amd.run_many can put many models' device part into one call
     def _run_prepare(self, iterations, store_samples, expectation):
-        if self._layout == 'observed':
-            _observed.refuse(self, "run_many", "batched launches take models of the dense layout")
+        self._refuse_if_observed("run_many")
         it = int(iterations)
         self._push()
         self._set_expectation(expectation, it)

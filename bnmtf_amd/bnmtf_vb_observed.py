@@ -19,7 +19,9 @@ from ._base import broadcast_lambda, check_R_M
 from .bnmtf_vb import bnmtf_vb_optimised
 
 
-class bnmtf_vb_observed(bnmtf_vb_optimised):
+class bnmtf_vb_observed(_observed.ObservedVB, bnmtf_vb_optimised):
+    _SET_STATE, _GET_STATE = "bnmtf_otvb_set_state", "bnmtf_otvb_get_state"
+
     def __init__(self, R, M, K, L, priors, *, device=0, verbose=True, rank=0, world=1, comm_id=None):
         self._layout = 'observed'
         self.R = np.array(R, dtype=float)
@@ -42,35 +44,11 @@ class bnmtf_vb_observed(bnmtf_vb_optimised):
             self._h = _observed.create_tri_handle(self)
         return self._h
 
-    # -- state hand-off -------------------------------------------------------
     def _push(self):
-        # the state the device holds already (nothing touched the q parameters or exptau since the last device call pulled
-        # them): no upload -- run(a); run(b) is the trajectory of run(a + b)
         for n, s in zip(self._NAMES, self._shapes()):      # the reference's tests set only some of the attributes
             if not hasattr(self, n):
                 setattr(self, n, np.ones(s))
-        exptau = float(getattr(self, "exptau", 1.0))
-        held = getattr(self, "_device_state", None)
-        if held is not None and held[0] is self._h and held[1] == exptau and all(np.array_equal(getattr(self, n), a) for n, a in zip(self._NAMES, held[2])):
-            return
-        self._device_state = None
-        arrs = [_lib.f64(getattr(self, n)) for n in self._NAMES]
-        _lib.check(_lib.lib().bnmtf_otvb_set_state(self._handle(), *[_lib.ptr(a) for a in arrs], exptau))
-        self._device_state = (self._h, exptau, [np.array(a, dtype=float) for a in arrs])
-
-    def _pull(self):
-        arrs = [np.zeros(s) for s in self._shapes()]
-        _lib.check(_lib.lib().bnmtf_otvb_get_state(self._handle(), *[_lib.ptr(a) for a in arrs]))
-        held = getattr(self, "_device_state", None)
-        for n, a in zip(self._NAMES, arrs):
-            setattr(self, n, a)
-        # (exptau: the hooks leave the device's as it was pushed; run() fills in the one formed from the device's beta_s)
-        self._device_state = (self._h, None if held is None else held[1], [a.copy() for a in arrs])
-
-    def _check_heldout(self, M_test):
-        if M_test is not None:
-            _observed.refuse(self, "run(M_test=)", "held-out curves are kept by the dense layout only; use predict(M_test) after the run")
-        return None
+        super(bnmtf_vb_observed, self)._push()
 
     def _run_device(self, it, orders, exptau, perf, terms, times):
         _lib.check(_lib.lib().bnmtf_otvb_run(self._handle(), it, _lib.ptr(orders), _lib.ptr(exptau), _lib.ptr(perf), _lib.ptr(terms), _lib.ptr(times)))
@@ -94,26 +72,3 @@ class bnmtf_vb_observed(bnmtf_vb_optimised):
 
     def _metric_sums(self, M_pred, A, S, B):
         return _observed.tri_metric_sums(self, M_pred, self.expF if A is None else A, self.expS if S is None else S, self.expG if B is None else B)
-
-    def omega_counts(self):
-        Mb = self.M != 0
-        return int(Mb.sum()), Mb.sum(axis=1).astype(np.uint32), Mb.sum(axis=0).astype(np.uint32)
-
-    # -- what the layout does not run: refused before any device call ------------
-    def masked_sums(self, which):
-        _observed.refuse(self, "masked_sums", "the sums over the missing entries belong to the dense layout's matrix-core product")
-
-    def column_maxima(self, which):
-        _observed.refuse(self, "column_maxima", "the fixed-point grid belongs to the dense layout's matrix-core product")
-
-    def set_sweep_path(self, fast=True):
-        _observed.refuse(self, "set_sweep_path", "it has one sweep kernel; BNMTF_OBS_LONG=1 forces its long form")
-
-    def set_small_path(self, on='auto'):
-        _observed.refuse(self, "set_small_path", "the one-launch path belongs to the dense layout")
-
-    def set_profiling(self, enable=True, kernel=None, every=1):
-        _observed.refuse(self, "set_profiling", "the per-kernel event brackets belong to the dense layout")
-
-    def is_small(self):
-        return False

@@ -46,7 +46,6 @@ extern "C" int bnmtf_shard_range(int64_t n, int rank, int world, int64_t* first,
 namespace bnmtf {
 static void np_free(bnmtf_model* h);   // api_np.inc
 static void obs_free(bnmtf_model* h);  // api_obs.inc
-static void otri_free(bnmtf_model* h); // api_obs_tri.inc
 
 template <typename T>
 static int dalloc(T** p, size_t count, bool zero = true) {
@@ -69,14 +68,12 @@ static int upload(T** dst, const std::vector<T>& src, hipStream_t st) {
   return BNMTF_OK;
 }
 
-// a handle of bnmtf_obs_create (the observed-entry layout, api_obs.inc) holds none of what the other entry points work on
+// a handle of bnmtf_obs_create or -- the tri-factorisation, L > 0 -- bnmtf_otri_create (the observed-entry layout, api_obs.inc)
+// holds none of what the other entry points work on
 static int refuse_obs(const bnmtf_model* h, const char* fn) {
   if (h && h->obs) {      // (fn null: reached through ensure_std, from any of the sampler and variational calls)
-    set_error("%s%sa handle of bnmtf_obs_create runs only the bnmf_obs_* calls (layout='observed')", fn ? fn : "", fn ? ": " : "");
-    return BNMTF_EINVAL;
-  }
-  if (h && h->otri) {     // ... and one of bnmtf_otri_create (api_obs_tri.inc) likewise
-    set_error("%s%sa handle of bnmtf_otri_create runs only the bnmtf_otri_* calls (layout='observed')", fn ? fn : "", fn ? ": " : "");
+    set_error("%s%sa handle of %s calls (layout='observed')", fn ? fn : "", fn ? ": " : "",
+              h->L > 0 ? "bnmtf_otri_create runs only the bnmtf_otri_*" : "bnmtf_obs_create runs only the bnmf_obs_*");
     return BNMTF_EINVAL;
   }
   return BNMTF_OK;
@@ -1121,7 +1118,6 @@ int bnmtf_destroy(bnmtf_handle h) try {
   if (h->comm) comm_destroy(h->comm);
   np_free(h);
   obs_free(h);
-  otri_free(h);
   heldout_free(h);
   small_free(h);            // (first: a small model's arena also holds Rfull, the posterior sums, Ad / Bd -- their pointers are cleared)
   free_dir(h->rows); free_dir(h->cols); free_dir(h->reff); free_dir(h->ceff);

@@ -1,53 +1,80 @@
-// Observed-entry layout of the two-factor Gibbs / ICM models (C ABI part 6, layout='observed') -- included at the end of api.hip.
-// A handle of bnmtf_obs_create holds, in ObsState, the observed entries as a row list and a column list, both factors row major
-// and transposed in fp32, the prior rates, the long form's residual scratch and the V half sweep's partial sums: memory
-// proportional to the number of observed entries.  None of the samplers' layouts, no dense operand, no copy of R or M.  The
-// iteration is two launches of obs_sweep_kernel and obs_finish_kernel (kernel_obs.hip) on the handle's stream; the samples leave
-// through the SampleSink like bnmf_gibbs_run's, written into their slots by the sweeps themselves.  One GPU.
-// The variational model on the same handle (bnmf_vbo_*, at the end of this file): its q parameters, the transposed S2 and the
-// half sweeps' partial sums are allocated by the first bnmf_vbo_set_state, so a Gibbs / ICM handle holds none of them.
+// The observed-entry layout (C ABI part 6, layout='observed') -- included at the end of api.hip, ahead of api_obs_tri.inc and
+// api_obs_trivb.inc, which build on what is here.
+// A handle of bnmtf_obs_create (two factors) or bnmtf_otri_create (the tri-factorisation: h->L > 0) holds, in ONE ObsState, the
+// observed entries as a row list and a column list, both factors row major and transposed in fp32, the prior rates, the long
+// form's residual scratch and the second half sweep's partial sums: memory proportional to the number of observed entries.  None
+// of the samplers' layouts, no dense operand, no copy of R or M.  The optional parts of the state:
+//   * the tri-factorisation's effective factors and Pv (bnmtf_otri_create; null on a two-factor handle), with a row stride of 32
+//     where a two-factor handle has K rounded up to 4;
+//   * the variational buffers -- q's parameters and the half sweeps' partial sums per direction, the transposed S2 of a two-factor
+//     handle, the effective factors' second moments of a tri-factorisation --, allocated by the first bnmf_vbo_set_state /
+//     bnmtf_otvb_set_state, so a Gibbs / ICM handle holds none of them.
+// obs_free is the one owner of all of it.  This file has the state, the helpers every model on the layout shares (one direction's
+// build / put / q, the common part of create, the half sweeps' argument builders, the record and the hooks' tails, the list
+// metric) and the two-factor models: the Gibbs / ICM iteration is two launches of obs_sweep_kernel and obs_finish_kernel
+// (kernel_obs.hip) on the handle's stream, the samples leave through the SampleSink like bnmf_gibbs_run's, written into their
+// slots by the sweeps themselves; the variational model (bnmf_vbo_*, kernel_obs_vb.hip) is at the end of the file.  One GPU.
 
 namespace bnmtf {
 
 struct ObsList {                 // one direction: units, their entries' inner indices and values
   uint32_t* ptr = nullptr; uint32_t* idx = nullptr; float* val = nullptr;
-  float* X = nullptr; float* XT = nullptr; int n = 0, ldT = 0;     // the direction's factor [n][KP] and [K][ldT]
-  float* lambda = nullptr;                                         // [n][KP]
+  float* X = nullptr; float* XT = nullptr; int n = 0, W = 0, ldT = 0;   // the direction's factor of W columns: [n][stride] and [W][ldT]
+  float* lambda = nullptr;                                         // [n][stride]
   double* numer = nullptr; double* taup = nullptr;                 // cond-params scratch [n]
   uint32_t longest = 0; size_t long_units = 0;                     // most entries of a unit; units beyond the register form
-  // variational state (bnmf_vbo_set_state): q's mu, tau, var [n][KP] beside the expectation in X / XT; S2 = var + X^2 transposed
-  // [K][ldT] with XT's zero word behind every column; the half sweep's partial sums [obs_sweep_blocks(n)][6]
+  // variational state (obs_alloc_q): q's mu, tau, var [n][stride] beside the expectation in X / XT; on a two-factor handle also
+  // S2 = var + X^2 transposed [W][ldT] with XT's zero word behind every column; the half sweep's partial sums [obs_sweep_blocks(n)][6]
   float* mu = nullptr; float* tauq = nullptr; float* var = nullptr; float* S2T = nullptr;
   double* vstat = nullptr;
+  void free_all() {              // every pointer member above
+    dfree(ptr); dfree(idx); dfree(val); dfree(X); dfree(XT); dfree(lambda); dfree(numer); dfree(taup);
+    dfree(mu); dfree(tauq); dfree(var); dfree(S2T); dfree(vstat);
+  }
 };
 struct ObsState {
-  ObsList rows, cols;
-  size_t n = 0; int KP = 0;
+  ObsList rows, cols;              // U's and V's direction, or F's (W = K) and G's (W = L)
+  size_t n = 0; int stride = 0;    // entries; row stride of every row-major factor: K rounded up to 4, or kObsTriStride
   float* escratch = nullptr;       // [n]
   double* part = nullptr;          // [obs_sweep_blocks(J)][4]
   double* scal = nullptr;          // tau_d, tau_f and out8 of the metric sums (one allocation)
   double* out8 = nullptr;
   bool force_long = false;
-  bool vb_alloc = false, vb_state = false;   // the variational buffers exist; they hold the state of the last bnmf_vbo_set_state / run
+  bool vb_alloc = false, vb_state = false;   // the variational buffers exist; they hold the state of the last variational set_state / run
   double* esd_part = nullptr;      // [obs_vb_esd_blocks(I)] exp_square_diff's partial sums
+  // the tri-factorisation only (api_obs_tri.inc, api_obs_trivb.inc)
+  float* ceffX = nullptr; float* ceffXT = nullptr;    // G S^T: [J][32] and [K][cols.ldT]
+  float* reffX = nullptr; float* reffXT = nullptr;    // F S:   [I][32] and [L][rows.ldT]
+  float* Pv = nullptr;                                // R~^T F [J][32]
+  float* ceffS2 = nullptr; float* ceffS2T = nullptr;  // variational: second moment of G S^T, [J][32] and [K][cols.ldT]
+  float* reffS2 = nullptr; float* reffS2T = nullptr;  // ... and of F S, [I][32] and [L][rows.ldT]
 };
+
+static bool obs_is_tri(const bnmtf_model* h) { return h->L > 0; }
 
 static void obs_free(bnmtf_model* h) {
   ObsState* s = h->obs;
   if (!s) return;
-  for (ObsList* d : {&s->rows, &s->cols}) {
-    dfree(d->ptr); dfree(d->idx); dfree(d->val); dfree(d->X); dfree(d->XT); dfree(d->lambda); dfree(d->numer); dfree(d->taup);
-    dfree(d->mu); dfree(d->tauq); dfree(d->var); dfree(d->S2T); dfree(d->vstat);
-  }
+  s->rows.free_all(); s->cols.free_all();
   dfree(s->escratch); dfree(s->part); dfree(s->scal); dfree(s->esd_part);
+  dfree(s->ceffX); dfree(s->ceffXT); dfree(s->reffX); dfree(s->reffXT); dfree(s->Pv);
+  dfree(s->ceffS2); dfree(s->ceffS2T); dfree(s->reffS2); dfree(s->reffS2T);
   h->tau_d = nullptr; h->tau_f = nullptr;
   delete s;
-  h->obs = nullptr;
+  h->obs = nullptr;              // (a tri-factorisation's S, lambdaS and S system's buffers are the model's own: bnmtf_destroy frees them)
 }
 
-static int obs_check(bnmtf_model* h, bool need_state) {
-  if (!h || !h->obs) { set_error("not a handle of bnmtf_obs_create"); return BNMTF_EINVAL; }
-  if (need_state && !h->have_state) { set_error("bnmf_obs_set_state has not been called"); return BNMTF_ESTATE; }
+// Every entry point's first step.  tri: the call belongs to the bnmtf_otri_* / bnmtf_otvb_* family; need: the state it works on.
+// A tri-factorisation's sampler calls refuse a variational state; the two-factor ones run on its expectations (DESIGN.md section 2.7).
+enum { kObsNoState = 0, kObsSamplerState, kObsVbState };
+static int obs_check(bnmtf_model* h, bool tri, int need) {
+  if (!h || !h->obs || obs_is_tri(h) != tri) { set_error("not a handle of %s", tri ? "bnmtf_otri_create" : "bnmtf_obs_create"); return BNMTF_EINVAL; }
+  if (need == kObsSamplerState && !h->have_state) { set_error("%s has not been called", tri ? "bnmtf_otri_set_state" : "bnmf_obs_set_state"); return BNMTF_ESTATE; }
+  if (need == kObsSamplerState && tri && h->obs->vb_state) {
+    set_error("the handle holds a variational state (bnmtf_otvb_set_state): it runs the bnmtf_otvb_* calls until bnmtf_otri_set_state replaces it");
+    return BNMTF_ESTATE;
+  }
+  if (need == kObsVbState && !(h->obs->vb_state && h->have_state)) { set_error("%s has not been called", tri ? "bnmtf_otvb_set_state" : "bnmf_vbo_set_state"); return BNMTF_ESTATE; }
   HIPCHK(hipSetDevice(h->device));
   return BNMTF_OK;
 }
@@ -76,9 +103,9 @@ static long long obs_sort(uint64_t n, const int32_t* major, const int32_t* minor
   return -1;
 }
 
-// What bnmtf_obs_create holds of the entries, built on the host before any device call (and handed out by
-// bnmtf_obs_build_lists): the checked entries as a row list and a column list, and the sums of R over them.  Refuses an entry
-// outside the matrix, an entry that occurs twice and a row or column without entries.
+// What a create holds of the entries, built on the host before any device call (and handed out by bnmtf_obs_build_lists): the
+// checked entries as a row list and a column list, and the sums of R over them.  Refuses an entry outside the matrix, an entry
+// that occurs twice and a row or column without entries.
 struct ObsLists {
   std::vector<uint32_t> rptr, ridx, cptr, cidx;
   std::vector<float> rval, cval;
@@ -105,20 +132,20 @@ static int obs_lists(int I, int J, uint64_t n, const int32_t* rows, const int32_
   return BNMTF_OK;
 }
 
-static int obs_build_dir(bnmtf_model* h, ObsList& d, int n, const std::vector<uint32_t>& ptr, const std::vector<uint32_t>& idx,
+// one direction: the list, the prior rates [n][stride], the factor of W columns in both forms and the hooks' scratch
+static int obs_build_dir(bnmtf_model* h, ObsList& d, int n, int W, const std::vector<uint32_t>& ptr, const std::vector<uint32_t>& idx,
                          const std::vector<float>& val, const double* lambda) {
-  ObsState* s = h->obs;
-  const int K = h->K, KP = s->KP;
-  d.n = n; d.ldT = round_up(n + 1, 64);          // (a zero behind every column of XT: the sweep's empty slots gather it)
+  const int KP = h->obs->stride;
+  d.n = n; d.W = W; d.ldT = round_up(n + 1, 64);          // (a zero behind every column of the transposed forms: the sweep's empty slots gather it)
   CHK(upload(&d.ptr, ptr, h->stream));
   CHK(upload(&d.idx, idx, h->stream));
   CHK(upload(&d.val, val, h->stream));
   std::vector<float> lam((size_t)n * KP, 0.f);
   for (int u = 0; u < n; ++u)
-    for (int k = 0; k < K; ++k) lam[(size_t)u * KP + k] = (float)lambda[(size_t)u * K + k];
+    for (int k = 0; k < W; ++k) lam[(size_t)u * KP + k] = (float)lambda[(size_t)u * W + k];
   CHK(upload(&d.lambda, lam, h->stream));
   CHK(dalloc(&d.X, (size_t)n * KP));
-  CHK(dalloc(&d.XT, (size_t)K * d.ldT));
+  CHK(dalloc(&d.XT, (size_t)W * d.ldT));
   CHK(dalloc(&d.numer, (size_t)n, false));
   CHK(dalloc(&d.taup, (size_t)n, false));
   for (int u = 0; u < n; ++u) {
@@ -129,13 +156,13 @@ static int obs_build_dir(bnmtf_model* h, ObsList& d, int n, const std::vector<ui
   return BNMTF_OK;
 }
 
-// fp64 host [n][K] -> fp32 device [n][KP] and [K][ldT]
+// fp64 host [n][W] -> fp32 device [n][stride] and [W][ldT]
 static int obs_put(bnmtf_model* h, ObsList& d, const double* src) {
-  const int K = h->K, KP = h->obs->KP;
-  std::vector<float> x((size_t)d.n * KP, 0.f), xt((size_t)K * d.ldT, 0.f);
+  const int W = d.W, KP = h->obs->stride;
+  std::vector<float> x((size_t)d.n * KP, 0.f), xt((size_t)W * d.ldT, 0.f);
   for (int u = 0; u < d.n; ++u)
-    for (int k = 0; k < K; ++k) {
-      const float v = (float)src[(size_t)u * K + k];
+    for (int k = 0; k < W; ++k) {
+      const float v = (float)src[(size_t)u * W + k];
       x[(size_t)u * KP + k] = v; xt[(size_t)k * d.ldT + u] = v;
     }
   HIPCHK(hipMemcpyAsync(d.X, x.data(), x.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -144,13 +171,94 @@ static int obs_put(bnmtf_model* h, ObsList& d, const double* src) {
   return BNMTF_OK;
 }
 
-static ObsSweepArgs obs_sweep_args(bnmtf_model* h, bool rows, int mode) {
+// a direction's variational buffers; with_S2T: the transposed second moment a two-factor half sweep gathers from the other
+// direction (a tri-factorisation gathers its effective factor's instead)
+static int obs_alloc_q(bnmtf_model* h, ObsList& d, bool with_S2T) {
+  const size_t nk = (size_t)d.n * h->obs->stride;
+  if (!d.mu) CHK(dalloc(&d.mu, nk));
+  if (!d.tauq) CHK(dalloc(&d.tauq, nk));
+  if (!d.var) CHK(dalloc(&d.var, nk));
+  if (with_S2T && !d.S2T) CHK(dalloc(&d.S2T, (size_t)d.W * d.ldT));
+  if (!d.vstat) CHK(dalloc(&d.vstat, (size_t)obs_sweep_blocks(d.n) * 6));
+  return BNMTF_OK;
+}
+
+// fp64 host [n][W] x 4 -> the direction's fp32 q: mu, tau, var [n][stride]; the expectation in X / XT; where the direction owns
+// an S2T, S2 = var + exp^2 there
+static int obs_put_q(bnmtf_model* h, ObsList& d, const double* mu, const double* tau, const double* ex, const double* var) {
+  const int W = d.W, KP = h->obs->stride;
+  const size_t nk = (size_t)d.n * KP;
+  std::vector<float> m(nk, 0.f), t(nk, 0.f), v(nk, 0.f), s2(d.S2T ? (size_t)W * d.ldT : 0, 0.f);
+  for (int u = 0; u < d.n; ++u)
+    for (int k = 0; k < W; ++k) {
+      const size_t src = (size_t)u * W + k, at = (size_t)u * KP + k;
+      m[at] = (float)mu[src]; t[at] = (float)tau[src]; v[at] = (float)var[src];
+      if (d.S2T) {
+        const float e = (float)ex[src];
+        s2[(size_t)k * d.ldT + u] = fmaf(e, e, v[at]);            // (as the sweep forms it)
+      }
+    }
+  CHK(obs_put(h, d, ex));
+  HIPCHK(hipMemcpyAsync(d.mu, m.data(), nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(d.tauq, t.data(), nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(d.var, v.data(), nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (d.S2T) HIPCHK(hipMemcpyAsync(d.S2T, s2.data(), s2.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return BNMTF_OK;
+}
+
+// The common part of bnmtf_obs_create / bnmtf_otri_create (the callers have checked their arguments): the lists, the model, its
+// stream, the state with both directions and the scalars.  The handle is the guard's from the moment it exists: every way out of
+// a create but release(), an exception included, destroys it.
+struct ObsCreateGuard {
+  bnmtf_model* h = nullptr;
+  ~ObsCreateGuard() { if (h) bnmtf_destroy(h); }
+  bnmtf_model* release() { bnmtf_model* r = h; h = nullptr; return r; }
+};
+static int obs_create_common(ObsCreateGuard& guard, int I, int J, int K, int L, int stride, uint64_t n, const int32_t* rows, const int32_t* cols,
+                             const float* values, const double* lambda_rows, const double* lambda_cols, double alpha, double beta,
+                             uint64_t seed, int device) {
+  ObsLists ls;
+  CHK(obs_lists(I, J, n, rows, cols, values, ls));
+  HIPCHK(hipSetDevice(device));
+  bnmtf_model* h = new bnmtf_model();
+  guard.h = h;
+  const int Wc = L > 0 ? L : K;
+  h->I = I; h->J = J; h->K = K; h->L = L; h->device = device;
+  h->alpha = alpha; h->beta = beta; h->seed = seed;
+  h->n_obs = (double)n; h->sumR = ls.sumR; h->sumR2 = ls.sumR2;
+  h->rows.nglob = I; h->rows.m = J; h->rows.W = K; h->cols.nglob = J; h->cols.m = I; h->cols.W = Wc;
+  h->std_built = false;
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { h->stream = nullptr; set_error("hipStreamCreate failed"); return BNMTF_EHIP; }
+  h->obs = new ObsState();
+  ObsState* s = h->obs;
+  s->n = (size_t)n; s->stride = stride;
+  const char* fl = getenv("BNMTF_OBS_LONG");
+  s->force_long = fl && fl[0] == '1';
+  CHK(obs_build_dir(h, s->rows, I, K, ls.rptr, ls.ridx, ls.rval, lambda_rows));
+  CHK(obs_build_dir(h, s->cols, J, Wc, ls.cptr, ls.cidx, ls.cval, lambda_cols));
+  CHK(dalloc(&s->escratch, (size_t)n, false));
+  CHK(dalloc(&s->part, (size_t)obs_sweep_blocks(J) * 4, false));
+  CHK(dalloc(&s->scal, 16));
+  h->tau_d = s->scal; h->tau_f = reinterpret_cast<float*>(s->scal + 1); s->out8 = s->scal + 8;
+  return BNMTF_OK;
+}
+
+// What a half sweep reads of its other operand: row major [m][stride], transposed [.][ldT] (ldT > m: word m of every column is
+// zero) and, for the variational sweeps, the second moment transposed.  Two factors: the other direction's list itself.
+struct ObsOther { const float* X; const float* XT; const float* S2T; int ldT, m; };
+static ObsOther obs_other(bnmtf_model* h, bool rows) {
+  const ObsList& o = rows ? h->obs->cols : h->obs->rows;
+  return ObsOther{o.X, o.XT, o.S2T, o.ldT, o.n};
+}
+
+// the half sweep of a direction (rows: U or F) against `o`
+static ObsSweepArgs obs_sweep_args(bnmtf_model* h, bool rows, const ObsOther& o, int mode) {
   ObsState* s = h->obs;
   ObsList& d = rows ? s->rows : s->cols;
-  ObsList& o = rows ? s->cols : s->rows;
   ObsSweepArgs a; memset(&a, 0, sizeof(a));
   a.ptr = d.ptr; a.idx = d.idx; a.val = d.val;
-  a.n = d.n; a.m = o.n; a.K = h->K; a.KP = s->KP;
+  a.n = d.n; a.m = o.m; a.K = d.W; a.KP = s->stride;
   a.mode = mode; a.cond_k = -1; a.force_long = s->force_long ? 1 : 0; a.min_x = h->cur_min_x;
   a.lambda = d.lambda;
   a.X = d.X; a.XT = d.XT; a.ldT = d.ldT;
@@ -160,6 +268,95 @@ static ObsSweepArgs obs_sweep_args(bnmtf_model* h, bool rows, int mode) {
   a.key0 = (uint32_t)h->seed; a.key1 = (uint32_t)(h->seed >> 32); a.it = (uint32_t)h->iteration;
   a.stream = rows ? kStreamRows : kStreamCols;
   return a;
+}
+
+// ... and the variational one (S2T: null where the direction owns none).  A tri-factorisation's caller adds its order and
+// covariance fields and takes XT out: its instantiation writes neither transposed form.
+static ObsVbSweepArgs obs_vb_sweep_args(bnmtf_model* h, bool rows, const ObsOther& o) {
+  ObsState* s = h->obs;
+  ObsList& d = rows ? s->rows : s->cols;
+  ObsVbSweepArgs a; memset(&a, 0, sizeof(a));
+  a.ptr = d.ptr; a.idx = d.idx; a.val = d.val;
+  a.n = d.n; a.m = o.m; a.K = d.W; a.KP = s->stride;
+  a.only_k = -1; a.moments = 1; a.force_long = s->force_long ? 1 : 0;
+  a.lambda = d.lambda;
+  a.X = d.X; a.XT = d.XT; a.S2T = d.S2T; a.ldT = d.ldT;
+  a.mu = d.mu; a.tauq = d.tauq; a.var = d.var;
+  a.Xo = o.X; a.XoT = o.XT; a.S2oT = o.S2T; a.ldT_o = o.ldT;
+  a.escratch = s->escratch;
+  a.tau = h->tau_f;
+  return a;
+}
+
+// tau and the record of iteration `it` of a run call, from the second half sweep's final residual
+static ObsFinishArgs obs_finish_args(bnmtf_model* h, int update, int it) {
+  ObsFinishArgs f; memset(&f, 0, sizeof(f));
+  f.part = h->obs->part; f.nb = obs_sweep_blocks(h->J);
+  f.n_obs = h->n_obs; f.sumR = h->sumR; f.sumR2 = h->sumR2; f.alpha = h->alpha; f.beta = h->beta;
+  f.update = update; f.gunit = update == BNMTF_UPDATE_DRAW ? h->gunit + it : nullptr;
+  f.tau_d = h->tau_d; f.tau_f = h->tau_f; f.rec = h->rec + (size_t)it * 5;
+  return f;
+}
+// ... and the variational finish's: update_tau, update_exp_tau and the record
+static ObsVbFinishArgs obs_vb_finish_args(bnmtf_model* h, int it) {
+  ObsState* s = h->obs;
+  ObsVbFinishArgs f; memset(&f, 0, sizeof(f));
+  f.stat_r = s->rows.vstat; f.nb_r = obs_sweep_blocks(h->I);
+  f.stat_c = s->cols.vstat; f.part = s->part; f.nb_c = obs_sweep_blocks(h->J);
+  f.n_obs = h->n_obs; f.sumR = h->sumR; f.sumR2 = h->sumR2; f.alpha = h->alpha; f.beta = h->beta;
+  f.tau_d = h->tau_d; f.tau_f = h->tau_f; f.rec = h->vb_rec + (size_t)it * 16;
+  return f;
+}
+
+// the sampler's record [n_iter][5] of a finished run call: tau, then MSE, R^2, Rp
+static int obs_fetch_rec(bnmtf_model* h, int n_iter, double* tau_out, double* perf_out) {
+  std::vector<double> rec((size_t)n_iter * 5);
+  HIPCHK(hipMemcpy(rec.data(), h->rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (int it = 0; it < n_iter; ++it) {
+    if (tau_out) tau_out[it] = rec[(size_t)it * 5];
+    if (perf_out) for (int m = 0; m < 3; ++m) perf_out[(size_t)it * 3 + m] = rec[(size_t)it * 5 + 1 + m];
+  }
+  return BNMTF_OK;
+}
+
+// the cond_params hook of a direction: (numer, tau) of column k for the state the device holds, which stays as it is
+static int obs_cond_params_dir(bnmtf_model* h, ObsList& d, ObsSweepArgs a, int k, double* numer_out, double* tau_out) {
+  a.cond_k = k; a.numer_out = d.numer; a.tau_out = d.taup;
+  launch_obs_sweep(a, h->stream);
+  HIPCHK(hipMemcpyAsync(numer_out, d.numer, sizeof(double) * d.n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(tau_out, d.taup, sizeof(double) * d.n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipGetLastError());
+  return BNMTF_OK;
+}
+
+// the six sums of metrics_from_sums of A B^T (A [I][W], B [J][W], fp64) over a list of entries in any order
+static int obs_list_metric(bnmtf_model* h, const char* fn, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values,
+                           const double* A, const double* B, int W, double sums_out[6]) {
+  if (n < 1 || n >= ((uint64_t)1 << 31)) { set_error("%s: between 1 and 2^31 - 1 entries (n=%llu)", fn, (unsigned long long)n); return BNMTF_EINVAL; }
+  for (uint64_t e = 0; e < n; ++e)
+    if (rows[e] < 0 || rows[e] >= h->I || cols[e] < 0 || cols[e] >= h->J) {
+      set_error("%s: entry %llu (%d, %d) lies outside the %d x %d matrix", fn, (unsigned long long)e, rows[e], cols[e], h->I, h->J);
+      return BNMTF_EINVAL;
+    }
+  const size_t nA = (size_t)h->I * W, nB = (size_t)h->J * W;
+  DevBuf<uint32_t> dr, dc; DevBuf<float> dv; DevBuf<double> dA, dB, part;
+  CHK(dr.alloc(n)); CHK(dc.alloc(n)); CHK(dv.alloc(n));
+  CHK(dA.alloc(nA)); CHK(dB.alloc(nB)); CHK(part.alloc((size_t)obs_metric_blocks(n) * 8));
+  HIPCHK(hipMemcpyAsync(dr.p, rows, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));      // (checked non-negative: the same bits as uint32)
+  HIPCHK(hipMemcpyAsync(dc.p, cols, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dv.p, values, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dA.p, A, nA * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dB.p, B, nB * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  ObsMetricArgs a; memset(&a, 0, sizeof(a));
+  a.row = dr.p; a.col = dc.p; a.val = dv.p; a.n = (size_t)n; a.A = dA.p; a.B = dB.p; a.K = W; a.part = part.p;
+  launch_obs_metric(a, h->obs->out8, h->stream);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipGetLastError());
+  double out8[8];
+  HIPCHK(hipMemcpy(out8, h->obs->out8, sizeof(out8), hipMemcpyDeviceToHost));
+  for (int m = 0; m < 6; ++m) sums_out[m] = out8[m];
+  return BNMTF_OK;
 }
 
 }  // namespace bnmtf
@@ -176,35 +373,16 @@ int bnmtf_obs_create(int I, int J, int K, uint64_t n, const int32_t* rows, const
     set_error("bnmtf_obs_create: unsupported shape I=%d J=%d K=%d (1 <= K <= %d)", I, J, K, BNMTF_OBS_MAX_RANK);
     return BNMTF_EINVAL;
   }
-  ObsLists ls;
-  CHK(obs_lists(I, J, n, rows, cols, values, ls));
-  HIPCHK(hipSetDevice(device));
-  bnmtf_model* h = new bnmtf_model();
-  h->I = I; h->J = J; h->K = K; h->L = 0; h->device = device;
-  h->alpha = alpha; h->beta = beta; h->seed = seed;
-  h->n_obs = (double)n; h->sumR = ls.sumR; h->sumR2 = ls.sumR2;
-  h->rows.nglob = I; h->rows.m = J; h->rows.W = K; h->cols.nglob = J; h->cols.m = I; h->cols.W = K;
-  h->std_built = false;
-  struct Guard { bnmtf_model* h; ~Guard() { if (h) bnmtf_destroy(h); } } guard{h};      // every way out but the last, an exception included, destroys the handle
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { h->stream = nullptr; set_error("hipStreamCreate failed"); return BNMTF_EHIP; }
-  h->obs = new ObsState();
+  ObsCreateGuard guard;
+  CHK(obs_create_common(guard, I, J, K, 0, round_up(K, 4), n, rows, cols, values, lambda_rows, lambda_cols, alpha, beta, seed, device));
+  bnmtf_model* h = guard.h;
   ObsState* s = h->obs;
-  s->n = (size_t)n; s->KP = round_up(K, 4);
-  const char* fl = getenv("BNMTF_OBS_LONG");
-  s->force_long = fl && fl[0] == '1';
-  int rcode;
-  if ((rcode = obs_build_dir(h, s->rows, I, ls.rptr, ls.ridx, ls.rval, lambda_rows)) || (rcode = obs_build_dir(h, s->cols, J, ls.cptr, ls.cidx, ls.cval, lambda_cols)) ||
-      (rcode = dalloc(&s->escratch, (size_t)n, false)) || (rcode = dalloc(&s->part, (size_t)obs_sweep_blocks(J) * 4, false)) ||
-      (rcode = dalloc(&s->scal, 16)))
-    return rcode;
-  h->tau_d = s->scal; h->tau_f = reinterpret_cast<float*>(s->scal + 1); s->out8 = s->scal + 8;
   char buf[512];
   snprintf(buf, sizeof(buf), "bnmf layout=observed I=%d J=%d K=%d entries=%llu (%.3g %% of the matrix) longest_row=%u longest_column=%u "
            "long_form_units=%zu/%zu force_long=%d", I, J, K, (unsigned long long)n, 100.0 * (double)n / ((double)I * (double)J),
            s->rows.longest, s->cols.longest, s->rows.long_units, s->cols.long_units, (int)s->force_long);
   h->description = buf;
-  guard.h = nullptr;
-  *out = h;
+  *out = guard.release();
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
@@ -224,7 +402,7 @@ int bnmtf_obs_build_lists(int I, int J, uint64_t n, const int32_t* rows, const i
 } BNMTF_ABI_GUARD
 
 int bnmf_obs_set_state(bnmtf_handle h, const double* U, const double* V, double tau) try {
-  CHK(obs_check(h, false));
+  CHK(obs_check(h, false, kObsNoState));
   if (!U || !V) { set_error("bnmf_obs_set_state: null argument"); return BNMTF_EINVAL; }
   CHK(obs_put(h, h->obs->rows, U));
   CHK(obs_put(h, h->obs->cols, V));
@@ -235,10 +413,10 @@ int bnmf_obs_set_state(bnmtf_handle h, const double* U, const double* V, double 
 } BNMTF_ABI_GUARD
 
 int bnmf_obs_get_state(bnmtf_handle h, double* U, double* V, double* tau) try {
-  CHK(obs_check(h, true));
+  CHK(obs_check(h, false, kObsSamplerState));
   ObsState* s = h->obs;
-  if (U) CHK(download_matrix(h, s->rows.X, h->I, h->K, s->KP, U));
-  if (V) CHK(download_matrix(h, s->cols.X, h->J, h->K, s->KP, V));
+  if (U) CHK(download_matrix(h, s->rows.X, h->I, h->K, s->stride, U));
+  if (V) CHK(download_matrix(h, s->cols.X, h->J, h->K, s->stride, V));
   if (tau) {
     HIPCHK(hipMemcpyAsync(tau, h->tau_d, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -248,7 +426,7 @@ int bnmf_obs_get_state(bnmtf_handle h, double* U, double* V, double* tau) try {
 
 int bnmf_obs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* V_out, double* tau_out, double* perf_out,
                  double* times_out) try {
-  CHK(obs_check(h, true));
+  CHK(obs_check(h, false, kObsSamplerState));
   if (n_iter < 0) { set_error("negative iteration count"); return BNMTF_EINVAL; }
   if (update < 0 || update > BNMTF_UPDATE_ICM) { set_error("unknown update rule"); return BNMTF_EINVAL; }
   if (n_iter == 0) return BNMTF_OK;
@@ -260,25 +438,20 @@ int bnmf_obs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* V_
   EventList ev;
   CHK(ev.create(times_out ? n_iter + 1 : 0));
   SampleSink sink;
-  sink.add(s->rows.X, h->I, h->K, s->KP, U_out);
-  sink.add(s->cols.X, h->J, h->K, s->KP, V_out);
+  sink.add(s->rows.X, h->I, h->K, s->stride, U_out);
+  sink.add(s->cols.X, h->J, h->K, s->stride, V_out);
   CHK(sink.begin(h, n_iter));
   if (times_out) HIPCHK(hipEventRecord(ev[0], h->stream));
   for (int it = 0; it < n_iter; ++it) {
     CHK(sink.open_slot(it));
-    ObsSweepArgs a = obs_sweep_args(h, true, mode);
+    ObsSweepArgs a = obs_sweep_args(h, true, obs_other(h, true), mode);
     a.snap = sink.slot_for(it, s->rows.X);
     launch_obs_sweep(a, h->stream);
-    a = obs_sweep_args(h, false, mode);
+    a = obs_sweep_args(h, false, obs_other(h, false), mode);
     a.snap = sink.slot_for(it, s->cols.X);
     a.part = s->part;
     launch_obs_sweep(a, h->stream);
-    ObsFinishArgs f; memset(&f, 0, sizeof(f));
-    f.part = s->part; f.nb = obs_sweep_blocks(h->J);
-    f.n_obs = h->n_obs; f.sumR = h->sumR; f.sumR2 = h->sumR2; f.alpha = h->alpha; f.beta = h->beta;
-    f.update = update; f.gunit = mode == kSweepDraw ? h->gunit + it : nullptr;
-    f.tau_d = h->tau_d; f.tau_f = h->tau_f; f.rec = h->rec + (size_t)it * 5;
-    launch_obs_finish(f, h->stream);
+    launch_obs_finish(obs_finish_args(h, update, it), h->stream);
     CHK(sink.close_slot(it));
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], h->stream));
     h->iteration++;
@@ -286,59 +459,25 @@ int bnmf_obs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* V_
   HIPCHK(hipStreamSynchronize(h->stream));
   CHK(sink.finish());
   HIPCHK(hipGetLastError());
-  std::vector<double> rec((size_t)n_iter * 5);
-  HIPCHK(hipMemcpy(rec.data(), h->rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (int it = 0; it < n_iter; ++it) {
-    if (tau_out) tau_out[it] = rec[(size_t)it * 5];
-    if (perf_out) for (int m = 0; m < 3; ++m) perf_out[(size_t)it * 3 + m] = rec[(size_t)it * 5 + 1 + m];
-  }
+  CHK(obs_fetch_rec(h, n_iter, tau_out, perf_out));
   ev.seconds(n_iter, times_out);
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
 int bnmf_obs_cond_params(bnmtf_handle h, int which, int k, double* numer_out, double* tau_out) try {
-  CHK(obs_check(h, true));
+  CHK(obs_check(h, false, kObsSamplerState));
   if (which != 0 && which != 1) { set_error("bnmf_obs_cond_params: which is 0 (rows) or 1 (columns)"); return BNMTF_EINVAL; }
   if (k < 0 || k >= h->K) { set_error("column %d out of range", k); return BNMTF_EINVAL; }
   if (!numer_out || !tau_out) { set_error("bnmf_obs_cond_params: null argument"); return BNMTF_EINVAL; }
-  ObsList& d = which == 0 ? h->obs->rows : h->obs->cols;
-  ObsSweepArgs a = obs_sweep_args(h, which == 0, kSweepDraw);
-  a.cond_k = k; a.numer_out = d.numer; a.tau_out = d.taup;
-  launch_obs_sweep(a, h->stream);
-  HIPCHK(hipMemcpyAsync(numer_out, d.numer, sizeof(double) * d.n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(tau_out, d.taup, sizeof(double) * d.n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipGetLastError());
-  return BNMTF_OK;
+  const bool rows = which == 0;
+  return obs_cond_params_dir(h, rows ? h->obs->rows : h->obs->cols, obs_sweep_args(h, rows, obs_other(h, rows), kSweepDraw), k, numer_out, tau_out);
 } BNMTF_ABI_GUARD
 
 int bnmf_obs_metric_sums(bnmtf_handle h, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values,
                          const double* A, const double* B, double sums_out[6]) try {
-  CHK(obs_check(h, false));
+  CHK(obs_check(h, false, kObsNoState));
   if (!rows || !cols || !values || !A || !B || !sums_out) { set_error("bnmf_obs_metric_sums: null argument"); return BNMTF_EINVAL; }
-  if (n < 1 || n >= ((uint64_t)1 << 31)) { set_error("bnmf_obs_metric_sums: between 1 and 2^31 - 1 entries (n=%llu)", (unsigned long long)n); return BNMTF_EINVAL; }
-  for (uint64_t e = 0; e < n; ++e)
-    if (rows[e] < 0 || rows[e] >= h->I || cols[e] < 0 || cols[e] >= h->J) {
-      set_error("bnmf_obs_metric_sums: entry %llu (%d, %d) lies outside the %d x %d matrix", (unsigned long long)e, rows[e], cols[e], h->I, h->J);
-      return BNMTF_EINVAL;
-    }
-  DevBuf<uint32_t> dr, dc; DevBuf<float> dv; DevBuf<double> dA, dB, part;
-  CHK(dr.alloc(n)); CHK(dc.alloc(n)); CHK(dv.alloc(n));
-  CHK(dA.alloc((size_t)h->I * h->K)); CHK(dB.alloc((size_t)h->J * h->K)); CHK(part.alloc((size_t)obs_metric_blocks(n) * 8));
-  HIPCHK(hipMemcpyAsync(dr.p, rows, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));      // (checked non-negative: the same bits as uint32)
-  HIPCHK(hipMemcpyAsync(dc.p, cols, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(dv.p, values, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(dA.p, A, (size_t)h->I * h->K * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(dB.p, B, (size_t)h->J * h->K * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  ObsMetricArgs a; memset(&a, 0, sizeof(a));
-  a.row = dr.p; a.col = dc.p; a.val = dv.p; a.n = (size_t)n; a.A = dA.p; a.B = dB.p; a.K = h->K; a.part = part.p;
-  launch_obs_metric(a, h->obs->out8, h->stream);
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipGetLastError());
-  double out8[8];
-  HIPCHK(hipMemcpy(out8, h->obs->out8, sizeof(out8), hipMemcpyDeviceToHost));
-  for (int m = 0; m < 6; ++m) sums_out[m] = out8[m];
-  return BNMTF_OK;
+  return obs_list_metric(h, "bnmf_obs_metric_sums", n, rows, cols, values, A, B, h->K, sums_out);
 } BNMTF_ABI_GUARD
 
 }  // extern "C"
@@ -346,64 +485,14 @@ int bnmf_obs_metric_sums(bnmtf_handle h, uint64_t n, const int32_t* rows, const 
 // ---- the variational two-factor model on the handle's lists (kernel_obs_vb.hip; DESIGN.md section 2.7) -----------------------
 namespace bnmtf {
 
-static int vbo_check(bnmtf_model* h, bool need_state) {
-  if (!h || !h->obs) { set_error("not a handle of bnmtf_obs_create"); return BNMTF_EINVAL; }
-  if (need_state && !(h->obs->vb_state && h->have_state)) { set_error("bnmf_vbo_set_state has not been called"); return BNMTF_ESTATE; }
-  HIPCHK(hipSetDevice(h->device));
-  return BNMTF_OK;
-}
-
 static int vbo_alloc(bnmtf_model* h) {
   ObsState* s = h->obs;
   if (s->vb_alloc) return BNMTF_OK;
-  for (ObsList* d : {&s->rows, &s->cols}) {
-    if (!d->mu) CHK(dalloc(&d->mu, (size_t)d->n * s->KP));
-    if (!d->tauq) CHK(dalloc(&d->tauq, (size_t)d->n * s->KP));
-    if (!d->var) CHK(dalloc(&d->var, (size_t)d->n * s->KP));
-    if (!d->S2T) CHK(dalloc(&d->S2T, (size_t)h->K * d->ldT));
-    if (!d->vstat) CHK(dalloc(&d->vstat, (size_t)obs_sweep_blocks(d->n) * 6));
-  }
+  CHK(obs_alloc_q(h, s->rows, true));
+  CHK(obs_alloc_q(h, s->cols, true));
   if (!s->esd_part) CHK(dalloc(&s->esd_part, (size_t)obs_vb_esd_blocks(h->I)));
   s->vb_alloc = true;
   return BNMTF_OK;
-}
-
-// fp64 host [n][K] x 4 -> the direction's fp32 q: mu, tau, var [n][KP]; the expectation in X / XT; S2 = var + exp^2 in S2T
-static int vbo_put(bnmtf_model* h, ObsList& d, const double* mu, const double* tau, const double* ex, const double* var) {
-  const int K = h->K, KP = h->obs->KP;
-  const size_t nk = (size_t)d.n * KP;
-  std::vector<float> m(nk, 0.f), t(nk, 0.f), v(nk, 0.f), s2((size_t)K * d.ldT, 0.f);
-  for (int u = 0; u < d.n; ++u)
-    for (int k = 0; k < K; ++k) {
-      const size_t src = (size_t)u * K + k, at = (size_t)u * KP + k;
-      m[at] = (float)mu[src]; t[at] = (float)tau[src]; v[at] = (float)var[src];
-      const float e = (float)ex[src];
-      s2[(size_t)k * d.ldT + u] = fmaf(e, e, v[at]);              // (as the sweep forms it)
-    }
-  CHK(obs_put(h, d, ex));
-  HIPCHK(hipMemcpyAsync(d.mu, m.data(), nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(d.tauq, t.data(), nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(d.var, v.data(), nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(d.S2T, s2.data(), s2.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return BNMTF_OK;
-}
-
-static ObsVbSweepArgs vbo_sweep_args(bnmtf_model* h, bool rows) {
-  ObsState* s = h->obs;
-  ObsList& d = rows ? s->rows : s->cols;
-  ObsList& o = rows ? s->cols : s->rows;
-  ObsVbSweepArgs a; memset(&a, 0, sizeof(a));
-  a.ptr = d.ptr; a.idx = d.idx; a.val = d.val;
-  a.n = d.n; a.m = o.n; a.K = h->K; a.KP = s->KP;
-  a.only_k = -1; a.moments = 1; a.force_long = s->force_long ? 1 : 0;
-  a.lambda = d.lambda;
-  a.X = d.X; a.XT = d.XT; a.S2T = d.S2T; a.ldT = d.ldT;
-  a.mu = d.mu; a.tauq = d.tauq; a.var = d.var;
-  a.Xo = o.X; a.XoT = o.XT; a.S2oT = o.S2T; a.ldT_o = o.ldT;
-  a.escratch = s->escratch;
-  a.tau = h->tau_f;
-  return a;
 }
 
 }  // namespace bnmtf
@@ -412,12 +501,12 @@ extern "C" {
 
 int bnmf_vbo_set_state(bnmtf_handle h, const double* muU, const double* tauU, const double* expU, const double* varU,
                        const double* muV, const double* tauV, const double* expV, const double* varV, double exptau) try {
-  CHK(vbo_check(h, false));
+  CHK(obs_check(h, false, kObsNoState));
   if (!muU || !tauU || !expU || !varU || !muV || !tauV || !expV || !varV) { set_error("bnmf_vbo_set_state: null argument"); return BNMTF_EINVAL; }
   CHK(vbo_alloc(h));
   h->obs->vb_state = false;
-  CHK(vbo_put(h, h->obs->rows, muU, tauU, expU, varU));
-  CHK(vbo_put(h, h->obs->cols, muV, tauV, expV, varV));
+  CHK(obs_put_q(h, h->obs->rows, muU, tauU, expU, varU));
+  CHK(obs_put_q(h, h->obs->cols, muV, tauV, expV, varV));
   CHK(set_tau(h, exptau));
   h->have_state = true;
   h->obs->vb_state = true;
@@ -426,22 +515,22 @@ int bnmf_vbo_set_state(bnmtf_handle h, const double* muU, const double* tauU, co
 
 int bnmf_vbo_get_state(bnmtf_handle h, double* muU, double* tauU, double* expU, double* varU,
                        double* muV, double* tauV, double* expV, double* varV) try {
-  CHK(vbo_check(h, true));
+  CHK(obs_check(h, false, kObsVbState));
   ObsState* s = h->obs;
   ObsList& r = s->rows; ObsList& c = s->cols;
-  if (muU) CHK(download_matrix(h, r.mu, h->I, h->K, s->KP, muU));
-  if (tauU) CHK(download_matrix(h, r.tauq, h->I, h->K, s->KP, tauU));
-  if (expU) CHK(download_matrix(h, r.X, h->I, h->K, s->KP, expU));
-  if (varU) CHK(download_matrix(h, r.var, h->I, h->K, s->KP, varU));
-  if (muV) CHK(download_matrix(h, c.mu, h->J, h->K, s->KP, muV));
-  if (tauV) CHK(download_matrix(h, c.tauq, h->J, h->K, s->KP, tauV));
-  if (expV) CHK(download_matrix(h, c.X, h->J, h->K, s->KP, expV));
-  if (varV) CHK(download_matrix(h, c.var, h->J, h->K, s->KP, varV));
+  if (muU) CHK(download_matrix(h, r.mu, h->I, h->K, s->stride, muU));
+  if (tauU) CHK(download_matrix(h, r.tauq, h->I, h->K, s->stride, tauU));
+  if (expU) CHK(download_matrix(h, r.X, h->I, h->K, s->stride, expU));
+  if (varU) CHK(download_matrix(h, r.var, h->I, h->K, s->stride, varU));
+  if (muV) CHK(download_matrix(h, c.mu, h->J, h->K, s->stride, muV));
+  if (tauV) CHK(download_matrix(h, c.tauq, h->J, h->K, s->stride, tauV));
+  if (expV) CHK(download_matrix(h, c.X, h->J, h->K, s->stride, expV));
+  if (varV) CHK(download_matrix(h, c.var, h->J, h->K, s->stride, varV));
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
 int bnmf_vbo_run(bnmtf_handle h, int n_iter, double* exptau_out, double* perf_out, double* elbo_terms_out, double* times_out) try {
-  CHK(vbo_check(h, true));
+  CHK(obs_check(h, false, kObsVbState));
   if (n_iter < 0) { set_error("negative iteration count"); return BNMTF_EINVAL; }
   if (n_iter == 0) return BNMTF_OK;
   ObsState* s = h->obs;
@@ -450,18 +539,13 @@ int bnmf_vbo_run(bnmtf_handle h, int n_iter, double* exptau_out, double* perf_ou
   CHK(ev.create(times_out ? n_iter + 1 : 0));
   if (times_out) HIPCHK(hipEventRecord(ev[0], h->stream));
   for (int it = 0; it < n_iter; ++it) {
-    ObsVbSweepArgs a = vbo_sweep_args(h, true);
+    ObsVbSweepArgs a = obs_vb_sweep_args(h, true, obs_other(h, true));
     a.stat = s->rows.vstat;
     launch_obs_vb_sweep(a, h->stream);
-    a = vbo_sweep_args(h, false);
+    a = obs_vb_sweep_args(h, false, obs_other(h, false));
     a.stat = s->cols.vstat; a.part = s->part;
     launch_obs_vb_sweep(a, h->stream);
-    ObsVbFinishArgs f; memset(&f, 0, sizeof(f));
-    f.stat_r = s->rows.vstat; f.nb_r = obs_sweep_blocks(h->I);
-    f.stat_c = s->cols.vstat; f.part = s->part; f.nb_c = obs_sweep_blocks(h->J);
-    f.n_obs = h->n_obs; f.sumR = h->sumR; f.sumR2 = h->sumR2; f.alpha = h->alpha; f.beta = h->beta;
-    f.tau_d = h->tau_d; f.tau_f = h->tau_f; f.rec = h->vb_rec + (size_t)it * 16;
-    launch_obs_vb_finish(f, h->stream);
+    launch_obs_vb_finish(obs_vb_finish_args(h, it), h->stream);
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], h->stream));
     h->iteration++;
   }
@@ -475,10 +559,10 @@ int bnmf_vbo_run(bnmtf_handle h, int n_iter, double* exptau_out, double* perf_ou
 } BNMTF_ABI_GUARD
 
 int bnmf_vbo_update(bnmtf_handle h, int which, int k, int moments) try {
-  CHK(vbo_check(h, true));
+  CHK(obs_check(h, false, kObsVbState));
   if (which != 0 && which != 1) { set_error("bnmf_vbo_update: which is 0 (rows) or 1 (columns)"); return BNMTF_EINVAL; }
   if (k < 0 || k >= h->K) { set_error("column %d out of range", k); return BNMTF_EINVAL; }
-  ObsVbSweepArgs a = vbo_sweep_args(h, which == 0);
+  ObsVbSweepArgs a = obs_vb_sweep_args(h, which == 0, obs_other(h, which == 0));
   a.only_k = k; a.moments = moments ? 1 : 0;
   launch_obs_vb_sweep(a, h->stream);
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -487,11 +571,11 @@ int bnmf_vbo_update(bnmtf_handle h, int which, int k, int moments) try {
 } BNMTF_ABI_GUARD
 
 int bnmf_vbo_exp_square_diff(bnmtf_handle h, double* out) try {
-  CHK(vbo_check(h, true));
+  CHK(obs_check(h, false, kObsVbState));
   if (!out) { set_error("bnmf_vbo_exp_square_diff: null argument"); return BNMTF_EINVAL; }
   ObsState* s = h->obs;
   ObsVbEsdArgs a; memset(&a, 0, sizeof(a));
-  a.ptr = s->rows.ptr; a.idx = s->rows.idx; a.val = s->rows.val; a.n = h->I; a.K = h->K; a.KP = s->KP;
+  a.ptr = s->rows.ptr; a.idx = s->rows.idx; a.val = s->rows.val; a.n = h->I; a.K = h->K; a.KP = s->stride;
   a.X = s->rows.X; a.var = s->rows.var; a.Xo = s->cols.X; a.varo = s->cols.var; a.part = s->esd_part;
   launch_obs_vb_esd(a, s->out8, h->stream);
   HIPCHK(hipMemcpyAsync(out, s->out8, sizeof(double), hipMemcpyDeviceToHost, h->stream));

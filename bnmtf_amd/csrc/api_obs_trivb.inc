@@ -1,7 +1,8 @@
 // The variational tri-factorisation on the observed-entry layout (C ABI part 8: bnmtf_vb_observed) -- included behind
 // api_obs_tri.inc at the end of api.hip.  Five entry points on the handle of bnmtf_otri_create; the first bnmtf_otvb_set_state
-// allocates what the variational model holds beyond the sampler's: q's mu, tau and variance of F and G [.][32] beside the
-// expectations in rows.X / cols.X, the second moments of the two effective factors, q(S) in the model's muS, tauS, varS beside S,
+// allocates what the variational model holds beyond the sampler's -- the variational parts of api_obs.inc's ObsState: q's mu, tau
+// and variance of F and G [.][32] beside the expectations in rows.X / cols.X (obs_alloc_q, obs_put_q: the two-factor model's,
+// without an S2T), the second moments of the two effective factors --, and in the model q(S) in muS, tauS, varS beside S,
 // the masked variance sums mv_rows [I][32] / mv_cols [J][32], the chain's permuted system, the half sweeps' partial sums.  Nothing
 // of size I x J.  The iteration (DESIGN.md section 2.7; bnmtf_vb_optimised.py:172-192 restated on the observed entries): the S
 // entries on the second-moment system of kernel_ssys.hip with its per-column inputs from obs_tri_gram_vb_kernel, the F and G half
@@ -10,23 +11,11 @@
 
 namespace bnmtf {
 
-static int otvb_check(bnmtf_model* h, bool need_state) {
-  if (!h || !h->otri) { set_error("not a handle of bnmtf_otri_create"); return BNMTF_EINVAL; }
-  if (need_state && !(h->otri->vb_state && h->have_state)) { set_error("bnmtf_otvb_set_state has not been called"); return BNMTF_ESTATE; }
-  HIPCHK(hipSetDevice(h->device));
-  return BNMTF_OK;
-}
-
 static int otvb_alloc(bnmtf_model* h) {
-  ObsTriState* s = h->otri;
+  ObsState* s = h->obs;
   if (s->vb_alloc) return BNMTF_OK;
-  for (ObsList* d : {&s->rows, &s->cols}) {
-    const size_t nk = (size_t)d->n * kObsTriStride;
-    if (!d->mu) CHK(dalloc(&d->mu, nk));
-    if (!d->tauq) CHK(dalloc(&d->tauq, nk));
-    if (!d->var) CHK(dalloc(&d->var, nk));
-    if (!d->vstat) CHK(dalloc(&d->vstat, (size_t)obs_sweep_blocks(d->n) * 6));
-  }
+  CHK(obs_alloc_q(h, s->rows, false));          // (no S2T: the half sweeps gather the effective factors' second moments)
+  CHK(obs_alloc_q(h, s->cols, false));
   if (!s->ceffS2) CHK(dalloc(&s->ceffS2, (size_t)h->J * kObsTriStride));
   if (!s->ceffS2T) CHK(dalloc(&s->ceffS2T, (size_t)h->K * s->cols.ldT));
   if (!s->reffS2) CHK(dalloc(&s->reffS2, (size_t)h->I * kObsTriStride));
@@ -44,26 +33,9 @@ static int otvb_alloc(bnmtf_model* h) {
   return BNMTF_OK;
 }
 
-// fp64 host [n][W] x 4 -> the direction's fp32 q: mu, tau, var [n][32]; the expectation in X / XT (otri_put)
-static int otvb_put(bnmtf_model* h, ObsList& d, int W, const double* mu, const double* tau, const double* ex, const double* var) {
-  const size_t nk = (size_t)d.n * kObsTriStride;
-  std::vector<float> m(nk, 0.f), t(nk, 0.f), v(nk, 0.f);
-  for (int u = 0; u < d.n; ++u)
-    for (int k = 0; k < W; ++k) {
-      const size_t src = (size_t)u * W + k, at = (size_t)u * kObsTriStride + k;
-      m[at] = (float)mu[src]; t[at] = (float)tau[src]; v[at] = (float)var[src];
-    }
-  CHK(otri_put(h, d, W, ex));
-  HIPCHK(hipMemcpyAsync(d.mu, m.data(), nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(d.tauq, t.data(), nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(d.var, v.data(), nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return BNMTF_OK;
-}
-
 // W~_j (packed, with the variance sums on the diagonal), Pv_j and mv_cols of the current q(F): one pass over the column list
 static void otvb_enqueue_gram(bnmtf_model* h) {
-  ObsTriState* s = h->otri;
+  ObsState* s = h->obs;
   ObsTriGramArgs w; memset(&w, 0, sizeof(w));
   w.ptr = s->cols.ptr; w.idx = s->cols.idx; w.val = s->cols.val; w.n = h->J; w.K = h->K; w.F = s->rows.X; w.Wc = h->ss_Wc; w.Pv = s->Pv;
   ObsTriGramVbArgs v; v.varF = s->rows.var; v.mv = h->mv_cols;
@@ -73,7 +45,7 @@ static void otvb_enqueue_gram(bnmtf_model* h) {
 // (A~, b) of the second-moment S system for the current q(F), q(G) and r = b - A~ E[S]: enqueue_tri_ssys's sequence with the
 // per-column inputs from the column list (gram_current: they are there, formed behind the F sweep)
 static void otvb_enqueue_ssys(bnmtf_model* h, bool gram_current) {
-  ObsTriState* s = h->otri;
+  ObsState* s = h->obs;
   const int K = h->K, L = h->L, J = h->J, n2 = K * L;
   if (!gram_current) otvb_enqueue_gram(h);
   GammaPackArgs gp; memset(&gp, 0, sizeof(gp));
@@ -106,7 +78,7 @@ static void otvb_enqueue_chain(bnmtf_model* h, const int* order_dev, int n_order
 // what a half sweep of F (rows) or G needs of the other factor and S: the effective factor (mean and second moment) and, for F,
 // the masked variance sums of G over the row list (those of F over the column list come with the column Grams)
 static void otvb_enqueue_side(bnmtf_model* h, bool rows) {
-  ObsTriState* s = h->otri;
+  ObsState* s = h->obs;
   ObsTriVbEffArgs e; memset(&e, 0, sizeof(e));
   e.S = h->S; e.varS = h->varS; e.K = h->K; e.L = h->L;
   if (rows) { e.X = s->cols.X; e.varX = s->cols.var; e.n = h->J; e.transposeS = 1; e.out = s->ceffX; e.out2 = s->ceffS2; e.outT = s->ceffXT; e.out2T = s->ceffS2T; e.ldT = s->cols.ldT; }
@@ -119,20 +91,10 @@ static void otvb_enqueue_side(bnmtf_model* h, bool rows) {
   }
 }
 
+// the half sweep of F (rows) or G against its effective factor, with the column order and the covariance term's operands
 static ObsVbSweepArgs otvb_sweep_args(bnmtf_model* h, bool rows, const int* order_dev) {
-  ObsTriState* s = h->otri;
-  ObsList& d = rows ? s->rows : s->cols;
-  ObsVbSweepArgs a; memset(&a, 0, sizeof(a));
-  a.ptr = d.ptr; a.idx = d.idx; a.val = d.val;
-  a.n = d.n; a.m = rows ? h->J : h->I; a.K = rows ? h->K : h->L; a.KP = kObsTriStride;
-  a.only_k = -1; a.moments = 1; a.force_long = s->force_long ? 1 : 0;
-  a.lambda = d.lambda;
-  a.X = d.X; a.ldT = d.ldT;                       // (XT / S2T: not written by this instantiation)
-  a.mu = d.mu; a.tauq = d.tauq; a.var = d.var;
-  a.Xo = rows ? s->ceffX : s->reffX; a.XoT = rows ? s->ceffXT : s->reffXT; a.S2oT = rows ? s->ceffS2T : s->reffS2T;
-  a.ldT_o = rows ? s->cols.ldT : s->rows.ldT;
-  a.escratch = s->escratch;
-  a.tau = h->tau_f;
+  ObsVbSweepArgs a = obs_vb_sweep_args(h, rows, otri_other(h, rows));
+  a.XT = nullptr;                                  // (XT / S2T: not written by this instantiation; a tri list owns no S2T)
   a.order = order_dev; a.cov_S = h->S; a.cov_mv = rows ? h->mv_rows : h->mv_cols;
   if (rows) { a.cov_sc = h->L; a.cov_st = 1; a.cov_n = h->L; }       // column k of F, inner l: S[k][l] (tri_sweep_args)
   else      { a.cov_sc = 1; a.cov_st = h->L; a.cov_n = h->K; }       // column l of G, inner k: S[k][l]
@@ -154,15 +116,15 @@ extern "C" {
 int bnmtf_otvb_set_state(bnmtf_handle h, const double* muF, const double* tauF, const double* expF, const double* varF,
                          const double* muS, const double* tauS, const double* expS, const double* varS,
                          const double* muG, const double* tauG, const double* expG, const double* varG, double exptau) try {
-  CHK(otvb_check(h, false));
+  CHK(obs_check(h, true, kObsNoState));
   if (!muF || !tauF || !expF || !varF || !muS || !tauS || !expS || !varS || !muG || !tauG || !expG || !varG) {
     set_error("bnmtf_otvb_set_state: null argument"); return BNMTF_EINVAL;
   }
   CHK(otvb_alloc(h));
-  h->otri->vb_state = false;
+  h->obs->vb_state = false;
   h->have_state = false;                 // (the expectations are replaced: a sampler's state ends here)
-  CHK(otvb_put(h, h->otri->rows, h->K, muF, tauF, expF, varF));
-  CHK(otvb_put(h, h->otri->cols, h->L, muG, tauG, expG, varG));
+  CHK(obs_put_q(h, h->obs->rows, muF, tauF, expF, varF));
+  CHK(obs_put_q(h, h->obs->cols, muG, tauG, expG, varG));
   const size_t n2 = (size_t)h->K * h->L;
   std::vector<float> tmp(n2);
   const double* src[4] = {muS, tauS, expS, varS};
@@ -174,15 +136,15 @@ int bnmtf_otvb_set_state(bnmtf_handle h, const double* muF, const double* tauF, 
   }
   CHK(set_tau(h, exptau));
   h->have_state = true;
-  h->otri->vb_state = true;
+  h->obs->vb_state = true;
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
 int bnmtf_otvb_get_state(bnmtf_handle h, double* muF, double* tauF, double* expF, double* varF,
                          double* muS, double* tauS, double* expS, double* varS,
                          double* muG, double* tauG, double* expG, double* varG) try {
-  CHK(otvb_check(h, true));
-  ObsList& r = h->otri->rows; ObsList& c = h->otri->cols;
+  CHK(obs_check(h, true, kObsVbState));
+  ObsList& r = h->obs->rows; ObsList& c = h->obs->cols;
   if (muF) CHK(download_matrix(h, r.mu, h->I, h->K, kObsTriStride, muF));
   if (tauF) CHK(download_matrix(h, r.tauq, h->I, h->K, kObsTriStride, tauF));
   if (expF) CHK(download_matrix(h, r.X, h->I, h->K, kObsTriStride, expF));
@@ -200,7 +162,7 @@ int bnmtf_otvb_get_state(bnmtf_handle h, double* muF, double* tauF, double* expF
 // update_F(k) (which = 0), update_S(k, l) (which = 1), update_G(l) (which = 2) for the state the device holds; moments != 0 also
 // the matching update_exp_*
 int bnmtf_otvb_update(bnmtf_handle h, int which, int k, int l, int moments) try {
-  CHK(otvb_check(h, true));
+  CHK(obs_check(h, true, kObsVbState));
   if (which < 0 || which > 2) { set_error("bnmtf_otvb_update: which is 0 (F), 1 (S) or 2 (G)"); return BNMTF_EINVAL; }
   if (which == 1) {
     if (k < 0 || k >= h->K || l < 0 || l >= h->L) { set_error("S index out of range"); return BNMTF_EINVAL; }
@@ -226,9 +188,9 @@ int bnmtf_otvb_update(bnmtf_handle h, int which, int k, int l, int moments) try 
 } BNMTF_ABI_GUARD
 
 int bnmtf_otvb_exp_square_diff(bnmtf_handle h, double* out) try {
-  CHK(otvb_check(h, true));
+  CHK(obs_check(h, true, kObsVbState));
   if (!out) { set_error("bnmtf_otvb_exp_square_diff: null argument"); return BNMTF_EINVAL; }
-  ObsTriState* s = h->otri;
+  ObsState* s = h->obs;
   ObsTriVbEsdArgs a; memset(&a, 0, sizeof(a));
   a.ptr = s->rows.ptr; a.idx = s->rows.idx; a.val = s->rows.val; a.n = h->I; a.K = h->K; a.L = h->L;
   a.F = s->rows.X; a.varF = s->rows.var; a.G = s->cols.X; a.varG = s->cols.var; a.S = h->S; a.varS = h->varS; a.part = s->esd_part;
@@ -243,11 +205,11 @@ int bnmtf_otvb_exp_square_diff(bnmtf_handle h, double* out) try {
 // order, each a list of valid indices; they go to the device once.  Outputs as bnmtf_vb_run's.
 int bnmtf_otvb_run(bnmtf_handle h, int n_iter, const int32_t* orders, double* exptau_out, double* perf_out, double* elbo_terms_out,
                    double* times_out) try {
-  CHK(otvb_check(h, true));
+  CHK(obs_check(h, true, kObsVbState));
   if (n_iter < 0) { set_error("negative iteration count"); return BNMTF_EINVAL; }
   if (n_iter == 0) return BNMTF_OK;
   if (!orders) { set_error("bnmtf_otvb_run: orders required"); return BNMTF_EINVAL; }
-  ObsTriState* s = h->otri;
+  ObsState* s = h->obs;
   const int K = h->K, L = h->L, n2 = K * L, per = n2 + K + L;
   for (int it = 0; it < n_iter; ++it)          // (the kernels index S, F and G with them)
     for (int t = 0; t < per; ++t) {
@@ -283,10 +245,7 @@ int bnmtf_otvb_run(bnmtf_handle h, int n_iter, const int32_t* orders, double* ex
     t3.rows = h->J; t3.K = K; t3.L = L; t3.G = s->cols.X; t3.S = h->S; t3.mv = h->mv_cols; t3.part = h->tri_third;
     launch_tri_third(t3, h->stream);
     ObsTriVbFinishArgs f; memset(&f, 0, sizeof(f));
-    f.f.stat_r = s->rows.vstat; f.f.nb_r = obs_sweep_blocks(h->I);
-    f.f.stat_c = s->cols.vstat; f.f.part = s->part; f.f.nb_c = obs_sweep_blocks(h->J);
-    f.f.n_obs = h->n_obs; f.f.sumR = h->sumR; f.f.sumR2 = h->sumR2; f.f.alpha = h->alpha; f.f.beta = h->beta;
-    f.f.tau_d = h->tau_d; f.f.tau_f = h->tau_f; f.f.rec = h->vb_rec + (size_t)it * 16;
+    f.f = obs_vb_finish_args(h, it);
     f.third = h->tri_third; f.n_third = tri_third_blocks(h->J);
     launch_obs_trivb_finish(f, h->stream);
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], h->stream));

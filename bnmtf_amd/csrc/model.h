@@ -105,8 +105,7 @@ struct Dir {
 
 struct Comm;   // RCCL wrapper (comm.cpp)
 struct NpState;   // the non-probabilistic models' buffers (api_np.inc)
-struct ObsState;  // the observed-entry layout's lists and factors (api_obs.inc)
-struct ObsTriState;   // the tri-factorisation on that layout: lists, factors, effective factors (api_obs_tri.inc)
+struct ObsState;  // the observed-entry layout's lists and factors, two factors or three (api_obs.inc)
 
 // A model small enough for the one-launch path (kernel_small.hip, api_small.inc): ONE device allocation holds its static tables
 // (both masked operands, slot / segment / permutation tables, prior rates) and its state (factors, q of the missing entries,
@@ -214,8 +213,7 @@ struct bnmtf_model {
   hipEvent_t snap_ready[8] = {nullptr}, copy_done[8] = {nullptr};
   double create_ms = 0.0;                                   // wall time of bnmtf_create (host layout + uploads)
   bnmtf::NpState* np = nullptr;                             // a handle of bnmtf_np_create (nmf_np / nmtf_np): its buffers
-  bnmtf::ObsState* obs = nullptr;                           // a handle of bnmtf_obs_create (layout='observed'): its buffers
-  bnmtf::ObsTriState* otri = nullptr;                       // a handle of bnmtf_otri_create (the tri-factorisation, layout='observed'): its buffers
+  bnmtf::ObsState* obs = nullptr;                           // a handle of bnmtf_obs_create or (L > 0) bnmtf_otri_create (layout='observed'): its buffers
   // held-out performance per iteration (bnmtf_set_heldout; api_heldout.inc, kernel_heldout.hip): the row-sorted list of the mask's
   // entries, the blocks' partial sums, the record [iterations][8] of the last run call and the iterations it holds
   uint32_t* held_rowptr = nullptr; uint32_t* held_col = nullptr; float* held_val = nullptr; size_t held_n = 0;

@@ -14,7 +14,7 @@ import math
 
 import numpy as np
 
-from . import _lib, _observed
+from . import _lib
 from ._base import metrics_from_sums
 from .bnmf_gibbs import bnmf_gibbs_optimised
 
@@ -40,8 +40,7 @@ class nmf_icm(bnmf_gibbs_optimised):
         """:114-150.  One device call runs all iterations; returns None like the reference.  M_test: the held-out metrics of the
         point estimate every iteration ends with, in all_performances_test (see bnmf_gibbs_optimised.run)."""
         if self._layout == 'observed':          # (DESIGN.md section 2.7: the ICM rules on the observed-entry kernel)
-            if M_test is not None:
-                _observed.refuse(self, "run(M_test=)", "held-out curves are kept by the dense layout only; use predict(M_test) after the run")
+            self._check_heldout(M_test)
             _lib.check(_lib.lib().bnmtf_set_minimum_tn(self._handle(), float(minimum_TN)))
             it, _, _, taus, perf, times = self._run_observed(iterations, _lib.UPDATE_ICM, False, None, None)
             return self._finish_icm(it, taus, perf, times)

@@ -7,7 +7,7 @@ import math
 
 import numpy as np
 
-from . import _lib, _observed
+from . import _lib
 from ._base import metrics_from_sums
 from .bnmtf_gibbs import bnmtf_gibbs_optimised
 from .nmf_icm import gamma_mode
@@ -22,8 +22,7 @@ class nmtf_icm(bnmtf_gibbs_optimised):
     def run(self, iterations, minimum_TN=0., *, M_test=None):
         """:132-173; returns None like the reference.  M_test: see nmf_icm.run."""
         if self._layout == 'observed':          # (DESIGN.md section 2.7: the ICM rules on the observed-entry kernels)
-            if M_test is not None:
-                _observed.refuse(self, "run(M_test=)", "held-out curves are kept by the dense layout only; use predict(M_test) after the run")
+            self._check_heldout(M_test)
             _lib.check(_lib.lib().bnmtf_set_minimum_tn(self._handle(), float(minimum_TN)))
             it, _, _, _, taus, perf, times = self._run_observed(iterations, _lib.UPDATE_ICM, False, None, None)
             return self._finish_icm(it, taus, perf, times)

@@ -2,11 +2,14 @@
 // HIP runtime, under AddressSanitizer + UBSan (`make asan`) or ThreadSanitizer (`make tsan`).  Kernels do not run, so no number
 // that comes back means anything; what is checked is the host code the calls go through: bnmtf_create's layout passes (worker
 // threads, slot tables -- also on their own, from a real mask --, shard ranges, the hand-over table sizes), the arenas and pools of created / destroyed models, every
-// host<->"device" copy's extent (device memory is heap memory here), the sample ring of run(), run_many's batching and lock-step walks, and the
-// in-process multi-rank rendezvous of comm.hip with one host thread per rank.
+// host<->"device" copy's extent (device memory is heap memory here), the sample ring of run(), run_many's batching and lock-step walks, the
+// in-process multi-rank rendezvous of comm.hip with one host thread per rank, and the observed-entry layout's 24 entry points
+// (api_obs*.inc): one state for four models, its lazily allocated variational part, every refusal and the create path's guard.
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
+#include <numeric>
 #include <random>
 #include <thread>
 #include <vector>
@@ -380,6 +383,172 @@ static void tri_blocks(const Data& d) {
   OK(bnmtf_destroy(c0)); OK(bnmtf_destroy(c1)); OK(bnmtf_destroy(t));
 }
 
+// ---- the observed-entry layout (api_obs.inc, api_obs_tri.inc, api_obs_trivb.inc) ------------------------------------------------
+// the mask's entries as the list the layout's calls take, in shuffled order
+struct Entries { std::vector<int32_t> rows, cols; std::vector<float> vals; uint64_t n; };
+static Entries entry_list(const Data& d, unsigned seed) {
+  std::vector<size_t> at;
+  for (size_t p = 0; p < d.M.size(); ++p) if (d.M[p]) at.push_back(p);
+  std::mt19937 g(seed);
+  std::shuffle(at.begin(), at.end(), g);
+  Entries e;
+  for (size_t p : at) { e.rows.push_back((int32_t)(p / d.J)); e.cols.push_back((int32_t)(p % d.J)); e.vals.push_back(d.R[p]); }
+  e.n = at.size();
+  return e;
+}
+
+// L = 0: bnmtf_obs_create, else bnmtf_otri_create; the status comes back, the handle in *h
+static int obs_create(const Data& d, const Entries& e, int K, int L, bnmtf_handle* h) {
+  std::vector<double> lr((size_t)d.I * K, 0.1), lc((size_t)d.J * (L ? L : K), 0.1), ls((size_t)K * (L ? L : 1), 0.1);
+  if (L == 0) return bnmtf_obs_create(d.I, d.J, K, e.n, e.rows.data(), e.cols.data(), e.vals.data(), lr.data(), lc.data(), 1.0, 1.0, 7, 0, h);
+  return bnmtf_otri_create(d.I, d.J, K, L, e.n, e.rows.data(), e.cols.data(), e.vals.data(), lr.data(), ls.data(), lc.data(), 1.0, 1.0, 7, 0, h);
+}
+
+// a create that must be refused, or fail, and leave nothing behind
+static void obs_create_refused(const Data& d, const Entries& e, int K, int L) {
+  const long live = hipstub_live_allocs();
+  bnmtf_handle h = reinterpret_cast<bnmtf_handle>(&h);
+  EXPECT_ERR(obs_create(d, e, K, L, &h));
+  if (h != nullptr || hipstub_live_allocs() != live) { fprintf(stderr, "a refused create (K=%d L=%d) left a handle or %ld allocations\n", K, L, hipstub_live_allocs() - live); exit(2); }
+}
+
+// create .. destroy of one handle: the sampler's calls, the variational ones (whose first set_state allocates), the sampler's again
+static void obs_walk(int I, int J, int K, int L, unsigned seed) {
+  const Data d = make_data(I, J, 0.8, seed);
+  const Entries e = entry_list(d, seed + 1);
+  const bool tri = L > 0;
+  const int Wc = tri ? L : K, iters = 3;
+  const long live0 = hipstub_live_allocs();
+  bnmtf_handle h = nullptr;
+  OK(obs_create(d, e, K, L, &h));
+  std::vector<double> F((size_t)I * K, 1.0), S((size_t)K * Wc, 1.0), G((size_t)J * Wc, 1.0), tau(iters), perf((size_t)iters * 3), times(iters);
+  std::vector<float> Fo((size_t)iters * I * K), So((size_t)iters * K * Wc), Go((size_t)iters * J * Wc);
+  std::vector<double> num(std::max(I, J)), tp(std::max(I, J));
+  double t = 0, sums[6];
+  auto set_state = [&] { if (tri) OK(bnmtf_otri_set_state(h, F.data(), S.data(), G.data(), 1.0)); else OK(bnmf_obs_set_state(h, F.data(), G.data(), 1.0)); };
+  auto run = [&](int update, bool outputs) {
+    float* fo = outputs ? Fo.data() : nullptr; float* so = outputs ? So.data() : nullptr; float* go = outputs ? Go.data() : nullptr;
+    double* ta = outputs ? tau.data() : nullptr; double* pe = outputs ? perf.data() : nullptr; double* ti = outputs ? times.data() : nullptr;
+    if (tri) OK(bnmtf_otri_run(h, iters, update, fo, so, go, ta, pe, ti)); else OK(bnmf_obs_run(h, iters, update, fo, go, ta, pe, ti));
+  };
+  // the variational calls ahead of their set_state
+  const int per = K * Wc + K + Wc;
+  std::vector<int32_t> orders((size_t)iters * per);
+  for (int it = 0; it < iters; ++it) {
+    int32_t* o = &orders[(size_t)it * per];
+    for (int a = 0; a < K * Wc; ++a) o[a] = K * Wc - 1 - a;
+    for (int k = 0; k < K; ++k) o[K * Wc + k] = (k + it) % K;
+    for (int l = 0; l < Wc; ++l) o[K * Wc + K + l] = Wc - 1 - l;
+  }
+  if (tri) EXPECT_ERR(bnmtf_otvb_run(h, 1, orders.data(), nullptr, nullptr, nullptr, nullptr)); else EXPECT_ERR(bnmf_vbo_run(h, 1, nullptr, nullptr, nullptr, nullptr));
+  set_state();
+  run(BNMTF_UPDATE_DRAW, true); run(BNMTF_UPDATE_MODE, true); run(BNMTF_UPDATE_ICM, false);
+  if (tri) {
+    OK(bnmtf_otri_cond_params(h, 0, K - 1, 0, num.data(), tp.data()));
+    OK(bnmtf_otri_cond_params(h, 1, K - 1, L - 1, num.data(), tp.data()));
+    OK(bnmtf_otri_cond_params(h, 2, 0, L - 1, num.data(), tp.data()));
+    EXPECT_ERR(bnmtf_otri_cond_params(h, 0, K, 0, num.data(), tp.data()));
+    EXPECT_ERR(bnmtf_otri_cond_params(h, 2, 0, L, num.data(), tp.data()));
+    EXPECT_ERR(bnmtf_otri_cond_params(h, 1, K, 0, num.data(), tp.data()));
+  } else {
+    OK(bnmf_obs_cond_params(h, 0, K - 1, num.data(), tp.data()));
+    OK(bnmf_obs_cond_params(h, 1, 0, num.data(), tp.data()));
+    EXPECT_ERR(bnmf_obs_cond_params(h, 0, K, num.data(), tp.data()));
+  }
+  // the metric sums: the training list, a short list of other entries, one outside the matrix
+  const int32_t fr[3] = {I - 1, 0, I / 2}, fc[3] = {0, J - 1, J / 2}, outside[3] = {0, J, 0};
+  const float fv[3] = {1.f, 2.f, 3.f};
+  if (tri) {
+    OK(bnmtf_otri_metric_sums(h, e.n, e.rows.data(), e.cols.data(), e.vals.data(), F.data(), S.data(), G.data(), sums));
+    OK(bnmtf_otri_metric_sums(h, 3, fr, fc, fv, F.data(), S.data(), G.data(), sums));
+    EXPECT_ERR(bnmtf_otri_metric_sums(h, 3, fr, outside, fv, F.data(), S.data(), G.data(), sums));
+    OK(bnmtf_otri_get_state(h, F.data(), S.data(), G.data(), &t));
+  } else {
+    OK(bnmf_obs_metric_sums(h, e.n, e.rows.data(), e.cols.data(), e.vals.data(), F.data(), G.data(), sums));
+    OK(bnmf_obs_metric_sums(h, 3, fr, fc, fv, F.data(), G.data(), sums));
+    EXPECT_ERR(bnmf_obs_metric_sums(h, 3, fr, outside, fv, F.data(), G.data(), sums));
+    OK(bnmf_obs_get_state(h, F.data(), G.data(), &t));
+  }
+  // the dense calls and the other kind's refuse the handle
+  EXPECT_ERR(bnmf_set_state(h, F.data(), G.data(), 1.0));
+  EXPECT_ERR(bnmf_gibbs_run(h, 1, BNMTF_UPDATE_DRAW, nullptr, nullptr, nullptr, nullptr, nullptr));
+  EXPECT_ERR(bnmtf_metric_sums(h, nullptr, F.data(), nullptr, G.data(), sums));
+  if (tri) EXPECT_ERR(bnmf_obs_run(h, 1, BNMTF_UPDATE_DRAW, nullptr, nullptr, nullptr, nullptr, nullptr));
+  else EXPECT_ERR(bnmtf_otri_run(h, 1, BNMTF_UPDATE_DRAW, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+  if (tri) EXPECT_ERR(bnmf_vbo_set_state(h, F.data(), F.data(), F.data(), F.data(), G.data(), G.data(), G.data(), G.data(), 1.0));
+  else EXPECT_ERR(bnmtf_otvb_set_state(h, F.data(), F.data(), F.data(), F.data(), S.data(), S.data(), S.data(), S.data(), G.data(), G.data(), G.data(), G.data(), 1.0));
+  // the variational model: the first set_state allocates, the second must not
+  std::vector<double> et(iters), elbo((size_t)iters * 10);
+  auto vb_set_state = [&] {
+    if (tri) OK(bnmtf_otvb_set_state(h, F.data(), F.data(), F.data(), F.data(), S.data(), S.data(), S.data(), S.data(), G.data(), G.data(), G.data(), G.data(), 1.0));
+    else OK(bnmf_vbo_set_state(h, F.data(), F.data(), F.data(), F.data(), G.data(), G.data(), G.data(), G.data(), 1.0));
+  };
+  const long live1 = hipstub_live_allocs();
+  vb_set_state();
+  const long live2 = hipstub_live_allocs();
+  vb_set_state();
+  if (live2 <= live1 || hipstub_live_allocs() != live2) { fprintf(stderr, "variational buffers: %ld, %ld, %ld live allocations\n", live1, live2, hipstub_live_allocs()); exit(2); }
+  if (tri) {
+    EXPECT_ERR(bnmtf_otri_run(h, 1, BNMTF_UPDATE_DRAW, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));     // (a variational state)
+    OK(bnmtf_otvb_run(h, iters, orders.data(), et.data(), perf.data(), elbo.data(), times.data()));
+    EXPECT_ERR(bnmtf_otvb_run(h, 1, nullptr, nullptr, nullptr, nullptr, nullptr));
+    for (int m = 0; m < 2; ++m) {
+      OK(bnmtf_otvb_update(h, 0, K - 1, 0, m)); OK(bnmtf_otvb_update(h, 1, K - 1, L - 1, m)); OK(bnmtf_otvb_update(h, 2, 0, L - 1, m));
+    }
+    EXPECT_ERR(bnmtf_otvb_update(h, 0, K, 0, 1)); EXPECT_ERR(bnmtf_otvb_update(h, 2, 0, L, 1)); EXPECT_ERR(bnmtf_otvb_update(h, 3, 0, 0, 1));
+    OK(bnmtf_otvb_exp_square_diff(h, &t));
+    OK(bnmtf_otvb_get_state(h, F.data(), F.data(), F.data(), F.data(), S.data(), S.data(), S.data(), S.data(), G.data(), G.data(), G.data(), G.data()));
+  } else {
+    OK(bnmf_vbo_run(h, iters, et.data(), perf.data(), elbo.data(), times.data()));
+    OK(bnmf_vbo_run(h, 1, nullptr, nullptr, nullptr, nullptr));
+    for (int m = 0; m < 2; ++m) { OK(bnmf_vbo_update(h, 0, K - 1, m)); OK(bnmf_vbo_update(h, 1, 0, m)); }
+    EXPECT_ERR(bnmf_vbo_update(h, 1, K, 1)); EXPECT_ERR(bnmf_vbo_update(h, 2, 0, 1));
+    OK(bnmf_vbo_exp_square_diff(h, &t));
+    OK(bnmf_vbo_get_state(h, F.data(), F.data(), F.data(), F.data(), G.data(), G.data(), G.data(), G.data()));
+    OK(bnmf_obs_run(h, 1, BNMTF_UPDATE_MODE, nullptr, nullptr, nullptr, nullptr, nullptr));      // (two factors: the sampler runs on the expectations)
+  }
+  // the sampler's set_state ends the variational state
+  set_state();
+  run(BNMTF_UPDATE_DRAW, true);
+  if (tri) EXPECT_ERR(bnmtf_otvb_exp_square_diff(h, &t)); else EXPECT_ERR(bnmf_vbo_exp_square_diff(h, &t));
+  char buf[1024];
+  OK(bnmtf_describe(h, buf, sizeof buf));
+  OK(bnmtf_destroy(h));
+  if (hipstub_live_allocs() != live0) { fprintf(stderr, "obs_walk(%d, %d, %d, %d): %ld allocations outlive the handle\n", I, J, K, L, hipstub_live_allocs() - live0); exit(2); }
+}
+
+// what the creates refuse, a create that fails midway, and the host builder of the lists on its own
+static void obs_refusals() {
+  const Data d = make_data(37, 23, 0.8, 51);
+  const Entries e = entry_list(d, 52);
+  for (int L : {0, 2}) {
+    const int K = 3;
+    Entries bad = e; bad.cols[5] = d.J;                                   // an entry outside the matrix
+    obs_create_refused(d, bad, K, L);
+    bad = e; bad.rows[7] = bad.rows[3]; bad.cols[7] = bad.cols[3];        // an entry twice
+    obs_create_refused(d, bad, K, L);
+    bad = Entries();                                                      // row 4 without entries
+    for (uint64_t q = 0; q < e.n; ++q) if (e.rows[q] != 4) { bad.rows.push_back(e.rows[q]); bad.cols.push_back(e.cols[q]); bad.vals.push_back(e.vals[q]); }
+    bad.n = bad.rows.size();
+    obs_create_refused(d, bad, K, L);
+    bad = e; bad.n = 0;
+    obs_create_refused(d, bad, K, L);
+    obs_create_refused(d, e, L ? 33 : 257, L);
+    if (L) obs_create_refused(d, e, K, 33);
+    for (long at : {3L, 7L}) {                                            // a host exception inside the first and the second direction's build (four uploads each)
+      hipstub_throw_at_sync(at);
+      obs_create_refused(d, e, K, L);
+      hipstub_throw_at_sync(0);
+    }
+  }
+  std::vector<uint32_t> rptr(d.I + 1), ridx(e.n), cptr(d.J + 1), cidx(e.n);
+  std::vector<float> rval(e.n), cval(e.n);
+  OK(bnmtf_obs_build_lists(d.I, d.J, e.n, e.rows.data(), e.cols.data(), e.vals.data(), rptr.data(), ridx.data(), rval.data(), cptr.data(), cidx.data(), cval.data()));
+  OK(bnmtf_obs_build_lists(d.I, d.J, e.n, e.rows.data(), e.cols.data(), e.vals.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+  if (rptr[d.I] != e.n || cptr[d.J] != e.n) { fprintf(stderr, "bnmtf_obs_build_lists: %u / %u of %llu entries\n", rptr[d.I], cptr[d.J], (unsigned long long)e.n); exit(2); }
+  EXPECT_ERR(bnmtf_obs_build_lists(d.I, d.J, 0, e.rows.data(), e.cols.data(), e.vals.data(), rptr.data(), ridx.data(), rval.data(), cptr.data(), cidx.data(), cval.data()));
+}
+
 // `world` ranks of this process, one thread each, joined by the in-process transport (communicator id "BNMTFLOC...")
 static void sharded(const Data& d, int K, int L, int world, const char* token, int iters) {
   uint8_t cid[128];
@@ -459,6 +628,11 @@ int main(int argc, char** argv) {
   column_blocks(make_data(70, 60, 0.1, 22));             // (blocks that qualify for the one-launch arena)
   tri_blocks(make_data(130, 110, 0.12, 23));
   tri_blocks(make_data(60, 50, 0.1, 24));
+  obs_walk(37, 23, 5, 0, 61);                            // row stride 8: padded
+  obs_walk(19, 21, 64, 0, 62);                           // row stride = K
+  obs_walk(37, 23, 3, 2, 63);
+  obs_walk(33, 31, 32, 32, 64);                          // row stride = W
+  obs_refusals();
   sharded(make_data(640, 512, 0.12, 9), 24, 0, 2, "a2", 5);
   sharded(make_data(515, 389, 0.12, 10), 40, 0, 3, "a3", 5);
   sharded(make_data(300, 260, 0.1, 11), 8, 6, 2, "t2", 3);
