@@ -133,6 +133,12 @@ _SIGS = {
     "bnmtf_otvb_update": ([_P, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
     "bnmtf_otvb_exp_square_diff": ([_P, C.POINTER(C.c_double)], C.c_int),
     "bnmtf_otvb_run": ([_P, C.c_int, _P, _P, _P, _P, _P], C.c_int),
+    "bnmtf_onp_create": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, _P, _P, _P, C.c_int, C.POINTER(_P)], C.c_int),
+    "bnmtf_onp_set_state": ([_P, _P, _P, _P], C.c_int),
+    "bnmtf_onp_get_state": ([_P, _P, _P, _P], C.c_int),
+    "bnmtf_onp_run": ([_P, C.c_int, _P, _P, _P], C.c_int),
+    "bnmtf_onp_update": ([_P, C.c_int, C.c_int, C.c_int], C.c_int),
+    "bnmtf_onp_metrics": ([_P, C.c_uint64, _P, _P, _P, _P], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 

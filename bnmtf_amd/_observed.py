@@ -1,9 +1,10 @@
-"""layout='observed' of bnmf_gibbs_optimised / nmf_icm and of bnmtf_gibbs_optimised / nmtf_icm, bnmf_vb_observed and
-bnmtf_vb_observed: the host side of the observed-entry layout.
+"""layout='observed' of bnmf_gibbs_optimised / nmf_icm, of bnmtf_gibbs_optimised / nmtf_icm and of nmf_np.NMF / nmtf_np.NMTF,
+bnmf_vb_observed and bnmtf_vb_observed: the host side of the observed-entry layout.
 
-The device keeps the residual R_ij - U_i.V_j on the OBSERVED entries (csrc/kernel_obs.hip, kernel_obs_vb.hip), so cost and device memory follow the
-number of observed entries: the layout for matrices that are mostly missing.  R and M stay dense NumPy arrays at the Python
-boundary; this module turns the mask into the entry lists the library takes, owns the bnmtf_obs_create / bnmtf_otri_create handle of a model and
+The device keeps the residual R_ij - U_i.V_j -- for the non-probabilistic models the product P_ij itself -- on the OBSERVED entries
+(csrc/kernel_obs.hip, kernel_obs_vb.hip, kernel_obs_np.hip), so cost and device memory follow the number of observed entries: the
+layout for matrices that are mostly missing.  R and M stay dense NumPy arrays at the Python boundary; this module turns the mask
+into the entry lists the library takes, owns the bnmtf_obs_create / bnmtf_otri_create / bnmtf_onp_create handle of a model and
 states what the layout does not run."""
 import ctypes as C
 
@@ -106,6 +107,77 @@ class ObservedVB(ObservedLayout):
 
     def column_maxima(self, which):
         refuse(self, "column_maxima")
+
+
+class ObservedNP(object):
+    """The layout switch of nmf_np.NMF and nmtf_np.NMTF, ahead of nmf_np.NPDevice in their MRO as ObservedLayout is ahead of
+    DeviceModel: with self._layout == 'observed' the handle is bnmtf_onp_create's, the device calls are the bnmtf_onp_* ones and
+    the sums of predict() / compute_I_div() come from the list metric; everything else -- initialise, run, train, the single
+    updates, the push-only-if-changed hand-over -- is NPDevice's own code.  With 'dense' every method hands on."""
+
+    def _init_layout(self, layout, world):
+        """The constructor's first step: the keyword, and what the layout does not run, before anything touches a device."""
+        check_layout(layout)
+        self._layout = layout
+        if layout == 'observed':
+            for name in ("K", "L"):
+                v = getattr(self, name, None)
+                if v is not None and not (1 <= int(v) <= MAX_RANK):
+                    raise _lib.BnmtfError("%s: %s = %s is outside what layout='observed' runs (1 <= %s <= %d on one handle; "
+                                          "DESIGN.md section 2.7, limits)" % (type(self).__name__, name, v, name, MAX_RANK))
+            if int(world) != 1:
+                refuse(self, "world = %s" % world, "the observed-entry layout runs on one GPU: world = 1")
+
+    def _handle(self):
+        if self._layout != 'observed':
+            return super(ObservedNP, self)._handle()
+        if self._h is None:
+            Mb = self.M != 0
+            assert (self.M == Mb).all(), "The indicator matrix M must contain only 0 and 1."
+            rows, cols, vals = entry_list(self.R, Mb)
+            self._train_list = (rows, cols, vals)
+            h = C.c_void_p()
+            _lib.check(_lib.lib().bnmtf_onp_create(int(self.I), int(self.J), int(self.K), int(getattr(self, "L", 0)), C.c_uint64(len(rows)),
+                                                   _lib.ptr(rows), _lib.ptr(cols), _lib.ptr(vals), int(self._device), C.byref(h)))
+            self._h = h
+        return self._h
+
+    def _entry(self, name):
+        """The bnmtf_onp_* call that stands in for the dense layout's `name` (the two-factor names: S is null, V is `which` 2)."""
+        if self._layout != 'observed':
+            return super(ObservedNP, self)._entry(name)
+        lib = _lib.lib              # (resolved at the call: naming an entry point is no device call)
+        return {"bnmf_np_run": lambda *a: lib().bnmtf_onp_run(*a), "bnmtf_np_run": lambda *a: lib().bnmtf_onp_run(*a),
+                "bnmf_np_set_state": lambda h, U, V: lib().bnmtf_onp_set_state(h, U, None, V),
+                "bnmtf_np_set_state": lambda *a: lib().bnmtf_onp_set_state(*a),
+                "bnmf_np_get_state": lambda h, U, V: lib().bnmtf_onp_get_state(h, U, None, V),
+                "bnmtf_np_get_state": lambda *a: lib().bnmtf_onp_get_state(*a),
+                "bnmf_np_update": lambda h, which, k: lib().bnmtf_onp_update(h, 2 * which, k, k),
+                "bnmtf_np_update": lambda *a: lib().bnmtf_onp_update(*a)}[name]
+
+    def _check_heldout(self, M_test):
+        if self._layout != 'observed':
+            return super(ObservedNP, self)._check_heldout(M_test)
+        if M_test is not None:
+            refuse(self, "run(M_test=)")
+        return None
+
+    def _sums(self, M_pred=None):
+        """The eight sums of metrics_from_np_sums over M_pred (None: the training entries) for the factors the device holds."""
+        if self._layout != 'observed':
+            return super(ObservedNP, self)._sums(M_pred)
+        self._push()
+        out = np.zeros(8)
+        if M_pred is None:
+            _lib.check(_lib.lib().bnmtf_onp_metrics(self._handle(), C.c_uint64(0), None, None, None, _lib.ptr(out)))
+            return out
+        Mp = np.asarray(M_pred)
+        assert Mp.shape == (self.I, self.J), "M_pred has the wrong shape: %s instead of %s." % (Mp.shape, (self.I, self.J))
+        assert ((Mp == 0) | (Mp == 1)).all(), "The indicator matrix M_pred must contain only 0 and 1."
+        rows, cols, vals = entry_list(self.R, Mp)
+        if len(rows):                           # (an empty mask: the dense layout's sums of nothing)
+            _lib.check(_lib.lib().bnmtf_onp_metrics(self._handle(), C.c_uint64(len(rows)), _lib.ptr(rows), _lib.ptr(cols), _lib.ptr(vals), _lib.ptr(out)))
+        return out
 
 
 def check_constructor(model, world):

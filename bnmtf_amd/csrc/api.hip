@@ -46,6 +46,7 @@ extern "C" int bnmtf_shard_range(int64_t n, int rank, int world, int64_t* first,
 namespace bnmtf {
 static void np_free(bnmtf_model* h);   // api_np.inc
 static void obs_free(bnmtf_model* h);  // api_obs.inc
+static bool obs_is_np(const bnmtf_model* h);   // api_obs.inc: a handle of bnmtf_onp_create
 
 template <typename T>
 static int dalloc(T** p, size_t count, bool zero = true) {
@@ -68,12 +69,13 @@ static int upload(T** dst, const std::vector<T>& src, hipStream_t st) {
   return BNMTF_OK;
 }
 
-// a handle of bnmtf_obs_create or -- the tri-factorisation, L > 0 -- bnmtf_otri_create (the observed-entry layout, api_obs.inc)
-// holds none of what the other entry points work on
+// a handle of bnmtf_obs_create, -- the tri-factorisation, L > 0 -- bnmtf_otri_create or -- NMF / NMTF -- bnmtf_onp_create (the
+// observed-entry layout, api_obs.inc) holds none of what the other entry points work on
 static int refuse_obs(const bnmtf_model* h, const char* fn) {
   if (h && h->obs) {      // (fn null: reached through ensure_std, from any of the sampler and variational calls)
     set_error("%s%sa handle of %s calls (layout='observed')", fn ? fn : "", fn ? ": " : "",
-              h->L > 0 ? "bnmtf_otri_create runs only the bnmtf_otri_*" : "bnmtf_obs_create runs only the bnmf_obs_*");
+              obs_is_np(h) ? "bnmtf_onp_create runs only the bnmtf_onp_*"
+                           : h->L > 0 ? "bnmtf_otri_create runs only the bnmtf_otri_*" : "bnmtf_obs_create runs only the bnmf_obs_*");
     return BNMTF_EINVAL;
   }
   return BNMTF_OK;
@@ -1701,4 +1703,5 @@ int bnmtf_gamma_sample(double alpha, double beta, uint64_t seed, uint64_t it, in
 #include "api_obs.inc"
 #include "api_obs_tri.inc"
 #include "api_obs_trivb.inc"
+#include "api_obs_np.inc"
 #include "api_many.inc"

@@ -9,6 +9,9 @@
 //   * the variational buffers -- q's parameters and the half sweeps' partial sums per direction, the transposed S2 of a two-factor
 //     handle, the effective factors' second moments of a tri-factorisation --, allocated by the first bnmf_vbo_set_state /
 //     bnmtf_otvb_set_state, so a Gibbs / ICM handle holds none of them.
+//   * the non-probabilistic models' parts (bnmtf_onp_create, api_obs_np.inc: the marker `np` is set): no prior rates, a row
+//     stride per direction, NMTF's S and effective factors, eight-wide partial sums; such a handle runs the bnmtf_onp_* calls
+//     only, and those run no other handle.
 // obs_free is the one owner of all of it.  This file has the state, the helpers every model on the layout shares (one direction's
 // build / put / q, the common part of create, the half sweeps' argument builders, the record and the hooks' tails, the list
 // metric) and the two-factor models: the Gibbs / ICM iteration is two launches of obs_sweep_kernel and obs_finish_kernel
@@ -20,7 +23,8 @@ namespace bnmtf {
 struct ObsList {                 // one direction: units, their entries' inner indices and values
   uint32_t* ptr = nullptr; uint32_t* idx = nullptr; float* val = nullptr;
   float* X = nullptr; float* XT = nullptr; int n = 0, W = 0, ldT = 0;   // the direction's factor of W columns: [n][stride] and [W][ldT]
-  float* lambda = nullptr;                                         // [n][stride]
+  int stride = 0;                                                  // its row stride: the state's, or -- a handle of bnmtf_onp_create -- W rounded up to 4
+  float* lambda = nullptr;                                         // [n][stride]; null on a handle of bnmtf_onp_create, as the next two
   double* numer = nullptr; double* taup = nullptr;                 // cond-params scratch [n]
   uint32_t longest = 0; size_t long_units = 0;                     // most entries of a unit; units beyond the register form
   // variational state (obs_alloc_q): q's mu, tau, var [n][stride] beside the expectation in X / XT; on a two-factor handle also
@@ -48,9 +52,18 @@ struct ObsState {
   float* Pv = nullptr;                                // R~^T F [J][32]
   float* ceffS2 = nullptr; float* ceffS2T = nullptr;  // variational: second moment of G S^T, [J][32] and [K][cols.ldT]
   float* reffS2 = nullptr; float* reffS2T = nullptr;  // ... and of F S, [I][32] and [L][rows.ldT]
+  // a handle of bnmtf_onp_create only (api_obs_np.inc): the marker; NMTF's S and the S step's output [K][L] and block partials
+  // [2][onp_s_blocks(I)][2] (its effective factors are ceffX .. reffXT above, at the strides K and L rounded up to 4); the last half
+  // sweep's and the metric call's partial sums [..][8]; the run's records [iterations][8]; what the single-column calls carry
+  bool np = false;
+  float* npS = nullptr; float* npS2 = nullptr; double* np_spart = nullptr;
+  double* np_part = nullptr; double* np_mpart = nullptr;
+  double* np_rec = nullptr; size_t np_rec_cap = 0;
+  int np_next_which = -1, np_next_col = -1;        // escratch holds the P that column np_next_col of this direction continues from
 };
 
 static bool obs_is_tri(const bnmtf_model* h) { return h->L > 0; }
+static bool obs_is_np(const bnmtf_model* h) { return h->obs && h->obs->np; }
 
 static void obs_free(bnmtf_model* h) {
   ObsState* s = h->obs;
@@ -59,16 +72,17 @@ static void obs_free(bnmtf_model* h) {
   dfree(s->escratch); dfree(s->part); dfree(s->scal); dfree(s->esd_part);
   dfree(s->ceffX); dfree(s->ceffXT); dfree(s->reffX); dfree(s->reffXT); dfree(s->Pv);
   dfree(s->ceffS2); dfree(s->ceffS2T); dfree(s->reffS2); dfree(s->reffS2T);
+  dfree(s->npS); dfree(s->npS2); dfree(s->np_spart); dfree(s->np_part); dfree(s->np_mpart); dfree(s->np_rec);
   h->tau_d = nullptr; h->tau_f = nullptr;
   delete s;
   h->obs = nullptr;              // (a tri-factorisation's S, lambdaS and S system's buffers are the model's own: bnmtf_destroy frees them)
 }
 
-// Every entry point's first step.  tri: the call belongs to the bnmtf_otri_* / bnmtf_otvb_* family; need: the state it works on.
+// Every entry point's first step (the bnmtf_onp_* calls: onp_check, api_obs_np.inc).  tri: the call belongs to the bnmtf_otri_* / bnmtf_otvb_* family; need: the state it works on.
 // A tri-factorisation's sampler calls refuse a variational state; the two-factor ones run on its expectations (DESIGN.md section 2.7).
 enum { kObsNoState = 0, kObsSamplerState, kObsVbState };
 static int obs_check(bnmtf_model* h, bool tri, int need) {
-  if (!h || !h->obs || obs_is_tri(h) != tri) { set_error("not a handle of %s", tri ? "bnmtf_otri_create" : "bnmtf_obs_create"); return BNMTF_EINVAL; }
+  if (!h || !h->obs || h->obs->np || obs_is_tri(h) != tri) { set_error("not a handle of %s", tri ? "bnmtf_otri_create" : "bnmtf_obs_create"); return BNMTF_EINVAL; }
   if (need == kObsSamplerState && !h->have_state) { set_error("%s has not been called", tri ? "bnmtf_otri_set_state" : "bnmf_obs_set_state"); return BNMTF_ESTATE; }
   if (need == kObsSamplerState && tri && h->obs->vb_state) {
     set_error("the handle holds a variational state (bnmtf_otvb_set_state): it runs the bnmtf_otvb_* calls until bnmtf_otri_set_state replaces it");
@@ -132,22 +146,26 @@ static int obs_lists(int I, int J, uint64_t n, const int32_t* rows, const int32_
   return BNMTF_OK;
 }
 
-// one direction: the list, the prior rates [n][stride], the factor of W columns in both forms and the hooks' scratch
-static int obs_build_dir(bnmtf_model* h, ObsList& d, int n, int W, const std::vector<uint32_t>& ptr, const std::vector<uint32_t>& idx,
+// one direction: the list, the prior rates [n][stride], the factor of W columns in both forms and the hooks' scratch (lambda
+// null: neither rates nor hooks -- the non-probabilistic models have no conditionals)
+static int obs_build_dir(bnmtf_model* h, ObsList& d, int n, int W, int KP, const std::vector<uint32_t>& ptr, const std::vector<uint32_t>& idx,
                          const std::vector<float>& val, const double* lambda) {
-  const int KP = h->obs->stride;
-  d.n = n; d.W = W; d.ldT = round_up(n + 1, 64);          // (a zero behind every column of the transposed forms: the sweep's empty slots gather it)
+  d.n = n; d.W = W; d.stride = KP; d.ldT = round_up(n + 1, 64);          // (a zero behind every column of the transposed forms: the sweep's empty slots gather it)
   CHK(upload(&d.ptr, ptr, h->stream));
   CHK(upload(&d.idx, idx, h->stream));
   CHK(upload(&d.val, val, h->stream));
-  std::vector<float> lam((size_t)n * KP, 0.f);
-  for (int u = 0; u < n; ++u)
-    for (int k = 0; k < W; ++k) lam[(size_t)u * KP + k] = (float)lambda[(size_t)u * W + k];
-  CHK(upload(&d.lambda, lam, h->stream));
+  if (lambda) {
+    std::vector<float> lam((size_t)n * KP, 0.f);
+    for (int u = 0; u < n; ++u)
+      for (int k = 0; k < W; ++k) lam[(size_t)u * KP + k] = (float)lambda[(size_t)u * W + k];
+    CHK(upload(&d.lambda, lam, h->stream));
+  }
   CHK(dalloc(&d.X, (size_t)n * KP));
   CHK(dalloc(&d.XT, (size_t)W * d.ldT));
-  CHK(dalloc(&d.numer, (size_t)n, false));
-  CHK(dalloc(&d.taup, (size_t)n, false));
+  if (lambda) {
+    CHK(dalloc(&d.numer, (size_t)n, false));
+    CHK(dalloc(&d.taup, (size_t)n, false));
+  }
   for (int u = 0; u < n; ++u) {
     const uint32_t c = ptr[u + 1] - ptr[u];
     d.longest = std::max(d.longest, c);
@@ -158,7 +176,7 @@ static int obs_build_dir(bnmtf_model* h, ObsList& d, int n, int W, const std::ve
 
 // fp64 host [n][W] -> fp32 device [n][stride] and [W][ldT]
 static int obs_put(bnmtf_model* h, ObsList& d, const double* src) {
-  const int W = d.W, KP = h->obs->stride;
+  const int W = d.W, KP = d.stride;
   std::vector<float> x((size_t)d.n * KP, 0.f), xt((size_t)W * d.ldT, 0.f);
   for (int u = 0; u < d.n; ++u)
     for (int k = 0; k < W; ++k) {
@@ -209,7 +227,8 @@ static int obs_put_q(bnmtf_model* h, ObsList& d, const double* mu, const double*
 
 // The common part of bnmtf_obs_create / bnmtf_otri_create (the callers have checked their arguments): the lists, the model, its
 // stream, the state with both directions and the scalars.  The handle is the guard's from the moment it exists: every way out of
-// a create but release(), an exception included, destroys it.
+// a create but release(), an exception included, destroys it.  bnmtf_onp_create (np): null prior rates, the columns' factor at
+// a stride of its own and the marker; its half sweeps' partial sums are eight wide and its own.
 struct ObsCreateGuard {
   bnmtf_model* h = nullptr;
   ~ObsCreateGuard() { if (h) bnmtf_destroy(h); }
@@ -217,7 +236,7 @@ struct ObsCreateGuard {
 };
 static int obs_create_common(ObsCreateGuard& guard, int I, int J, int K, int L, int stride, uint64_t n, const int32_t* rows, const int32_t* cols,
                              const float* values, const double* lambda_rows, const double* lambda_cols, double alpha, double beta,
-                             uint64_t seed, int device) {
+                             uint64_t seed, int device, bool np = false, int stride_cols = 0) {
   ObsLists ls;
   CHK(obs_lists(I, J, n, rows, cols, values, ls));
   HIPCHK(hipSetDevice(device));
@@ -232,13 +251,13 @@ static int obs_create_common(ObsCreateGuard& guard, int I, int J, int K, int L, 
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { h->stream = nullptr; set_error("hipStreamCreate failed"); return BNMTF_EHIP; }
   h->obs = new ObsState();
   ObsState* s = h->obs;
-  s->n = (size_t)n; s->stride = stride;
+  s->n = (size_t)n; s->stride = stride; s->np = np;
   const char* fl = getenv("BNMTF_OBS_LONG");
   s->force_long = fl && fl[0] == '1';
-  CHK(obs_build_dir(h, s->rows, I, K, ls.rptr, ls.ridx, ls.rval, lambda_rows));
-  CHK(obs_build_dir(h, s->cols, J, Wc, ls.cptr, ls.cidx, ls.cval, lambda_cols));
+  CHK(obs_build_dir(h, s->rows, I, K, stride, ls.rptr, ls.ridx, ls.rval, lambda_rows));
+  CHK(obs_build_dir(h, s->cols, J, Wc, stride_cols > 0 ? stride_cols : stride, ls.cptr, ls.cidx, ls.cval, lambda_cols));
   CHK(dalloc(&s->escratch, (size_t)n, false));
-  CHK(dalloc(&s->part, (size_t)obs_sweep_blocks(J) * 4, false));
+  if (!np) CHK(dalloc(&s->part, (size_t)obs_sweep_blocks(J) * 4, false));
   CHK(dalloc(&s->scal, 16));
   h->tau_d = s->scal; h->tau_f = reinterpret_cast<float*>(s->scal + 1); s->out8 = s->scal + 8;
   return BNMTF_OK;

@@ -708,4 +708,55 @@ void launch_obs_mv(const ObsMvArgs& a, hipStream_t st);
 void launch_obs_trivb_finish(const ObsTriVbFinishArgs& a, hipStream_t st);
 void launch_obs_trivb_esd(const ObsTriVbEsdArgs& a, double* out, hipStream_t st);
 
+// ---------------------------------------------------------------------------
+// The non-probabilistic NMF / NMTF on the observed-entry layout (kernel_obs_np.hip): the multiplicative
+// updates of kernel_np.hip with P = U V^T (or F S G^T) on the observed entries only, one wave per unit; ranks up to kObsMaxRank
+// ---------------------------------------------------------------------------
+struct OnpSweepArgs {
+  const uint32_t* ptr; const uint32_t* idx; const float* val;     // as ObsSweepArgs
+  int n, m, K, KP;                   // units, inner extent, rank, row stride of this factor and of Xo (K rounded up to 4; padding columns zero)
+  int k0, k1;                        // the columns [k0, k1) in order: all of them, or one (the single-column form)
+  int force_long;                    // every unit down the long form (BNMTF_OBS_LONG=1)
+  int resume, keep;                  // P of every entry from escratch instead of phase 1 / into escratch behind the last column
+  float* X; float* XT; int ldT;      // this direction's factor [n][KP] and transposed [K][ldT]
+  const float* Xo; const float* XoT; int ldT_o;   // the other (or effective) factor [m][KP] and [K][ldT_o], ldT_o > m: XoT[k][m] is zero
+  float* escratch;                   // [entries] P at the entry's list position (the long form; resume / keep)
+  double* part;                      // null, or [obs_sweep_blocks(n)][8]: n, R, R^2, P, P^2, R P, I-divergence, SSE of the final P
+};
+struct OnpEffArgs {         // out = X . S (transposeS = 0: inner K, width L) or X . S^T (transposeS = 1: inner L, width K), fp32, inner index in order
+  const float* X; int n, ldX;        // [n][ldX]
+  const float* S; int K, L, transposeS;
+  float* out; int ldo;               // [n][ldo], the padding columns zero
+  float* outT; int ldT;              // [width][ldT]
+};
+struct OnpSPassArgs {       // one pass of NMTF's S step over the row list (np_s_pass_kernel's scheme)
+  const uint32_t* ptr; const uint32_t* idx; const float* val; int I;
+  const float* F; int ldF;           // [I][ldF]
+  const float* GT; int ldGT;         // [L][ldGT]
+  const float* Xo;                   // build: G S^T [J][ldF]
+  float* P;                          // [entries] in row-list order
+  const float* S_in; float* S_out;   // the step's starting values (read only); every entry as it is finished
+  int K, L;
+  int prev, cur;                     // entries of S (k L + l) or -1: finish prev and move P by its change; sum cur's numerator and denominator
+  int build;                         // P from F and G S^T first (the step's first pass)
+  int apply;                         // cur < 0: still move P by prev's change (the single update leaves P current)
+  int nb;                            // blocks of every summing pass: the partials of prev
+  const double* part_prev; double* part_cur;   // [nb][2]
+};
+struct OnpMetricArgs {      // the eight sums of metrics_from_np_sums over an entry list; P in fp64 from the fp32 factors
+  const uint32_t* row;               // the entries' rows, or null: the entries are a row list and ptr [I + 1] finds the row
+  const uint32_t* ptr; int I;
+  const uint32_t* col; const float* val; size_t n;
+  const float* A; int ldA;           // [I][ldA]
+  const float* S; int K, L;          // L > 0: P = (A_i S) . B_j with A_i S in fp64
+  const float* B; int ldB;           // [J][ldB]
+  double* part;                      // [obs_metric_blocks(n)][8]
+};
+inline int onp_s_blocks(int I) { const int b = obs_sweep_blocks(I); return b > 1024 ? 1024 : b; }
+void launch_onp_sweep(const OnpSweepArgs& a, hipStream_t st);
+void launch_onp_fold(const double* part, int nb, double* out8, hipStream_t st);       // thread t the blocks t, t + 256, ..., then a tree
+void launch_onp_eff(const OnpEffArgs& a, hipStream_t st);
+void launch_onp_s_pass(const OnpSPassArgs& a, hipStream_t st);
+void launch_onp_metric(const OnpMetricArgs& a, double* out8, hipStream_t st);
+
 }  // namespace bnmtf

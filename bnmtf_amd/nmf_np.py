@@ -13,13 +13,18 @@ owns a few rows, their data and their P = U V^T in registers); run() is one devi
     NMF.predict(M_pred); NMF.compute_I_div()
 
 Same constructor arguments, attributes and assertion messages as the reference; build-only extras are keyword-only
-(device, verbose).  One GPU; ranks 1 <= K <= 256."""
+(device, verbose, layout).  One GPU; ranks 1 <= K <= 256.
+
+layout='observed' (default 'dense'): the same updates with P kept on the observed entries only (csrc/kernel_obs_np.hip;
+DESIGN.md section 2.7; _observed.ObservedNP) -- device memory and time follow the number of observed entries, and a row or
+column may be as long as it likes (the dense layout: at most 16 384 entries).  The whole API keeps its meaning; run(M_test=) and
+run_many are the dense layout's and are refused."""
 import ctypes as C
 import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _observed
 from ._base import HeldoutMixin, check_R_M, check_rank, compute_MSE, compute_R2, compute_Rp
 
 MAX_RANK_NP = 256
@@ -73,6 +78,10 @@ class NPDevice(HeldoutMixin):
 
     def _factors(self):
         raise NotImplementedError
+
+    def _entry(self, name):
+        """The library's entry point `name` (_observed.ObservedNP: the other layout's call in its place)."""
+        return getattr(_lib.lib(), name)
 
     def _push(self):
         """Hand the current factors to the device unless it holds them already (nothing touched them since the last pull)."""
@@ -144,11 +153,12 @@ class NPDevice(HeldoutMixin):
         return float(self._sums(None)[6])
 
 
-class NMF(NPDevice):
-    def __init__(self, R, M, K, *, device=0, verbose=True, rank=0, world=1, comm_id=None):
+class NMF(_observed.ObservedNP, NPDevice):
+    def __init__(self, R, M, K, *, device=0, verbose=True, rank=0, world=1, comm_id=None, layout='dense'):
         self.R = np.array(R, dtype=float)
         self.M = np.array(M, dtype=float)
         self.K = K
+        self._init_layout(layout, world)
         self.metrics = ['MSE', 'R^2', 'Rp']
         check_R_M(self.R, self.M)
         (self.I, self.J) = self.R.shape
@@ -179,7 +189,7 @@ class NMF(NPDevice):
         """:87-107.  One device call runs all iterations.  M_test: the held-out metrics of U V^T behind every iteration, in
         all_performances_test (see bnmf_gibbs_optimised.run)."""
         self._check_initialised()
-        self._run_device(_lib.lib().bnmf_np_run, iterations, M_test)
+        self._run_device(self._entry("bnmf_np_run"), iterations, M_test)
 
     def _check_initialised(self):
         assert hasattr(self, 'U') and hasattr(self, 'V'), "U and V have not been initialised - please run NMF.initialise() first."
@@ -200,7 +210,7 @@ class NMF(NPDevice):
     def _update(self, which, k):
         assert 0 <= int(k) < self.K, "column %s out of range (K = %s)" % (k, self.K)
         self._push()
-        _lib.check(_lib.lib().bnmf_np_update(self._handle(), int(which), int(k)))
+        _lib.check(self._entry("bnmf_np_update")(self._handle(), int(which), int(k)))
         self._pull()
 
     def _factors(self):
@@ -208,10 +218,10 @@ class NMF(NPDevice):
 
     def _set_state(self, U, V):
         assert U.shape == (self.I, self.K) and V.shape == (self.J, self.K), "U, V have the wrong shapes: %s, %s" % (U.shape, V.shape)
-        _lib.check(_lib.lib().bnmf_np_set_state(self._handle(), _lib.ptr(U), _lib.ptr(V)))
+        _lib.check(self._entry("bnmf_np_set_state")(self._handle(), _lib.ptr(U), _lib.ptr(V)))
 
     def _pull(self):
         U = np.zeros((self.I, self.K)); V = np.zeros((self.J, self.K))
-        _lib.check(_lib.lib().bnmf_np_get_state(self._handle(), _lib.ptr(U), _lib.ptr(V)))
+        _lib.check(self._entry("bnmf_np_get_state")(self._handle(), _lib.ptr(U), _lib.ptr(V)))
         self.U, self.V = U, V
         self._note_pulled()

@@ -11,21 +11,26 @@ predecessor left -- one launch per entry, each applying the previous entry's cha
     NMTF.run(iterations)                            # M_test=Mt: all_performances_test, the held-out metrics per iteration
     NMTF.predict(M_pred); NMTF.compute_I_div()
 
-One GPU; ranks 1 <= K, L <= 256."""
+One GPU; ranks 1 <= K, L <= 256.
+
+layout='observed' (keyword, default 'dense'): the same updates on the observed-entry layout (csrc/kernel_obs_np.hip; DESIGN.md
+section 2.7; _observed.ObservedNP): P lives on the observed entries only, so the K L passes of the S step read what is observed
+instead of an I x J matrix, and rows and columns have no length limit.  run(M_test=) and run_many are refused there."""
 import numpy as np
 
-from . import _lib
+from . import _lib, _observed
 from ._base import check_R_M, check_rank
 from .kmeans import KMeans
 from .nmf_np import MAX_RANK_NP, NPDevice
 
 
-class NMTF(NPDevice):
-    def __init__(self, R, M, K, L, *, device=0, verbose=True, rank=0, world=1, comm_id=None):
+class NMTF(_observed.ObservedNP, NPDevice):
+    def __init__(self, R, M, K, L, *, device=0, verbose=True, rank=0, world=1, comm_id=None, layout='dense'):
         self.R = np.array(R, dtype=float)
         self.M = np.array(M, dtype=float)
         self.K = K
         self.L = L
+        self._init_layout(layout, world)
         self.metrics = ['MSE', 'R^2', 'Rp']
         check_R_M(self.R, self.M)
         (self.I, self.J) = self.R.shape
@@ -75,7 +80,7 @@ class NMTF(NPDevice):
         """:116-144.  One device call runs all iterations.  M_test: the held-out metrics of F S G^T behind every iteration, in
         all_performances_test (see bnmf_gibbs_optimised.run)."""
         self._check_initialised()
-        self._run_device(_lib.lib().bnmtf_np_run, iterations, M_test)
+        self._run_device(self._entry("bnmtf_np_run"), iterations, M_test)
 
     def _check_initialised(self):
         assert hasattr(self, 'F') and hasattr(self, 'S') and hasattr(self, 'G'), \
@@ -107,7 +112,7 @@ class NMTF(NPDevice):
 
     def _update(self, which, k, l):
         self._push()
-        _lib.check(_lib.lib().bnmtf_np_update(self._handle(), int(which), int(k), int(l)))
+        _lib.check(self._entry("bnmtf_np_update")(self._handle(), int(which), int(k), int(l)))
         self._pull()
 
     def _factors(self):
@@ -116,10 +121,10 @@ class NMTF(NPDevice):
     def _set_state(self, F, S, G):
         assert F.shape == (self.I, self.K) and S.shape == (self.K, self.L) and G.shape == (self.J, self.L), \
             "F, S, G have the wrong shapes: %s, %s, %s" % (F.shape, S.shape, G.shape)
-        _lib.check(_lib.lib().bnmtf_np_set_state(self._handle(), _lib.ptr(F), _lib.ptr(S), _lib.ptr(G)))
+        _lib.check(self._entry("bnmtf_np_set_state")(self._handle(), _lib.ptr(F), _lib.ptr(S), _lib.ptr(G)))
 
     def _pull(self):
         F = np.zeros((self.I, self.K)); S = np.zeros((self.K, self.L)); G = np.zeros((self.J, self.L))
-        _lib.check(_lib.lib().bnmtf_np_get_state(self._handle(), _lib.ptr(F), _lib.ptr(S), _lib.ptr(G)))
+        _lib.check(self._entry("bnmtf_np_get_state")(self._handle(), _lib.ptr(F), _lib.ptr(S), _lib.ptr(G)))
         self.F, self.S, self.G = F, S, G
         self._note_pulled()

@@ -524,6 +524,30 @@ BNMTF_API int bnmtf_otvb_exp_square_diff(bnmtf_handle h, double* out);
 BNMTF_API int bnmtf_otvb_run(bnmtf_handle h, int n_iter, const int32_t* orders, double* exptau_out, double* perf_out,
                    double* elbo_terms_out, double* times_out);
 
+/* ---- the non-probabilistic NMF / NMTF on the observed-entry layout (nmf_np.NMF / nmtf_np.NMTF with layout='observed';
+ * DESIGN.md section 2.7) ------------------------------------------------------------------------------------------------------
+ * The multiplicative updates of the bnmf_np_* / bnmtf_np_* calls above with P = U V^T (or F S G^T) kept on the observed entries
+ * only (csrc/kernel_obs_np.hip): cost and memory proportional to the number of observed entries, nothing of size I x J, no limit on
+ * the length of a row or column.  1 <= K <= BNMTF_ONP_MAX_RANK; L = 0: NMF, else NMTF with 1 <= L <= BNMTF_ONP_MAX_RANK; one GPU.
+ * The handle is one of its own kind: the bnmf_obs_*, bnmf_vbo_*, bnmtf_otri_* and bnmtf_otvb_* calls refuse it and these refuse
+ * theirs.  Fixed summation order, no atomics: the same call gives the same bits, run(a) then run(b) those of run(a + b). */
+#define BNMTF_ONP_MAX_RANK 256
+/* the entries as bnmtf_obs_create takes them, with its checks and messages (before any device call); no priors, no seed */
+BNMTF_API int bnmtf_onp_create(int I, int J, int K, int L, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values,
+                     int device, bnmtf_handle* out);
+/* A [I][K], S [K][L], B [J][K] (NMF) or [J][L] (NMTF), fp64 on the host, fp32 on the device; S: null for NMF, required for NMTF */
+BNMTF_API int bnmtf_onp_set_state(bnmtf_handle h, const double* A, const double* S, const double* B);
+/* any pointer may be null */
+BNMTF_API int bnmtf_onp_get_state(bnmtf_handle h, double* A, double* S, double* B);
+/* n_iter iterations (NMF: U then V; NMTF: S, F, G); perf_out [n][3] MSE / R^2 / Rp, idiv_out [n], times_out [n]; any may be null */
+BNMTF_API int bnmtf_onp_run(bnmtf_handle h, int n_iter, double* perf_out, double* idiv_out, double* times_out);
+/* one column: which = 0 column k of U / F, 1 entry (k, l) of S (NMTF), 2 column l of V / G.  The columns of a factor called in
+ * order continue one half sweep: together they give its bits */
+BNMTF_API int bnmtf_onp_update(bnmtf_handle h, int which, int k, int l);
+/* the eight sums n, sum R, sum R^2, sum P, sum P^2, sum R P, I-divergence, SSE of the handle's factors over the entries given, in
+ * any order (n = 0: the training entries); P in fp64 from the fp32 factors, NMTF: (F_i S) . G_j with F_i S in fp64 */
+BNMTF_API int bnmtf_onp_metrics(bnmtf_handle h, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values, double* out8);
+
 #ifdef __cplusplus
 }
 #endif
