@@ -1157,6 +1157,29 @@ int bnmtf_sync(bnmtf_handle h) try {
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
+int bnmtf_handover_dump(bnmtf_handle h, int which, int64_t* info, uint32_t* t_in, uint32_t* t_out, uint32_t* pk, uint32_t* region_ofs,
+                        float* region) try {
+  CHK(refuse_obs(h, "bnmtf_handover_dump"));
+  if (!info || which < 0 || which > 1) { set_error("bnmtf_handover_dump: null info or which=%d (0 rows, 1 cols)", which); return BNMTF_EINVAL; }
+  if (!h->ho_enabled) { set_error("bnmtf_handover_dump: the handle has no hand-over tables"); return BNMTF_ESTATE; }
+  const Dir& d = which ? h->cols : h->rows;
+  const Dir& o = which ? h->rows : h->cols;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  uint32_t total = 0;
+  HIPCHK(hipMemcpy(&total, d.ho_region_ofs + d.ho_blocks, sizeof(total), hipMemcpyDeviceToHost));
+  const size_t words = ((d.f_slots + 1) / 2) * 64, n_pk = (size_t)d.ho_blocks * o.ho_blocks * 3, n_ofs = (size_t)d.ho_blocks + 1, n_region = (size_t)total + 256;
+  const int64_t scalars[BNMTF_HANDOVER_INFO_LEN] = {d.ho_blocks, o.ho_blocks, d.ho_lds_floats, d.ho_ppb, d.ho_filled, h->ho_regions_current,
+                                                     (int64_t)words, (int64_t)words, (int64_t)n_pk, (int64_t)n_ofs, (int64_t)n_region};
+  memcpy(info, scalars, sizeof(scalars));
+  if (t_in && words) HIPCHK(hipMemcpy(t_in, d.ho_in, words * 4, hipMemcpyDeviceToHost));
+  if (t_out && words) HIPCHK(hipMemcpy(t_out, d.ho_out, words * 4, hipMemcpyDeviceToHost));
+  if (pk) HIPCHK(hipMemcpy(pk, d.ho_pk, n_pk * 4, hipMemcpyDeviceToHost));
+  if (region_ofs) HIPCHK(hipMemcpy(region_ofs, d.ho_region_ofs, n_ofs * 4, hipMemcpyDeviceToHost));
+  if (region) HIPCHK(hipMemcpy(region, d.ho_region, n_region * 4, hipMemcpyDeviceToHost));
+  return BNMTF_OK;
+} BNMTF_ABI_GUARD
+
 int bnmtf_omega_counts(bnmtf_handle h, uint64_t* total, uint32_t* row, uint32_t* col) try {
   CHK(refuse_obs(h, "bnmtf_omega_counts"));
   if (total) *total = (uint64_t)h->n_obs;

@@ -105,6 +105,19 @@ BNMTF_API int bnmtf_slot_layout(int n, int m, int KP, int world, const uint32_t*
                                 int32_t* unit_map, uint32_t* pair_E, uint32_t* pair_base, uint32_t* off, uint32_t* off16,
                                 int32_t* gen_units, uint16_t* row_blk, int32_t* u_unit_map, uint32_t* u_pair_E,
                                 uint32_t* u_pair_base, uint32_t* u_off16);
+/* A TEST HOOK like bnmtf_slot_layout: the q hand-over tables of one direction (which = 0 rows, 1 cols; csrc/kernel_handover.hip)
+ * and what its region holds now, copied to the host so that the routing can be tested entry by entry
+ * (tests/test_handover_exact_gpu.py).  Synchronises the handle's stream, launches nothing, changes no state; BNMTF_ESTATE when
+ * the handle has no hand-over tables (describe(): handover=0).
+ * info [BNMTF_HANDOVER_INFO_LEN]: the direction's blocks, the other direction's blocks, ho_lds_floats, ho_ppb (pairs per block =
+ * waves of the block shape), ho_filled, ho_regions_current, then the element counts of the five arrays in argument order.  An
+ * array is copied where its pointer is not NULL (a first call with NULL arrays gives the sizes).  t_in / t_out [(slot rows + 1)
+ * / 2][64] words of two 16-bit places (rows 2r and 2r + 1 of a lane) in the block's region / staging area, pk [blocks][other
+ * blocks][3] (staging start, entries, start in the other direction's regions), region_ofs [blocks + 1], region [region_ofs[blocks]
+ * + 256] floats. */
+#define BNMTF_HANDOVER_INFO_LEN 11
+BNMTF_API int bnmtf_handover_dump(bnmtf_handle h, int which, int64_t* info, uint32_t* t_in, uint32_t* t_out, uint32_t* pk,
+                                  uint32_t* region_ofs, float* region);
 
 /* size_Omega and the per-row / per-column observed counts (bit-exact integers;
  * size_Omega = M.sum(), bnmf_gibbs_optimised.py:65; counts :83-84).

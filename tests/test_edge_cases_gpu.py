@@ -1,6 +1,7 @@
 """Edge shapes of the hot path on the device against the oracle (mode updates: every step deterministic):
 a mask with nothing missing (no slots at all: the sweeps reduce to the Gram terms), rank one, a single row / a single
-column, and a mask with most entries missing (slot rows beyond what the on-chip kernels take: the generic kernel)."""
+column, and a mask with most entries missing (160 x 1500 at 90 %: 44 slot rows per lane on the rows, 2-wave blocks on the columns,
+no hand-over)."""
 import numpy as np
 import pytest
 
@@ -25,8 +26,8 @@ def _data(I, J, K, frac_missing, seed):
 @pytest.mark.parametrize("I,J,K,miss", [(70, 90, 6, 0.0), (45, 33, 1, 0.2), (1, 40, 3, 0.1), (50, 1, 2, 0.0), (160, 1500, 5, 0.9)])
 def test_bnmf_gibbs_edge_shapes(monkeypatch, I, J, K, miss, handover):
     """handover = "1": q handed over between the half sweeps wherever its tables can be built -- with nothing missing
-    the regions are empty, with 90 % missing the units need more slot rows than the on-chip kernels take and the hand-over has to
-    stay off by itself."""
+    the regions are empty, at 160 x 1500 the 750 pairs of columns run 2-wave blocks, which hand nothing over, and the hand-over has
+    to stay off by itself."""
     monkeypatch.setenv("BNMTF_HANDOVER", handover)
     R, M, rs = _data(I, J, K, miss, 3)
     U0, V0 = rs.exponential(1.0, (I, K)), rs.exponential(1.0, (J, K))
@@ -34,8 +35,9 @@ def test_bnmf_gibbs_edge_shapes(monkeypatch, I, J, K, miss, handover):
     o.U, o.V, o.tau = U0.copy(), V0.copy(), 0.8
     o.run(4, draw=False)
     b = bnmf_gibbs_optimised(R, M, K, PRI2, verbose=False, seed=1)
-    if handover == "0" or miss >= 0.9:
-        assert "handover=0" in b.describe()
+    # (160 x 1500: the 750 pairs of columns run 2-wave blocks, which hand nothing over -- tests/test_handover_cases_cpu.py; every
+    # other shape here has 8-wave blocks on both directions and builds its tables: the "handover" cases do test the hand-over)
+    assert ("handover=1" in b.describe()) == (handover == "1" and miss < 0.9), b.describe()
     b.U, b.V, b.tau = U0.copy(), V0.copy(), 0.8
     b.run(4, update='mode')
     # the masked SSE comes from Gram identities in fp32 products: its error scales with the terms that cancel (sum R^2), not
