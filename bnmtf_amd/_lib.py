@@ -78,6 +78,8 @@ _SIGS = {
     "bnmtf_kmeans_assign": ([_P, _P, _P, _P, _P], C.c_int),
     "bnmtf_kmeans_sums": ([_P, _P, _P, _P], C.c_int),
     "bnmtf_kmeans_set_row": ([_P, C.c_int, _P], C.c_int),
+    "bnmtf_kmeans_create_list": ([C.c_int, C.c_int, C.c_uint64, _P, _P, _P, C.c_int, C.c_int, C.POINTER(_P)], C.c_int),
+    "bnmtf_kmeans_build_lists": ([C.c_int, C.c_int, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "bnmtf_metric_sums": ([_P, _P, _P, _P, _P, _P], C.c_int),
     "bnmtf_metric_sums_wide": ([_P, _P, _P, _P, C.c_int, _P], C.c_int),
     "bnmtf_set_heldout": ([_P, _P], C.c_int),

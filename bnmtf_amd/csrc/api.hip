@@ -35,13 +35,7 @@ void set_error(const char* fmt, ...) {
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 }  // namespace bnmtf
-// No C++ exception leaves the library: every entry point that returns a status is a function-try-block ending in this handler
-// (round 6: a std::system_error from a thread that could not be had crossed the ABI once -- std::terminate, the caller's process
-// gone; HISTORY 8.4).  Out of host memory -> BNMTF_ENOMEM, anything else -> BNMTF_EINVAL, the message in bnmtf_last_error().
-#define BNMTF_ABI_GUARD                                                                                                              \
-  catch (const std::bad_alloc&) { bnmtf::set_error("out of host memory"); return BNMTF_ENOMEM; }                                     \
-  catch (const std::exception& e) { bnmtf::set_error("host exception: %s", e.what()); return BNMTF_EINVAL; }                         \
-  catch (...) { bnmtf::set_error("host exception"); return BNMTF_EINVAL; }
+// (BNMTF_ABI_GUARD, the handler every entry point that returns a status ends in: model.h)
 extern "C" int bnmtf_shard_range(int64_t n, int rank, int world, int64_t* first, int64_t* count);
 namespace bnmtf {
 static void np_free(bnmtf_model* h);   // api_np.inc

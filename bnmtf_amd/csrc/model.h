@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <exception>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -21,6 +23,14 @@ void set_error(const char* fmt, ...);
       return BNMTF_EHIP;                                                                      \
     }                                                                                         \
   } while (0)
+
+// No C++ exception leaves the library: every entry point that returns a status is a function-try-block ending in this handler
+// (round 6: a std::system_error from a thread that could not be had crossed the ABI once -- std::terminate, the caller's process
+// gone; HISTORY 8.4).  Out of host memory -> BNMTF_ENOMEM, anything else -> BNMTF_EINVAL, the message in bnmtf_last_error().
+#define BNMTF_ABI_GUARD                                                                                                              \
+  catch (const std::bad_alloc&) { bnmtf::set_error("out of host memory"); return BNMTF_ENOMEM; }                                     \
+  catch (const std::exception& e) { bnmtf::set_error("host exception: %s", e.what()); return BNMTF_EINVAL; }                         \
+  catch (...) { bnmtf::set_error("host exception"); return BNMTF_EINVAL; }
 
 #define CHK(expr)                  \
   do {                             \

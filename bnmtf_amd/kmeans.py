@@ -5,6 +5,10 @@ on the GPU in fp64 (bnmtf_kmeans_* of libbnmtf_hip.so); the O(K x coordinates) c
 empty-cluster rule are host code.  There is no CPU compute path here: without the library or a GPU the class raises
 (the NumPy restatement used to check it lives in oracle/kmeans_oracle.py, test infrastructure).
 
+layout='observed' (the models of the observed-entry layout pass it): the device holds the observed entries as two lists instead of
+X and M in full -- bnmtf_kmeans_create_list, DESIGN.md section 2.7 --, so its memory and the work of a pass follow the entries;
+the same calls return the same bits, and everything in this file but the create is shared.
+
 Semantics kept from the reference, all pinned by tests/golden/kmeans.npz (reference runs under `random.seed`):
 centroids start uniformly between each coordinate's observed min and max (same `random.uniform` call order);
 distance = mean squared difference over the coordinates both the point and the centroid know (no overlap = infinitely
@@ -18,13 +22,15 @@ import random
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _observed
 
 max_iterations = 200
 
 
 class KMeans(object):
-    def __init__(self, X, M, K, resolve_empty='singleton', *, device=0):
+    def __init__(self, X, M, K, resolve_empty='singleton', *, device=0, layout='dense'):
+        _observed.check_layout(layout)
+        self._layout = layout                            # 'observed': the device holds the observed entries as two lists
         self._device = 0 if device is None else int(device)
         self._dh = None
         self.X = np.array(X, dtype=float)
@@ -63,10 +69,17 @@ class KMeans(object):
     # ---- device side
     def _device_handle(self):
         if self._dh is None:
-            self._M8 = np.ascontiguousarray(self.M != 0, dtype=np.uint8)
             h = C.c_void_p()
-            _lib.check(_lib.lib().bnmtf_kmeans_create(_lib.ptr(self.X), _lib.ptr(self._M8), self.no_points, self.no_coordinates,
-                                                      int(self.K), self._device, C.byref(h)))
+            if self._layout == 'observed':               # the same calls on the entry list of the compacted (X, M): the same bits
+                points, coords = np.nonzero(self.M != 0)
+                points = np.ascontiguousarray(points, dtype=np.int32); coords = np.ascontiguousarray(coords, dtype=np.int32)
+                values = np.ascontiguousarray(self.X[points, coords], dtype=np.float64)
+                _lib.check(_lib.lib().bnmtf_kmeans_create_list(self.no_points, self.no_coordinates, C.c_uint64(len(points)), _lib.ptr(points),
+                                                               _lib.ptr(coords), _lib.ptr(values), int(self.K), self._device, C.byref(h)))
+            else:
+                self._M8 = np.ascontiguousarray(self.M != 0, dtype=np.uint8)
+                _lib.check(_lib.lib().bnmtf_kmeans_create(_lib.ptr(self.X), _lib.ptr(self._M8), self.no_points, self.no_coordinates,
+                                                          int(self.K), self._device, C.byref(h)))
             self._dh = h
         return self._dh
 

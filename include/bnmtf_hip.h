@@ -358,6 +358,21 @@ BNMTF_API int bnmtf_kmeans_sums(void* h, const int32_t* assign, double* cnt_out,
 /* X[index][:] = values: `self.centroids[c] = self.X[index]` (kmeans.py:141) makes the refilled centroid a view of the data
  * point, so the means written into the centroid afterwards (:158-163) change the point; the host class mirrors that */
 BNMTF_API int bnmtf_kmeans_set_row(void* h, int index, const double* values);
+/* The same handle from the n observed entries (point, coordinate, value), given in any order: device memory and the work of a
+ * pass follow n (28 bytes an entry; nothing of size n_points x n_coords), for the data of the observed-entry layout.  assign, sums,
+ * set_row (still n_coords values: the point's observed entries take theirs) and destroy serve it unchanged, and every output
+ * equals, bit for bit, that of a bnmtf_kmeans_create handle of the same (X, M).  A point or a coordinate may be empty.  Refused
+ * with BNMTF_EINVAL before any device call: a null argument, a shape below 1 x 1, K outside 1 .. 1024, n >= 2^31, an entry outside
+ * the matrix, an entry given twice. */
+BNMTF_API int bnmtf_kmeans_create_list(int n_points, int n_coords, uint64_t n, const int32_t* points, const int32_t* coords, const double* values,
+                             int K, int device, void** out);
+/* The host half of bnmtf_kmeans_create_list on its own (no GPU needed), its checks included: point_ptr [n_points + 1], point_coord /
+ * point_val [n] -- a point's entries ordered by (coordinate & 63, coordinate) --, coord_ptr [n_coords + 1], coord_point / coord_val
+ * [n] -- a coordinate's entries ordered by (point & 3, point) -- and point_to_coord [n], the place in the coordinate list of the
+ * entry at each place of the point list.  Any output may be null. */
+BNMTF_API int bnmtf_kmeans_build_lists(int n_points, int n_coords, uint64_t n, const int32_t* points, const int32_t* coords, const double* values,
+                             uint32_t* point_ptr, uint32_t* point_coord, double* point_val, uint32_t* coord_ptr, uint32_t* coord_point,
+                             double* coord_val, uint32_t* point_to_coord);
 
 /* ---- measurement aids (bench.py) --------------------------------------- */
 #define BNMTF_KERNEL_GEMM_ROWS 0   /* P  = R~ . V      (U/F step numerators)        */
