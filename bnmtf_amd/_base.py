@@ -79,6 +79,38 @@ def metrics_from_sums(s):
     return {"MSE": sse / n, "R^2": (1.0 - sse / ss_tot) if ss_tot != 0.0 else np.inf, "Rp": float(rp)}
 
 
+def check_binary(mask, name):
+    """The device holds 0/1 masks; the reference would weight by the values of a mask (all its callers pass 0/1).  Returns the
+    mask as booleans."""
+    mask = np.asarray(mask)
+    nonzero = mask != 0
+    assert (mask == nonzero).all(), "The indicator matrix %s must contain only 0 and 1." % name
+    return nonzero
+
+
+def performances(perf):
+    """all_performances (bnmf_gibbs_optimised.py:123) from the [iterations][3] array the device calls fill."""
+    return {'MSE': list(perf[:, 0]), 'R^2': list(perf[:, 1]), 'Rp': list(perf[:, 2])}
+
+
+def information_criterion(metric, estimate, log_likelihood, mse, n_parameters, size_Omega, elbo=lambda: 0.):
+    """quality() of every model class (bnmf_gibbs_optimised.py:227-245): estimate() gives what log_likelihood(*estimate) and
+    mse(*estimate) are evaluated at -- the posterior means of a sampler, nothing for a class that keeps its estimate itself."""
+    assert metric in ['loglikelihood', 'BIC', 'AIC', 'MSE', 'ELBO'], 'Unrecognised metric for model quality: %s.' % metric
+    estimate = estimate()
+    ll = log_likelihood(*estimate)
+    if metric == 'loglikelihood':
+        return ll
+    elif metric == 'BIC':
+        return - 2 * ll + n_parameters * math.log(size_Omega)
+    elif metric == 'AIC':
+        return - 2 * ll + 2 * n_parameters
+    elif metric == 'MSE':
+        return mse(*estimate)
+    elif metric == 'ELBO':
+        return elbo()
+
+
 class HeldoutMixin(object):
     """Held-out performance per iteration, run(..., M_test=): what the classes that own a device handle (`_h`, `_handle()`, R) share
     -- DeviceModel's and nmf_np.NPDevice's.  The mask is validated on the host, set on the handle before the device call and its
@@ -92,7 +124,7 @@ class HeldoutMixin(object):
         Mt = np.asarray(M_test)
         assert Mt.shape == self.R.shape, "Input matrix R is not of the same size as the held-out indicator matrix M_test: " \
             "%s and %s respectively." % (self.R.shape, Mt.shape)
-        assert ((Mt == 0) | (Mt == 1)).all(), "The indicator matrix M_test must contain only 0 and 1."
+        check_binary(Mt, "M_test")
         assert Mt.any(), "The held-out indicator matrix M_test has no entries."
         from ._lib import BnmtfError
         if getattr(self, "_blocks", None) is not None:
@@ -158,15 +190,18 @@ class DeviceModel(HeldoutMixin):
     def _lambda_arrays(self):
         raise NotImplementedError
 
+    def _draw_seed(self):
+        """The Philox key of a model that was given none, when its handle is made: from NumPy's global stream, which the
+        reference's samplers follow."""
+        if self._seed is None:
+            self._seed = int(np.random.randint(0, 2 ** 62))
+
     def _handle(self):
         if self._h is None:
             L = _lib.lib()
-            if self._seed is None:      # follow NumPy's global seeding like the reference's samplers do
-                self._seed = int(np.random.randint(0, 2 ** 62))
+            self._draw_seed()
             lr, lc, ls = self._lambda_arrays()
-            # the device holds a 0/1 mask; the reference would weight by the values of M (all its callers pass 0/1)
-            Mb = np.ascontiguousarray(self.M != 0)              # one byte per entry already: handed over as uint8 without a copy
-            assert (self.M == Mb).all(), "The indicator matrix M must contain only 0 and 1."
+            Mb = np.ascontiguousarray(check_binary(self.M, "M"))        # one byte per entry already: handed over as uint8 without a copy
             self._keep = (np.ascontiguousarray(self.R, dtype=np.float32),
                           Mb.view(np.uint8),
                           _lib.f64(lr), _lib.f64(lc), None if ls is None else _lib.f64(ls),
@@ -260,8 +295,7 @@ class DeviceModel(HeldoutMixin):
     def _metric_sums(self, M_pred, A, S, B):
         out = np.zeros(6)
         if M_pred is not None:
-            Mp_ = np.asarray(M_pred)
-            assert ((Mp_ == 0) | (Mp_ == 1)).all(), "The indicator matrix M_pred must contain only 0 and 1."
+            check_binary(M_pred, "M_pred")
         Mp = None if M_pred is None else np.ascontiguousarray(np.asarray(M_pred) != 0, dtype=np.uint8)
         A = None if A is None else _lib.f64(A)
         S = None if S is None else _lib.f64(S)

@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._base import check_binary
 
 LAYOUTS = ('dense', 'observed')
 MAX_RANK = 256          # BNMTF_OBS_MAX_RANK: nothing ties a rank to a lane, one handle takes them all
@@ -132,8 +133,7 @@ class ObservedNP(object):
         if self._layout != 'observed':
             return super(ObservedNP, self)._handle()
         if self._h is None:
-            Mb = self.M != 0
-            assert (self.M == Mb).all(), "The indicator matrix M must contain only 0 and 1."
+            Mb = check_binary(self.M, "M")
             rows, cols, vals = entry_list(self.R, Mb)
             self._train_list = (rows, cols, vals)
             h = C.c_void_p()
@@ -173,7 +173,7 @@ class ObservedNP(object):
             return out
         Mp = np.asarray(M_pred)
         assert Mp.shape == (self.I, self.J), "M_pred has the wrong shape: %s instead of %s." % (Mp.shape, (self.I, self.J))
-        assert ((Mp == 0) | (Mp == 1)).all(), "The indicator matrix M_pred must contain only 0 and 1."
+        check_binary(Mp, "M_pred")
         rows, cols, vals = entry_list(self.R, Mp)
         if len(rows):                           # (an empty mask: the dense layout's sums of nothing)
             _lib.check(_lib.lib().bnmtf_onp_metrics(self._handle(), C.c_uint64(len(rows)), _lib.ptr(rows), _lib.ptr(cols), _lib.ptr(vals), _lib.ptr(out)))
@@ -224,8 +224,7 @@ def entry_list(R, Mask):
 
 def _create(model, create, ranks, lambdas):
     """The handle `create` gives for a model's R, M, seed and device, with its ranks and prior rates."""
-    Mb = model.M != 0
-    assert (model.M == Mb).all(), "The indicator matrix M must contain only 0 and 1."
+    Mb = check_binary(model.M, "M")
     rows, cols, vals = entry_list(model.R, Mb)
     model._train_list = (rows, cols, vals)
     lams = [_lib.f64(l) for l in lambdas]
@@ -251,7 +250,7 @@ def _pred_list(model, M_pred):
     if M_pred is None:
         return model._train_list
     Mp = np.asarray(M_pred)
-    assert ((Mp == 0) | (Mp == 1)).all(), "The indicator matrix M_pred must contain only 0 and 1."
+    check_binary(Mp, "M_pred")
     assert Mp.shape == model.R.shape, "Input matrix R is not of the same size as the indicator matrix M_pred: %s and %s respectively." % (model.R.shape, Mp.shape)
     return entry_list(model.R, Mp)
 

@@ -50,6 +50,8 @@ def _kinds():
 
 
 def _kind(model):
+    # (the two Gibbs classes share one run(), _sampler.GibbsSampler's: isinstance tells them apart, and `run is cls.run` keeps out a
+    # subclass that brings its own -- nmf_icm / nmtf_icm, whose run() is _sampler.ICMRules')
     for kind, cls, needs in _kinds():
         if isinstance(model, cls) and type(model).run is cls.run and all(hasattr(model, f) for f in needs):
             return kind
@@ -121,18 +123,12 @@ def run_many(models, iterations, update='draw', store_samples=True, expectation=
         n = len(ms)
         arr = lambda xs: (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in xs])
         hs = (C.c_void_p * n)(*[m._handle().value for m in ms])
-        if kind == "bnmf":
-            states = [(np.zeros((m.I, m.K)), np.zeros((m.J, m.K)), np.zeros(1)) for m in ms]      # what every model ends with
-            _lib.check(_lib.lib().bnmf_gibbs_run_many(hs, n, bufs[0][0], upd, arr([b[1] for b in bufs]), arr([b[2] for b in bufs]),
-                                                      arr([b[3] for b in bufs]), arr([b[4] for b in bufs]), arr([b[5] for b in bufs]),
-                                                      arr([s[0] for s in states]), arr([s[1] for s in states]), arr([s[2] for s in states])))
-        else:
-            states = [(np.zeros((m.I, m.K)), np.zeros((m.K, m.L)), np.zeros((m.J, m.L)), np.zeros(1)) for m in ms]
-            _lib.check(_lib.lib().bnmtf_gibbs_run_many(hs, n, bufs[0][0], upd, arr([b[1] for b in bufs]), arr([b[2] for b in bufs]),
-                                                       arr([b[3] for b in bufs]), arr([b[4] for b in bufs]), arr([b[5] for b in bufs]),
-                                                       arr([b[6] for b in bufs]),
-                                                       arr([s[0] for s in states]), arr([s[1] for s in states]), arr([s[2] for s in states]),
-                                                       arr([s[3] for s in states])))
+        states = [tuple(np.zeros(s) for s in m._shapes()) + (np.zeros(1),) for m in ms]      # what every model ends with: its factors, tau
+        # the entry point takes, per output array of run() and then per array of the final state, the models' pointers: both in
+        # the order of the class's factor tuple (_sampler.py)
+        outputs = zip(*[b[1:] for b in bufs])
+        entry = getattr(_lib.lib(), ms[0]._DENSE["run_many"])
+        _lib.check(entry(hs, n, bufs[0][0], upd, *[arr(col) for col in outputs], *[arr(col) for col in zip(*states)]))
         for i, m, b, st in zip(idx, ms, bufs, states):
             out[i] = m._run_finish(b, store_samples, state=st)
     return out

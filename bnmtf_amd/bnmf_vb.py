@@ -12,7 +12,8 @@ import numpy as np
 import scipy.special
 
 from . import _lib
-from ._base import DeviceModel, broadcast_lambda, check_rank, check_R_M, metrics_from_sums
+from ._base import (DeviceModel, broadcast_lambda, check_binary, check_rank, check_R_M, information_criterion, metrics_from_sums,
+                    performances)
 from .distributions import TN_vector_expectation, TN_vector_variance, gamma_expectation, gamma_expectation_log
 from ._blocked import BLOCK, MAX_BLOCKS, VBColumnBlocks
 
@@ -53,8 +54,7 @@ class bnmf_vb_optimised(DeviceModel):
     def _metric_sums(self, M_pred, A, S, B):
         if self._blocks is not None:
             if M_pred is not None:
-                Mp_ = np.asarray(M_pred)
-                assert ((Mp_ == 0) | (Mp_ == 1)).all(), "The indicator matrix M_pred must contain only 0 and 1."
+                check_binary(M_pred, "M_pred")
             return self._blocks.metric_sums(M_pred, self.expU if A is None else A, self.expV if B is None else B)
         return super(bnmf_vb_optimised, self)._metric_sums(M_pred, A, S, B)
 
@@ -148,7 +148,7 @@ class bnmf_vb_optimised(DeviceModel):
         self._pull()
         self.all_exp_tau = list(exptau)
         self.all_times = list(times)
-        self.all_performances = {'MSE': list(perf[:, 0]), 'R^2': list(perf[:, 1]), 'Rp': list(perf[:, 2])}
+        self.all_performances = performances(perf)
         self.all_elbo_terms = terms        # per iteration: exp_square_diff, beta_s, then (quad, log erfc, log tau, lambda E) sums of U and of V
         self._all_elbo = None              # (all_elbo: finished from the terms when somebody reads it -- a model search reads the last state only)
         if it > 0:
@@ -320,18 +320,9 @@ class bnmf_vb_optimised(DeviceModel):
 
     def quality(self, metric):
         """:247-262."""
-        assert metric in ['loglikelihood', 'BIC', 'AIC', 'MSE', 'ELBO'], 'Unrecognised metric for model quality: %s.' % metric
-        log_likelihood = self.log_likelihood()
-        if metric == 'loglikelihood':
-            return log_likelihood
-        elif metric == 'BIC':
-            return - 2 * log_likelihood + (self.I * self.K + self.J * self.K) * math.log(self.size_Omega)
-        elif metric == 'AIC':
-            return - 2 * log_likelihood + 2 * (self.I * self.K + self.J * self.K)
-        elif metric == 'MSE':
-            return metrics_from_sums(self._metric_sums(None, self.expU, None, self.expV))['MSE']
-        elif metric == 'ELBO':
-            return self.elbo()
+        return information_criterion(metric, tuple, self.log_likelihood,
+                                     lambda: metrics_from_sums(self._metric_sums(None, self.expU, None, self.expV))['MSE'],
+                                     self.I * self.K + self.J * self.K, self.size_Omega, self.elbo)
 
     def log_likelihood(self):
         """:264-266."""

@@ -18,7 +18,7 @@ import numpy as np
 import scipy.special
 
 from . import _lib
-from ._base import DeviceModel, broadcast_lambda, check_rank, check_R_M, metrics_from_sums
+from ._base import DeviceModel, broadcast_lambda, check_rank, check_R_M, information_criterion, metrics_from_sums, performances
 from .distributions import TN_vector_expectation, TN_vector_variance, gamma_expectation, gamma_expectation_log
 from .kmeans import KMeans
 
@@ -144,7 +144,7 @@ class bnmtf_vb_optimised(DeviceModel):
         self._pull()
         self.all_exp_tau = list(exptau)
         self.all_times = list(times)
-        self.all_performances = {'MSE': list(perf[:, 0]), 'R^2': list(perf[:, 1]), 'Rp': list(perf[:, 2])}
+        self.all_performances = performances(perf)
         if it > 0:
             self.alpha_s = self.alpha + self.size_Omega / 2.0
             self.beta_s = terms[-1, 1]
@@ -238,19 +238,9 @@ class bnmtf_vb_optimised(DeviceModel):
 
     def quality(self, metric):
         """:320-337."""
-        assert metric in ['loglikelihood', 'BIC', 'AIC', 'MSE', 'ELBO'], 'Unrecognised metric for model quality: %s.' % metric
-        log_likelihood = self.log_likelihood()
-        npar = self.I * self.K + self.K * self.L + self.J * self.L
-        if metric == 'loglikelihood':
-            return log_likelihood
-        elif metric == 'BIC':
-            return - 2 * log_likelihood + npar * math.log(self.size_Omega)
-        elif metric == 'AIC':
-            return - 2 * log_likelihood + 2 * npar
-        elif metric == 'MSE':
-            return metrics_from_sums(self._metric_sums(None, self.expF, self.expS, self.expG))['MSE']
-        elif metric == 'ELBO':
-            return self.elbo()
+        return information_criterion(metric, tuple, self.log_likelihood,
+                                     lambda: metrics_from_sums(self._metric_sums(None, self.expF, self.expS, self.expG))['MSE'],
+                                     self.I * self.K + self.K * self.L + self.J * self.L, self.size_Omega, self.elbo)
 
     def log_likelihood(self):
         """:339-342."""

@@ -25,7 +25,7 @@ import math
 import numpy as np
 
 from . import _lib, _observed
-from ._base import HeldoutMixin, check_R_M, check_rank, compute_MSE, compute_R2, compute_Rp
+from ._base import HeldoutMixin, check_binary, check_R_M, check_rank, compute_MSE, compute_R2, compute_Rp, performances
 
 MAX_RANK_NP = 256
 
@@ -56,8 +56,7 @@ class NPDevice(HeldoutMixin):
     def _handle(self):
         if self._h is None:
             R32 = np.ascontiguousarray(self.R, dtype=np.float32)
-            Mb = np.ascontiguousarray(self.M != 0)
-            assert (self.M == Mb).all(), "The indicator matrix M must contain only 0 and 1."
+            Mb = np.ascontiguousarray(check_binary(self.M, "M"))
             M8 = Mb.view(np.uint8)
             h = C.c_void_p()
             _lib.check(_lib.lib().bnmtf_np_create(_lib.ptr(R32), _lib.ptr(M8), self.I, self.J, self.K, getattr(self, "L", 0),
@@ -100,8 +99,7 @@ class NPDevice(HeldoutMixin):
         if M_pred is not None:
             Mp_ = np.asarray(M_pred)
             assert Mp_.shape == (self.I, self.J), "M_pred has the wrong shape: %s instead of %s." % (Mp_.shape, (self.I, self.J))
-            assert ((Mp_ == 0) | (Mp_ == 1)).all(), "The indicator matrix M_pred must contain only 0 and 1."
-            Mp = np.ascontiguousarray(Mp_ != 0, dtype=np.uint8)
+            Mp = np.ascontiguousarray(check_binary(Mp_, "M_pred"), dtype=np.uint8)
         out = np.zeros(8)
         _lib.check(_lib.lib().bnmtf_np_metrics(self._handle(), _lib.ptr(Mp), _lib.ptr(out)))
         return out
@@ -128,7 +126,7 @@ class NPDevice(HeldoutMixin):
         """What run() does behind the device call."""
         self._pull()
         self.all_times = list(times)
-        self.all_performances = {'MSE': list(perf[:, 0]), 'R^2': list(perf[:, 1]), 'Rp': list(perf[:, 2])}
+        self.all_performances = performances(perf)
         if self.verbose:
             for i in range(it):
                 print("Iteration %s. I-divergence: %s. MSE: %s. R^2: %s. Rp: %s." % (i + 1, idiv[i], perf[i, 0], perf[i, 1], perf[i, 2]))

@@ -97,3 +97,28 @@ def test_draws_follow_the_oracles_chain_and_a_narrow_model_agrees_with_its_block
     p = b.predict(1.0 - M, 1, 1)
     assert np.isfinite(p["MSE"])
     b.close()
+
+
+def test_quality_of_a_blocked_model_is_the_oracles_on_the_same_samples():
+    """quality() (:262-280) of a model in blocks, all five metrics: the posterior means of the stored samples, the masked sums
+    through the blocks' full-width metric call.  The oracle is given the model's own samples, so both evaluate the same fp64 means;
+    R is fp32-representable (the device holds fp32), and what is left is the summation order of fp64 sums over 1 700 entries and
+    the cancellation in SSE = sum R^2 - 2 sum R P + sum P^2 (terms up to ~1e3 times the SSE): 1e-16 x 1e3 x 2e3, within 1e-9."""
+    rs = np.random.RandomState(4)
+    I, J, K, L = 48, 40, 5, 66
+    R = (rs.exponential(1.0, (I, 4)) @ rs.exponential(1.0, (4, J)) + 0.1 * rs.randn(I, J)).astype(np.float32).astype(float)
+    M = (rs.rand(I, J) >= 0.1).astype(float)
+    M[np.arange(I), rs.randint(0, J, I)] = 1.0; M[rs.randint(0, I, J), np.arange(J)] = 1.0
+    pri = dict(alpha=1.0, beta=1.0, lambdaF=0.1, lambdaS=0.1, lambdaG=0.1)
+    np.random.seed(3)
+    b = bnmtf_gibbs_optimised(R, M, K, L, pri, verbose=False, seed=17)
+    b.initialise('random', 'random')
+    assert "blocks of F" in b.describe()
+    b.run(3)
+    o = O.BNMTFGibbsOracle(R, M, K, L, pri, seed=17)
+    o.all_F, o.all_S, o.all_G, o.all_tau = (np.array(a, dtype=float) for a in (b.all_F, b.all_S, b.all_G, b.all_tau))
+    for metric in ["loglikelihood", "BIC", "AIC", "MSE", "ELBO"]:
+        got, want = b.quality(metric, 1, 1), o.quality(metric, 1, 1)
+        print(metric, got, want)
+        np.testing.assert_allclose(got, want, rtol=1e-9, err_msg=metric)
+    b.close()
