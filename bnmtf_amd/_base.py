@@ -7,6 +7,7 @@ import math
 import numpy as np
 
 from . import _lib
+from .entries import Entries
 
 
 def check_rank(what, limit, **ranks):
@@ -121,6 +122,9 @@ class HeldoutMixin(object):
         takes).  Same shape as R, at least one entry; it may overlap the training mask, as predict() allows."""
         if M_test is None:
             return None
+        if isinstance(M_test, Entries):
+            raise _lib.BnmtfError("%s: run(M_test=) takes a 0/1 mask shaped like R on the dense layout; an Entries is taken by the "
+                                  "two-factor models with layout='observed' (Entries.to_dense() gives the mask)" % type(self).__name__)
         Mt = np.asarray(M_test)
         assert Mt.shape == self.R.shape, "Input matrix R is not of the same size as the held-out indicator matrix M_test: " \
             "%s and %s respectively." % (self.R.shape, Mt.shape)

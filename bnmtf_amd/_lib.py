@@ -84,6 +84,7 @@ _SIGS = {
     "bnmtf_metric_sums_wide": ([_P, _P, _P, _P, C.c_int, _P], C.c_int),
     "bnmtf_set_heldout": ([_P, _P], C.c_int),
     "bnmtf_get_heldout": ([_P, C.c_int, _P], C.c_int),
+    "bnmtf_set_heldout_entries": ([_P, C.c_uint64, _P, _P, _P], C.c_int),
     "bnmtf_set_tau": ([_P, C.c_double], C.c_int),
     "bnmf_vb_half_sweep": ([_P, C.c_int], C.c_int),
     "bnmf_vb_esd_terms": ([_P, _P], C.c_int),

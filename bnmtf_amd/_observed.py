@@ -3,15 +3,18 @@ bnmf_vb_observed and bnmtf_vb_observed: the host side of the observed-entry layo
 
 The device keeps the residual R_ij - U_i.V_j -- for the non-probabilistic models the product P_ij itself -- on the OBSERVED entries
 (csrc/kernel_obs.hip, kernel_obs_vb.hip, kernel_obs_np.hip), so cost and device memory follow the number of observed entries: the
-layout for matrices that are mostly missing.  R and M stay dense NumPy arrays at the Python boundary; this module turns the mask
-into the entry lists the library takes, owns the bnmtf_obs_create / bnmtf_otri_create / bnmtf_onp_create handle of a model and
-states what the layout does not run."""
+layout for matrices that are mostly missing.  The three classes on the two-factor handle (bnmf_gibbs_optimised, nmf_icm,
+bnmf_vb_observed) take the matrix as dense NumPy arrays R, M or as an Entries (entries.py: lists, nothing of size I x J on the
+host either), and an Entries as run()'s M_test for a held-out curve; for the other classes R and M stay dense at the Python
+boundary.  This module turns either form into the entry lists the library takes, owns the bnmtf_obs_create / bnmtf_otri_create /
+bnmtf_onp_create handle of a model and states what the layout does not run."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from ._base import check_binary
+from ._base import check_binary, check_R_M
+from .entries import Entries
 
 LAYOUTS = ('dense', 'observed')
 MAX_RANK = 256          # BNMTF_OBS_MAX_RANK: nothing ties a rank to a lane, one handle takes them all
@@ -29,10 +32,13 @@ REFUSALS = {
     "set_profiling": "the per-kernel event brackets belong to the dense layout",
     "masked_sums": "the sums over the missing entries belong to the dense layout's matrix-core product",
     "column_maxima": "the fixed-point grid belongs to the dense layout's matrix-core product",
-    "run(M_test=)": "held-out curves are kept by the dense layout only; use predict(M_test) after the run",
+    "run(M_test=)": "a 0/1 mask belongs to the dense layout: pass the held-out entries with their values as an Entries",
     "run(expectation=)": "the posterior sums on the device belong to the dense layout; approx_expectation averages the stored samples",
     "run_many": "batched launches take models of the dense layout",
 }
+
+HELDOUT_TWO_FACTOR = ("held-out curves on this layout are built for the two-factor models bnmf_gibbs_optimised, nmf_icm and "
+                      "bnmf_vb_observed, which take the held-out entries as an Entries; use predict(M_test) after the run")
 
 
 def refuse(model, what, why=None):
@@ -66,15 +72,41 @@ class ObservedLayout(object):
     def omega_counts(self):
         if self._layout != 'observed':
             return super(ObservedLayout, self).omega_counts()
-        Mb = self.M != 0
-        return int(Mb.sum()), Mb.sum(axis=1).astype(np.uint32), Mb.sum(axis=0).astype(np.uint32)
+        rows, cols, _ = entries_of(self)
+        return len(rows), np.bincount(rows, minlength=self.I).astype(np.uint32), np.bincount(cols, minlength=self.J).astype(np.uint32)
 
     def _check_heldout(self, M_test):
+        """run()'s M_test on this layout, before any device call: None, or an Entries of the model's shape with at least one entry
+        (it may overlap the training entries); a dense mask is the dense layout's."""
         if self._layout != 'observed':
             return super(ObservedLayout, self)._check_heldout(M_test)
-        if M_test is not None:
+        if M_test is None:
+            return None
+        if hasattr(self, "L"):
+            refuse(self, "run(M_test=)", HELDOUT_TWO_FACTOR)
+        if not isinstance(M_test, Entries):
             refuse(self, "run(M_test=)")
-        return None
+        assert M_test.shape == (self.I, self.J), "Input matrix R is not of the same size as the held-out entries M_test: %s and %s respectively." \
+            % ((self.I, self.J), M_test.shape)
+        assert len(M_test) > 0, "The held-out entries M_test are empty."
+        return M_test
+
+    def _set_heldout(self, Et):
+        """The list of _check_heldout onto the handle (bnmtf_set_heldout_entries) -- or, with None, a list left there by an
+        earlier run() off it."""
+        if self._layout != 'observed':
+            return super(ObservedLayout, self)._set_heldout(Et)
+        held = getattr(self, "_heldout", None)
+        if Et is None:
+            if held is not None and held[0] is self._h:
+                _lib.check(_lib.lib().bnmtf_set_heldout_entries(self._handle(), C.c_uint64(0), None, None, None))
+            self._heldout = None
+            if hasattr(self, "all_performances_test"):
+                del self.all_performances_test
+            return
+        vals = Et.values32()
+        _lib.check(_lib.lib().bnmtf_set_heldout_entries(self._handle(), C.c_uint64(len(Et)), _lib.ptr(Et.rows), _lib.ptr(Et.cols), _lib.ptr(vals)))
+        self._heldout = (self._h, len(Et))
 
 
 class ObservedVB(ObservedLayout):
@@ -159,7 +191,7 @@ class ObservedNP(object):
         if self._layout != 'observed':
             return super(ObservedNP, self)._check_heldout(M_test)
         if M_test is not None:
-            refuse(self, "run(M_test=)")
+            refuse(self, "run(M_test=)", HELDOUT_TWO_FACTOR)
         return None
 
     def _sums(self, M_pred=None):
@@ -222,10 +254,56 @@ def entry_list(R, Mask):
             np.ascontiguousarray(np.asarray(R)[Mb], dtype=np.float32))
 
 
+def take_R_M(model, R, M, layout='observed'):
+    """The constructor's first step on the three classes that take either form: R and M onto the model with check_R_M's
+    assertions, and ((I, J), size_Omega).  Dense arrays as ever; an Entries (then M is None) only with layout='observed'."""
+    if isinstance(R, Entries):
+        if layout != 'observed':
+            raise _lib.BnmtfError("%s: an Entries is taken with layout='observed'; layout='dense' takes R and M as dense arrays "
+                                  "(Entries.to_dense() gives them)" % type(model).__name__)
+        if M is not None:
+            raise _lib.BnmtfError("%s: with an Entries as R the mask is the list itself: M must be None" % type(model).__name__)
+        model.R, model.M = R, None
+        R.check_rows_columns()
+        return R.shape, len(R)
+    model.R = np.array(R, dtype=float)
+    model.M = np.array(M, dtype=float)
+    check_R_M(model.R, model.M)
+    return model.R.shape, model.M.sum()
+
+
+def refuse_entries(model, *given):
+    """The classes that do not take an Entries yet say so at construction."""
+    if any(isinstance(g, Entries) for g in given):
+        raise _lib.BnmtfError("%s: an Entries is taken by the models on the two-factor handle of layout='observed' only "
+                              "(bnmf_gibbs_optimised, nmf_icm, bnmf_vb_observed); this class takes R and M as dense arrays"
+                              % type(model).__name__)
+
+
+def entries_of(model, M_pred=None, name="M"):
+    """(rows, cols, values in fp32) of a model's training entries (M_pred None), or of M_pred -- an Entries, whose values are the
+    true values at its entries, or a 0/1 matrix that picks them from the model's dense R: the one place where either form of
+    input becomes the lists the library takes: row major, the fp32 cast entry_list's."""
+    if M_pred is None:
+        if isinstance(model.R, Entries):
+            return model.R.row_major()
+        return entry_list(model.R, check_binary(model.M, name))
+    if isinstance(M_pred, Entries):
+        assert M_pred.shape == tuple(model.R.shape), "Input matrix R is not of the same size as the entries %s: %s and %s respectively." \
+            % (name, tuple(model.R.shape), M_pred.shape)
+        return M_pred.row_major()
+    if isinstance(model.R, Entries):
+        raise _lib.BnmtfError("%s: a model built from an Entries holds no dense R to pick the values of a 0/1 mask from: pass %s "
+                              "as an Entries with the true values at its entries" % (type(model).__name__, name))
+    Mp = np.asarray(M_pred)
+    check_binary(Mp, name)
+    assert Mp.shape == model.R.shape, "Input matrix R is not of the same size as the indicator matrix %s: %s and %s respectively." % (name, model.R.shape, Mp.shape)
+    return entry_list(model.R, Mp)
+
+
 def _create(model, create, ranks, lambdas):
-    """The handle `create` gives for a model's R, M, seed and device, with its ranks and prior rates."""
-    Mb = check_binary(model.M, "M")
-    rows, cols, vals = entry_list(model.R, Mb)
+    """The handle `create` gives for a model's entries, seed and device, with its ranks and prior rates."""
+    rows, cols, vals = entries_of(model)
     model._train_list = (rows, cols, vals)
     lams = [_lib.f64(l) for l in lambdas]
     h = C.c_void_p()
@@ -249,16 +327,14 @@ def _pred_list(model, M_pred):
     """The entry list of M_pred (None: the training entries) for the metric calls."""
     if M_pred is None:
         return model._train_list
-    Mp = np.asarray(M_pred)
-    check_binary(Mp, "M_pred")
-    assert Mp.shape == model.R.shape, "Input matrix R is not of the same size as the indicator matrix M_pred: %s and %s respectively." % (model.R.shape, Mp.shape)
-    return entry_list(model.R, Mp)
+    return entries_of(model, M_pred, "M_pred")
 
 
 def _list_metric(model, M_pred, call, factors):
-    """The six sums `call` gives for the factors (fp64) over the entries of M_pred (None: the training entries)."""
-    h = model._handle()
-    rows, cols, vals = _pred_list(model, M_pred)
+    """The six sums the library's `call` gives for the factors (fp64) over the entries of M_pred (None: the training entries)."""
+    given = None if M_pred is None else _pred_list(model, M_pred)      # (what it refuses: before any device call)
+    h, call = model._handle(), getattr(_lib.lib(), call)
+    rows, cols, vals = _pred_list(model, None) if given is None else given
     out = np.zeros(6)
     if len(rows) == 0:                      # (an empty mask: the dense layout's sums of nothing)
         return out
@@ -270,9 +346,9 @@ def _list_metric(model, M_pred, call, factors):
 def tri_metric_sums(model, M_pred, F, S, G):
     """The six sums of metrics_from_sums of (F.S).G^T over the entries of M_pred (None: the training entries): F.S and the dot
     products in fp64 (bnmtf_otri_metric_sums), never the sweeps' fp32 effective factor."""
-    return _list_metric(model, M_pred, _lib.lib().bnmtf_otri_metric_sums, (F, S, G))
+    return _list_metric(model, M_pred, "bnmtf_otri_metric_sums", (F, S, G))
 
 
 def metric_sums(model, M_pred, A, B):
     """The six sums of metrics_from_sums of A.B^T over the entries of M_pred (None: the training entries), on the device in fp64."""
-    return _list_metric(model, M_pred, _lib.lib().bnmf_obs_metric_sums, (A, B))
+    return _list_metric(model, M_pred, "bnmf_obs_metric_sums", (A, B))

@@ -112,7 +112,8 @@ class GibbsSampler(_observed.ObservedLayout, DeviceModel):
         metrics and cumulative times come back afterwards.  store_samples=False skips the hand-off of the samples
         (device-resident benchmark mode); update='mode' runs the ICM harness; expectation=(burn_in, thinning) also accumulates
         the posterior means of exactly that approx_expectation(burn_in, thinning) on the device (what the model-selection drivers
-        need: with store_samples=False no sample ever crosses to the host).  M_test (a 0/1 matrix shaped like R; it may overlap
+        need: with store_samples=False no sample ever crosses to the host).  M_test (a 0/1 matrix shaped like R -- with
+        layout='observed' of the two-factor classes an Entries, the held-out entries with their values --; it may overlap
         M): the held-out MSE / R^2 / Rp of the state every iteration ends with are computed on the device and kept in
         all_performances_test; without it no such attribute exists after the call."""
         update = _lib.UPDATE_MODE if update == 'mode' else _lib.UPDATE_DRAW
@@ -138,14 +139,16 @@ class GibbsSampler(_observed.ObservedLayout, DeviceModel):
         """run() with layout='observed': one device call (bnmf_obs_run / bnmtf_otri_run) runs all iterations -- per iteration the
         half sweeps on the entry lists (between them the tri-factorisation's dense S system from the column list) and the
         end-of-iteration kernel; samples, tau, metrics and times come back as from the dense layout's call."""
-        self._check_heldout(M_test)
+        Et = self._check_heldout(M_test)
         if expectation is not None:
             _observed.refuse(self, "run(expectation=)")
         it = int(iterations)
         self._push()
+        self._set_heldout(Et)
         self._dev_expect = None
         bufs = self._buffers(it, store_samples and update != _lib.UPDATE_ICM)
         _lib.check(self._entry("run")(self._handle(), it, int(update), *[_lib.ptr(b) for b in bufs[1:]]))
+        self._finish_heldout(it)
         return bufs
 
     def _run_blocked(self, iterations, update, store_samples, expectation, minimum_TN=0.0, icm=False):
@@ -312,9 +315,9 @@ class ICMRules(object):
         M_test: the held-out metrics of the point estimate every iteration ends with, in all_performances_test (see
         GibbsSampler.run)."""
         if self._layout == 'observed':          # (DESIGN.md section 2.7: the ICM rules on the observed-entry kernels)
-            self._check_heldout(M_test)
+            Et = self._check_heldout(M_test)
             _lib.check(_lib.lib().bnmtf_set_minimum_tn(self._handle(), float(minimum_TN)))
-            bufs = self._run_observed(iterations, _lib.UPDATE_ICM, False, None, None)
+            bufs = self._run_observed(iterations, _lib.UPDATE_ICM, False, None, Et)
             return self._finish_icm(bufs[0], *bufs[-3:])
         Mt = self._check_heldout(M_test)
         it = int(iterations)

@@ -19,12 +19,15 @@ layout='observed' keeps the per-entry state on the OBSERVED entries instead of t
 ones (_observed.py): cost and device memory follow the number of
 observed entries, the layout for matrices that are mostly missing.  Same chain for the same
 seed (same conditionals, same Philox keying), ranks up to 256 on one handle, one GPU; no
-M_test=, expectation=, run_many, set_sweep_path / set_small_path / set_profiling.
+expectation=, run_many, set_sweep_path / set_small_path / set_profiling.  On this layout the
+matrix may be given as lists, bnmf_gibbs_optimised(Entries, None, K, priors, layout='observed')
+(entries.py: nothing of size I x J on the host), and run(M_test=Entries) keeps the held-out
+curve in all_performances_test.
 """
 import numpy as np
 
 from . import _lib, _observed
-from ._base import broadcast_lambda, check_rank, check_R_M
+from ._base import broadcast_lambda, check_rank
 from ._blocked import BLOCK, MAX_BLOCKS, ColumnBlocks
 from ._sampler import GibbsSampler
 
@@ -43,16 +46,12 @@ class bnmf_gibbs_optimised(GibbsSampler):
     def __init__(self, R, M, K, priors, *, seed=None, device=0, verbose=True, rank=0, world=1, comm_id=None, layout='dense'):
         _observed.check_layout(layout)
         self._layout = layout
-        self.R = np.array(R, dtype=float)
-        self.M = np.array(M, dtype=float)
         self.K = K
-        check_R_M(self.R, self.M)
+        (self.I, self.J), self.size_Omega = _observed.take_R_M(self, R, M, layout)      # (dense arrays, or an Entries and None)
         if layout == 'observed':
             _observed.check_constructor(self, world)
         else:
             check_rank("bnmf_gibbs_optimised", MAX_RANK_BLOCKED, K=self.K)
-        (self.I, self.J) = self.R.shape
-        self.size_Omega = self.M.sum()
         self.alpha, self.beta = float(priors['alpha']), float(priors['beta'])
         self.lambdaU = broadcast_lambda(priors['lambdaU'], (self.I, self.K), "lambdaU")
         self.lambdaV = broadcast_lambda(priors['lambdaV'], (self.J, self.K), "lambdaV")

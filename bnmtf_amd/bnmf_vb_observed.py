@@ -6,15 +6,16 @@
 
 The API, the attributes and the assertion messages of bnmf_vb_optimised.  The device keeps the residual R_ij - E[U_i].E[V_j] on
 the OBSERVED entries (csrc/kernel_obs_vb.hip), so cost and device memory follow the number of observed entries: the class for
-matrices that are mostly missing.  R and M stay dense NumPy arrays at the Python boundary.  Ranks up to 256 on one handle (no
-column blocks), one GPU; no run(M_test=), masked_sums, run_many, set_sweep_path / set_small_path / set_profiling.  A class of its
-own, not a keyword of bnmf_vb_optimised: that class keeps refusing layout=."""
+matrices that are mostly missing.  The matrix is given as dense arrays R, M or as lists, bnmf_vb_observed(Entries, None, K, priors)
+(entries.py: nothing of size I x J on the host); run(M_test=Entries) keeps the held-out curve of E[U] E[V]^T in
+all_performances_test.  Ranks up to 256 on one handle (no column blocks), one GPU; no masked_sums, run_many, set_sweep_path /
+set_small_path / set_profiling.  A class of its own, not a keyword of bnmf_vb_optimised: that class keeps refusing layout=."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib, _observed
-from ._base import broadcast_lambda, check_R_M
+from ._base import broadcast_lambda
 from .bnmf_vb import bnmf_vb_optimised
 
 
@@ -23,13 +24,9 @@ class bnmf_vb_observed(_observed.ObservedVB, bnmf_vb_optimised):
 
     def __init__(self, R, M, K, priors, *, device=0, verbose=True, rank=0, world=1, comm_id=None):
         self._layout = 'observed'
-        self.R = np.array(R, dtype=float)
-        self.M = np.array(M, dtype=float)
         self.K = K
-        check_R_M(self.R, self.M)
+        (self.I, self.J), self.size_Omega = _observed.take_R_M(self, R, M)      # (dense arrays, or an Entries and None)
         _observed.check_constructor(self, world)
-        (self.I, self.J) = self.R.shape
-        self.size_Omega = self.M.sum()
         self.alpha, self.beta = float(priors['alpha']), float(priors['beta'])
         self.lambdaU = broadcast_lambda(priors['lambdaU'], (self.I, self.K), "lambdaU")
         self.lambdaV = broadcast_lambda(priors['lambdaV'], (self.J, self.K), "lambdaV")

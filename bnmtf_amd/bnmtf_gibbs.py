@@ -31,6 +31,7 @@ class bnmtf_gibbs_optimised(GibbsSampler):
 
     def __init__(self, R, M, K, L, priors, *, seed=None, device=0, verbose=True, rank=0, world=1, comm_id=None, layout='dense'):
         _observed.check_layout(layout)
+        _observed.refuse_entries(self, R, M)
         self._layout = layout
         self.R = np.array(R, dtype=float)
         self.M = np.array(M, dtype=float)

@@ -24,6 +24,7 @@ class bnmtf_vb_observed(_observed.ObservedVB, bnmtf_vb_optimised):
 
     def __init__(self, R, M, K, L, priors, *, device=0, verbose=True, rank=0, world=1, comm_id=None):
         self._layout = 'observed'
+        _observed.refuse_entries(self, R, M)
         self.R = np.array(R, dtype=float)
         self.M = np.array(M, dtype=float)
         self.K, self.L = K, L

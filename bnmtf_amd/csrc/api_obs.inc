@@ -349,6 +349,19 @@ static int obs_cond_params_dir(bnmtf_model* h, ObsList& d, ObsSweepArgs a, int k
   return BNMTF_OK;
 }
 
+// the held-out launch pair of iteration `it` of a run call, behind the iteration's finish kernel on the handle's stream: the six
+// sums of the factors the iteration ends with (a variational handle: the expectations) over the list of bnmtf_set_heldout_entries.
+// No list: nothing is launched.
+static void obs_heldout_enqueue(bnmtf_model* h, int it) {
+  if (!h->held_n) return;
+  ObsState* s = h->obs;
+  ObsHeldoutArgs a; memset(&a, 0, sizeof(a));
+  a.rowptr = h->held_rowptr; a.col = h->held_col; a.rval = h->held_val;
+  a.A = s->rows.X; a.B = s->cols.X; a.I = h->I; a.K = h->K; a.stride = s->stride;
+  a.part = h->held_part; a.rec = h->held_rec + (size_t)it * 8;
+  launch_obs_heldout(a, h->stream);
+}
+
 // the six sums of metrics_from_sums of A B^T (A [I][W], B [J][W], fp64) over a list of entries in any order
 static int obs_list_metric(bnmtf_model* h, const char* fn, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values,
                            const double* A, const double* B, int W, double sums_out[6]) {
@@ -451,6 +464,7 @@ int bnmf_obs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* V_
   if (n_iter == 0) return BNMTF_OK;
   ObsState* s = h->obs;
   CHK(ensure_rec(h, (size_t)n_iter));
+  CHK(heldout_begin(h, n_iter));
   const int mode = update == BNMTF_UPDATE_DRAW ? kSweepDraw : kSweepMode;
   h->cur_min_x = update == BNMTF_UPDATE_ICM ? (float)h->min_tn : 0.f;
   if (mode == kSweepDraw) CHK(stage_gamma_variates(h, n_iter));
@@ -472,12 +486,14 @@ int bnmf_obs_run(bnmtf_handle h, int n_iter, int update, float* U_out, float* V_
     launch_obs_sweep(a, h->stream);
     launch_obs_finish(obs_finish_args(h, update, it), h->stream);
     CHK(sink.close_slot(it));
+    obs_heldout_enqueue(h, it);
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], h->stream));
     h->iteration++;
   }
   HIPCHK(hipStreamSynchronize(h->stream));
   CHK(sink.finish());
   HIPCHK(hipGetLastError());
+  heldout_end(h, n_iter);
   CHK(obs_fetch_rec(h, n_iter, tau_out, perf_out));
   ev.seconds(n_iter, times_out);
   return BNMTF_OK;
@@ -497,6 +513,49 @@ int bnmf_obs_metric_sums(bnmtf_handle h, uint64_t n, const int32_t* rows, const 
   CHK(obs_check(h, false, kObsNoState));
   if (!rows || !cols || !values || !A || !B || !sums_out) { set_error("bnmf_obs_metric_sums: null argument"); return BNMTF_EINVAL; }
   return obs_list_metric(h, "bnmf_obs_metric_sums", n, rows, cols, values, A, B, h->K, sums_out);
+} BNMTF_ABI_GUARD
+
+// run(M_test=Entries) of the two-factor models on this layout: the held-out entries with their values, in any order, onto the
+// handle (the row-sorted list bnmtf_set_heldout builds from a dense mask; this handle has no dense R to pick the values from)
+int bnmtf_set_heldout_entries(bnmtf_handle h, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values) try {
+  if (!h) { set_error("bnmtf_set_heldout_entries: null handle"); return BNMTF_EINVAL; }
+  if (!h->obs || h->obs->np || obs_is_tri(h)) {
+    set_error("bnmtf_set_heldout_entries: a call of the two-factor handle of bnmtf_obs_create (bnmf_obs_run, bnmf_vbo_run); this is a handle of %s",
+              !h->obs ? (h->np ? "bnmtf_np_create" : "bnmtf_create: it takes a mask, bnmtf_set_heldout") : h->obs->np ? "bnmtf_onp_create" : "bnmtf_otri_create");
+    return BNMTF_EINVAL;
+  }
+  CHK(obs_check(h, false, kObsNoState));
+  const bool clear = n == 0 || !rows || !cols || !values;
+  std::vector<uint32_t> ptr, idx; std::vector<float> val;
+  if (!clear) {
+    if (n >= ((uint64_t)1 << 31)) { set_error("bnmtf_set_heldout_entries: at most 2^31 - 1 entries (n=%llu)", (unsigned long long)n); return BNMTF_EINVAL; }
+    for (uint64_t e = 0; e < n; ++e)
+      if (rows[e] < 0 || rows[e] >= h->I || cols[e] < 0 || cols[e] >= h->J) {
+        set_error("bnmtf_set_heldout_entries: entry %llu (%d, %d) lies outside the %d x %d matrix", (unsigned long long)e, rows[e], cols[e], h->I, h->J);
+        return BNMTF_EINVAL;
+      }
+    const long long dup = obs_sort(n, rows, cols, values, h->I, h->J, ptr, idx, val);
+    if (dup >= 0) {
+      const int i = (int)(std::upper_bound(ptr.begin(), ptr.end(), (uint32_t)dup) - ptr.begin()) - 1;
+      set_error("bnmtf_set_heldout_entries: the entry (%d, %u) occurs twice (position %lld of the sorted list)", i, idx[(size_t)dup], dup);
+      return BNMTF_EINVAL;
+    }
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  heldout_free(h);
+  if (clear) return BNMTF_OK;
+  auto build = [&]() -> int {
+    CHK(upload(&h->held_rowptr, ptr, h->stream));
+    CHK(upload(&h->held_col, idx, h->stream));
+    CHK(upload(&h->held_val, val, h->stream));
+    CHK(dalloc(&h->held_part, (size_t)heldout_blocks(h->I) * 8));
+    return BNMTF_OK;
+  };
+  int rc;
+  try { rc = build(); } catch (...) { heldout_free(h); throw; }      // (a build that fails midway, by a status or by an exception, leaves no list behind)
+  if (rc != BNMTF_OK) { heldout_free(h); return rc; }
+  h->held_n = (size_t)n;
+  return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
 }  // extern "C"
@@ -554,6 +613,7 @@ int bnmf_vbo_run(bnmtf_handle h, int n_iter, double* exptau_out, double* perf_ou
   if (n_iter == 0) return BNMTF_OK;
   ObsState* s = h->obs;
   CHK(vb_reserve_rec(h, n_iter));
+  CHK(heldout_begin(h, n_iter));
   EventList ev;
   CHK(ev.create(times_out ? n_iter + 1 : 0));
   if (times_out) HIPCHK(hipEventRecord(ev[0], h->stream));
@@ -565,11 +625,13 @@ int bnmf_vbo_run(bnmtf_handle h, int n_iter, double* exptau_out, double* perf_ou
     a.stat = s->cols.vstat; a.part = s->part;
     launch_obs_vb_sweep(a, h->stream);
     launch_obs_vb_finish(obs_vb_finish_args(h, it), h->stream);
+    obs_heldout_enqueue(h, it);
     if (times_out) HIPCHK(hipEventRecord(ev[it + 1], h->stream));
     h->iteration++;
   }
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
+  heldout_end(h, n_iter);
   std::vector<double> rec((size_t)n_iter * 16);
   HIPCHK(hipMemcpy(rec.data(), h->vb_rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
   unpack_vb_rec(rec.data(), n_iter, exptau_out, perf_out, elbo_terms_out);

@@ -218,7 +218,10 @@ __global__ __launch_bounds__(256) void heldout_fold_many(const HeldoutFoldPack* 
   heldout_fold_body(p.part, p.nblocks, p.rec + (size_t)it * 8);
 }
 
-// the fold behind a main kernel of `nblocks` blocks -- launched, or recorded behind the main kernel's record
+}  // namespace
+
+// the fold behind a main kernel of `nblocks` blocks -- launched, or recorded behind the main kernel's record (kernels.h: the
+// observed-entry layout's held-out kernel, kernel_obs_heldout.hip, ends in it as well)
 void launch_fold(const double* part, int nblocks, double* rec, hipStream_t st) {
   if (g_recorder) {
     HeldoutFoldPack p; memset(&p, 0, sizeof(p));
@@ -228,6 +231,8 @@ void launch_fold(const double* part, int nblocks, double* rec, hipStream_t st) {
   }
   hipLaunchKernelGGL(heldout_fold_kernel, dim3(1), dim3(256), 0, st, part, nblocks, rec);
 }
+
+namespace {
 
 // the values of R at the listed entries: a wave per row, its lanes along the row's entries
 __global__ __launch_bounds__(256) void heldout_values_kernel(const float* R, int I, int J, const uint32_t* rowptr, const uint32_t* col, float* rval) {

@@ -553,6 +553,9 @@ __host__ __device__ inline int heldout_blocks(int I) { return (I + kHeldoutRowsP
 // iteration's own) -- the main kernel and the fold
 void launch_heldout(const HeldoutArgs& a, hipStream_t st);
 void launch_heldout_np(const HeldoutNpArgs& a, hipStream_t st);
+// the fold behind a main kernel of `nblocks` blocks: rec[0 .. 8) = the column sums of part [nblocks][8] in a fixed order (launched,
+// or recorded behind the main kernel's record); kernel_obs_heldout.hip's launcher ends in it too
+void launch_fold(const double* part, int nblocks, double* rec, hipStream_t st);
 // rval[e] = R[i][col[e]] for the entries e of every row i (R [I][J])
 void launch_heldout_values(const float* R, int I, int J, const uint32_t* rowptr, const uint32_t* col, float* rval, hipStream_t st);
 
@@ -600,6 +603,21 @@ inline int obs_metric_blocks(size_t n) { const size_t b = (n + 255) / 256; retur
 void launch_obs_sweep(const ObsSweepArgs& a, hipStream_t st);
 void launch_obs_finish(const ObsFinishArgs& a, hipStream_t st);
 void launch_obs_metric(const ObsMetricArgs& a, double* out8, hipStream_t st);   // out8: n, sum R, sum R^2, sum P, sum P^2, sum R P, 0, 0
+
+// Held-out sums of a two-factor handle's own factors, once per iteration (kernel_obs_heldout.hip; bnmtf_set_heldout_entries): the
+// six sums of metrics_from_sums over a row-sorted list of entries, fp64 products of the fp32 rows, fixed summation order
+constexpr int kObsHeldoutRows = kHeldoutRowsPerBlock;   // a wave per row, heldout_blocks(I) blocks
+constexpr int kObsHeldoutStep = 64;                      // entries of a row per wave step: a lane each
+struct ObsHeldoutArgs {
+  const uint32_t* rowptr;            // [I + 1] the held-out entries of row i are [rowptr[i], rowptr[i + 1])
+  const uint32_t* col;               // [n] their columns, ascending within a row
+  const float* rval;                 // [n] their values
+  const float* A; const float* B;    // rows.X [I][stride] and cols.X [J][stride]
+  int I, K, stride;                  // K <= kObsMaxRank; stride = K rounded up to 4
+  double* part;                      // [heldout_blocks(I)][8]
+  double* rec;                       // [8] the iteration's record: n, sum R, sum R^2, sum P, sum P^2, sum R P, 0, 0
+};
+void launch_obs_heldout(const ObsHeldoutArgs& a, hipStream_t st);   // the kernel and launch_fold
 
 // The variational two-factor model on the same lists (kernel_obs_vb.hip): q = (mu, tau, var) beside the expectation X, and
 // S2 = var + X^2 transposed beside XT for the other direction's second gather

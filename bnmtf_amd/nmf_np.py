@@ -153,6 +153,7 @@ class NPDevice(HeldoutMixin):
 
 class NMF(_observed.ObservedNP, NPDevice):
     def __init__(self, R, M, K, *, device=0, verbose=True, rank=0, world=1, comm_id=None, layout='dense'):
+        _observed.refuse_entries(self, R, M)
         self.R = np.array(R, dtype=float)
         self.M = np.array(M, dtype=float)
         self.K = K

@@ -26,6 +26,7 @@ from .nmf_np import MAX_RANK_NP, NPDevice
 
 class NMTF(_observed.ObservedNP, NPDevice):
     def __init__(self, R, M, K, L, *, device=0, verbose=True, rank=0, world=1, comm_id=None, layout='dense'):
+        _observed.refuse_entries(self, R, M)
         self.R = np.array(R, dtype=float)
         self.M = np.array(M, dtype=float)
         self.K = K

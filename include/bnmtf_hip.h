@@ -333,6 +333,16 @@ BNMTF_API int bnmtf_set_heldout(bnmtf_handle h, const double* M_test);
 /* the records of the last run call: sums_out [n_iter][6] = n, sum R, sum R^2, sum P, sum P^2, sum R P per iteration (R as the
  * device holds it, fp32).  BNMTF_ESTATE if that call ran fewer than n_iter iterations or no mask was set. */
 BNMTF_API int bnmtf_get_heldout(bnmtf_handle h, int n_iter, double* sums_out);
+/* run(M_test=Entries) of bnmf_gibbs_optimised(layout='observed'), nmf_icm(layout='observed') and bnmf_vb_observed: the held-out
+ * entries of a two-factor handle of bnmtf_obs_create as lists (rows, cols, values) of n entries in any order -- the handle keeps
+ * no copy of R, so the values arrive with the entries; they may overlap the training entries.  n == 0 or a NULL list clears.
+ * While a list is set, bnmf_obs_run and bnmf_vbo_run record the six sums of every iteration for bnmtf_get_heldout
+ * (csrc/kernel_obs_heldout.hip: fp64 products of the handle's fp32 factor rows -- the variational model's expectations --, fixed
+ * summation order); without one they launch and allocate nothing more.  BNMTF_EINVAL: an entry outside the matrix, an entry that
+ * occurs twice (named by its position in the sorted list), and any other handle -- this is a two-factor call: bnmtf_otri_create's
+ * and bnmtf_onp_create's handles keep no held-out record yet, bnmtf_create's and bnmtf_np_create's take bnmtf_set_heldout, which
+ * keeps refusing the handles of this layout. */
+BNMTF_API int bnmtf_set_heldout_entries(bnmtf_handle h, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values);
 
 /* ---- distributions (stand-alone hooks; code/models/distributions/) ----- */
 /* TN_vector_draw (truncated_normal_vector.py:37-50): out[e] ~ TN(mu[e],tau[e]) on
