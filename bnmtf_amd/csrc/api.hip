@@ -1722,3 +1722,4 @@ int bnmtf_gamma_sample(double alpha, double beta, uint64_t seed, uint64_t it, in
 #include "api_obs_trivb.inc"
 #include "api_obs_np.inc"
 #include "api_many.inc"
+#include "api_predictive.inc"

@@ -1,0 +1,139 @@
+// Posterior predictive statistics of stored samples (C ABI part 10: bnmtf_amd.posterior_predictive, bnmtf_amd/predictive.py) --
+// included behind api_many.inc at the end of api.hip.
+// bnmtf_predictive_samples takes no handle: the entry list, the host's sample arrays and where in them the call's samples lie.  It
+// checks everything and sorts the list by row (a stable counting sort; the permutation scatters the outputs back) before its first
+// device call, makes a stream, three events, the two list arrays, one staging buffer per factor and the three accumulators [n] on
+// the device, and walks the samples in chunks: upload of the chunk (one copy per factor when step = 1, else one per sample), one
+// launch of predictive_kernel (kernel_predictive.hip), which read-modify-writes the accumulators.  Everything is owned by objects
+// of this function: whichever way it leaves, nothing stays.  One stream: the upload of a chunk follows the kernel of the one
+// before (DESIGN.md section 2.8 has the measured split that decided against a second stream).
+
+namespace bnmtf {
+
+constexpr size_t kPredictiveStageBytes = (size_t)256 << 20;      // chunk_samples = 0: as many samples as fit this, at least one
+
+struct PredictiveStream {
+  hipStream_t s = nullptr;
+  ~PredictiveStream() { if (s) (void)hipStreamDestroy(s); }
+};
+struct PredictiveEvent {
+  hipEvent_t e = nullptr;
+  ~PredictiveEvent() { if (e) (void)hipEventDestroy(e); }
+};
+// upload and kernel time of this host thread's last bnmtf_predictive_samples, from the events (bnmtf_predictive_times)
+static thread_local double g_predictive_ms[2] = {0.0, 0.0};
+
+// samples [t0, t0 + c) of the call, array indices first + t * step, `per` floats each, onto dst
+static int predictive_upload(float* dst, const float* src, size_t per, uint64_t first, uint64_t step, int t0, int c, hipStream_t st) {
+  if (step == 1) {
+    HIPCHK(hipMemcpyAsync(dst, src + (first + (uint64_t)t0) * per, (size_t)c * per * sizeof(float), hipMemcpyHostToDevice, st));
+    return BNMTF_OK;
+  }
+  for (int s = 0; s < c; ++s)
+    HIPCHK(hipMemcpyAsync(dst + (size_t)s * per, src + (first + (uint64_t)(t0 + s) * step) * per, per * sizeof(float), hipMemcpyHostToDevice, st));
+  return BNMTF_OK;
+}
+
+}  // namespace bnmtf
+
+extern "C" {
+
+int bnmtf_predictive_samples(int device, int I, int J, int K, int L, uint64_t n, const int32_t* rows, const int32_t* cols,
+                             const float* A, const float* S, const float* B, uint64_t first, uint64_t step, int T, int chunk_samples,
+                             double* p_first, double* sum_d, double* sum_d2) try {
+  if (!rows || !cols || !A || !B || !p_first || !sum_d || !sum_d2) { set_error("bnmtf_predictive_samples: null argument"); return BNMTF_EINVAL; }
+  if (I < 1 || J < 1 || K < 1 || K > kObsMaxRank || L < 0 || L > kObsMaxRank) {
+    set_error("bnmtf_predictive_samples: unsupported shape I=%d J=%d K=%d L=%d (1 <= K <= %d, 0 <= L <= %d)", I, J, K, L, kObsMaxRank, kObsMaxRank);
+    return BNMTF_EINVAL;
+  }
+  if ((L > 0) != (S != nullptr)) { set_error("bnmtf_predictive_samples: S is required when L >= 1 and null when L = 0 (L=%d)", L); return BNMTF_EINVAL; }
+  if (n < 1 || n >= ((uint64_t)1 << 31)) { set_error("bnmtf_predictive_samples: 1 <= n < 2^31 entries (n=%llu)", (unsigned long long)n); return BNMTF_EINVAL; }
+  if (T < 1 || step < 1 || chunk_samples < 0) {
+    set_error("bnmtf_predictive_samples: T >= 1, step >= 1, chunk_samples >= 0 (T=%d step=%llu chunk_samples=%d)", T, (unsigned long long)step, chunk_samples);
+    return BNMTF_EINVAL;
+  }
+  for (uint64_t e = 0; e < n; ++e)
+    if (rows[e] < 0 || rows[e] >= I || cols[e] < 0 || cols[e] >= J) {
+      set_error("bnmtf_predictive_samples: entry %llu (%d, %d) lies outside the %d x %d matrix", (unsigned long long)e, rows[e], cols[e], I, J);
+      return BNMTF_EINVAL;
+    }
+
+  // ---- the list by row, in the given order within a row
+  std::vector<uint32_t> rowptr((size_t)I + 1, 0u), col(n), perm(n);
+  for (uint64_t e = 0; e < n; ++e) rowptr[(size_t)rows[e] + 1]++;
+  for (int i = 0; i < I; ++i) rowptr[(size_t)i + 1] += rowptr[i];
+  {
+    std::vector<uint32_t> at(rowptr.begin(), rowptr.end() - 1);
+    for (uint64_t e = 0; e < n; ++e) { const uint32_t q = at[rows[e]]++; col[q] = (uint32_t)cols[e]; perm[q] = (uint32_t)e; }
+  }
+
+  const int W = L > 0 ? L : K;
+  const size_t perA = (size_t)I * K, perS = (size_t)K * L, perB = (size_t)J * W;
+  int chunk = chunk_samples;
+  if (chunk == 0) {
+    const size_t fit = kPredictiveStageBytes / ((perA + perS + perB) * sizeof(float));
+    chunk = fit < 1 ? 1 : fit > (size_t)T ? T : (int)fit;
+  }
+  if (chunk > T) chunk = T;
+
+  // ---- the device's side: all of it owned here
+  HIPCHK(hipSetDevice(device));
+  PredictiveStream st;
+  PredictiveEvent ev[3];
+  DevBuf<uint32_t> d_rowptr, d_col;
+  DevBuf<float> dA, dS, dB;
+  DevBuf<double> d_first, d_sum, d_sum2;
+  HIPCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+  for (auto& e : ev) HIPCHK(hipEventCreate(&e.e));
+  CHK(d_rowptr.alloc(rowptr.size())); CHK(d_col.alloc(n));
+  CHK(dA.alloc((size_t)chunk * perA)); CHK(dB.alloc((size_t)chunk * perB));
+  if (L > 0) CHK(dS.alloc((size_t)chunk * perS));
+  CHK(d_first.alloc(n, true)); CHK(d_sum.alloc(n, true)); CHK(d_sum2.alloc(n, true));
+  HIPCHK(hipMemcpyAsync(d_rowptr.p, rowptr.data(), rowptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st.s));
+  HIPCHK(hipMemcpyAsync(d_col.p, col.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st.s));
+
+  PredictiveArgs a; memset(&a, 0, sizeof(a));
+  a.rowptr = d_rowptr.p; a.col = d_col.p;
+  a.A = dA.p; a.S = L > 0 ? dS.p : nullptr; a.B = dB.p;
+  a.I = I; a.J = J; a.K = K; a.L = L;
+  a.p_first = d_first.p; a.sum_d = d_sum.p; a.sum_d2 = d_sum2.p;
+  double upload_ms = 0.0, kernel_ms = 0.0;
+  for (int t0 = 0; t0 < T; t0 += chunk) {
+    const int c = T - t0 < chunk ? T - t0 : chunk;
+    HIPCHK(hipEventRecord(ev[0].e, st.s));
+    CHK(predictive_upload(dA.p, A, perA, first, step, t0, c, st.s));
+    if (L > 0) CHK(predictive_upload(dS.p, S, perS, first, step, t0, c, st.s));
+    CHK(predictive_upload(dB.p, B, perB, first, step, t0, c, st.s));
+    HIPCHK(hipEventRecord(ev[1].e, st.s));
+    a.C = c; a.first = t0 == 0 ? 1 : 0;
+    launch_predictive(a, st.s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[2].e, st.s));
+    HIPCHK(hipEventSynchronize(ev[2].e));          // (the staging buffers are the next chunk's; the stream orders that by itself)
+    float up = 0.f, kn = 0.f;
+    HIPCHK(hipEventElapsedTime(&up, ev[0].e, ev[1].e));
+    HIPCHK(hipEventElapsedTime(&kn, ev[1].e, ev[2].e));
+    upload_ms += up; kernel_ms += kn;
+  }
+  HIPCHK(hipStreamSynchronize(st.s));
+  HIPCHK(hipGetLastError());
+
+  // ---- back, from list order to the given order
+  std::vector<double> sorted(n);
+  double* const outs[3] = {p_first, sum_d, sum_d2};
+  const double* const devs[3] = {d_first.p, d_sum.p, d_sum2.p};
+  for (int m = 0; m < 3; ++m) {
+    HIPCHK(hipMemcpy(sorted.data(), devs[m], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    for (uint64_t q = 0; q < n; ++q) outs[m][perm[q]] = sorted[q];
+  }
+  g_predictive_ms[0] = upload_ms; g_predictive_ms[1] = kernel_ms;
+  return BNMTF_OK;
+} BNMTF_ABI_GUARD
+
+int bnmtf_predictive_times(double* upload_ms, double* kernel_ms) try {
+  if (!upload_ms || !kernel_ms) { set_error("bnmtf_predictive_times: null argument"); return BNMTF_EINVAL; }
+  *upload_ms = g_predictive_ms[0]; *kernel_ms = g_predictive_ms[1];
+  return BNMTF_OK;
+} BNMTF_ABI_GUARD
+
+}  // extern "C"

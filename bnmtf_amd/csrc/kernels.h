@@ -619,6 +619,23 @@ struct ObsHeldoutArgs {
 };
 void launch_obs_heldout(const ObsHeldoutArgs& a, hipStream_t st);   // the kernel and launch_fold
 
+// Posterior predictive statistics of stored samples over a row-sorted entry list (kernel_predictive.hip; bnmtf_predictive_samples):
+// one launch per chunk of samples, the per-entry accumulators read-modify-written in sample order
+constexpr int kPredictiveRows = kHeldoutRowsPerBlock;   // a wave per row, heldout_blocks(I) blocks
+constexpr int kPredictiveStep = 64;                      // entries of a row per wave step: a lane each
+struct PredictiveArgs {
+  const uint32_t* rowptr;            // [I + 1] the entries of row i are [rowptr[i], rowptr[i + 1])
+  const uint32_t* col;               // [n] their columns
+  const float* A;                    // [C][I][K] the chunk's samples of U, or F; unpadded
+  const float* S;                    // [C][K][L], or null (L = 0)
+  const float* B;                    // [C][J][K] V, or [C][J][L] G
+  int I, J, K, L;                    // K, L <= kObsMaxRank
+  int C;                             // samples in the chunk
+  int first;                         // the chunk begins with the call's first sample: it sets p_first
+  double* p_first; double* sum_d; double* sum_d2;   // [n] in list order; the sums zero before the first chunk
+};
+void launch_predictive(const PredictiveArgs& a, hipStream_t st);
+
 // The variational two-factor model on the same lists (kernel_obs_vb.hip): q = (mu, tau, var) beside the expectation X, and
 // S2 = var + X^2 transposed beside XT for the other direction's second gather
 struct ObsVbSweepArgs {

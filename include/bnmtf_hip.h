@@ -586,6 +586,25 @@ BNMTF_API int bnmtf_onp_update(bnmtf_handle h, int which, int k, int l);
  * any order (n = 0: the training entries); P in fp64 from the fp32 factors, NMTF: (F_i S) . G_j with F_i S in fp64 */
 BNMTF_API int bnmtf_onp_metrics(bnmtf_handle h, uint64_t n, const int32_t* rows, const int32_t* cols, const float* values, double* out8);
 
+/* ---- posterior predictive statistics of stored samples over an entry list (bnmtf_amd.posterior_predictive; DESIGN.md section
+ * 2.8) -------------------------------------------------------------------------------------------------------------------------
+ * No handle: the call makes its own stream and buffers on `device` and frees all of them on every path.  Per entry e = (rows[e],
+ * cols[e]) -- any order, an entry may occur more than once, 1 <= n < 2^31 -- and per sample s = 0 .. T - 1 (array index
+ * first + s step, step >= 1, T >= 1) the prediction p_s: L = 0, S null: A [.][I][K] . B [.][J][K]; L >= 1: (A [.][I][K] S [.][K][L]) .
+ * B [.][J][L]; 1 <= K <= 256, 0 <= L <= 256.  Host arrays, fp32, contiguous, row stride exactly K (or L).  Outputs [n] in the given
+ * order: p_first = p_0, sum_d = sum_s (p_s - p_0), sum_d2 = sum_s (p_s - p_0)^2; the caller finishes mean = p_first + sum_d / T and
+ * variance = max(0, sum_d2 / T - (sum_d / T)^2).  Every fp32 value is widened to fp64, p_s is the fma chain over the inner index
+ * ascending ((A S)_l first, over k ascending), the samples are added in ascending s: an entry's three numbers depend on that entry
+ * and the samples alone -- not on chunk_samples (samples uploaded per kernel launch; 0: as many as fit the library's staging size,
+ * at least one), not on the list's order or on what else is in it.  Everything is checked before the first device call. */
+BNMTF_API int bnmtf_predictive_samples(int device, int I, int J, int K, int L, uint64_t n,
+    const int32_t* rows, const int32_t* cols, const float* A, const float* S, const float* B,
+    uint64_t first, uint64_t step, int T, int chunk_samples,
+    double* p_first, double* sum_d, double* sum_d2);
+/* upload and kernel time (ms, from events on the call's stream, summed over its chunks) of the calling host thread's last
+ * bnmtf_predictive_samples that returned BNMTF_OK; zeros before one did (tools/predictive_rates.py) */
+BNMTF_API int bnmtf_predictive_times(double* upload_ms, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
