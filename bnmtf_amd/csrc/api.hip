@@ -1722,4 +1722,5 @@ int bnmtf_gamma_sample(double alpha, double beta, uint64_t seed, uint64_t it, in
 #include "api_obs_trivb.inc"
 #include "api_obs_np.inc"
 #include "api_many.inc"
+#include "api_top.inc"
 #include "api_predictive.inc"

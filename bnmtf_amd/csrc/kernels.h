@@ -636,6 +636,28 @@ struct PredictiveArgs {
 };
 void launch_predictive(const PredictiveArgs& a, hipStream_t st);
 
+// The n best columns of every selected row under a total order (kernel_top.hip; bnmtf_top_entries): a wave
+// per (row, column segment) pair, its sorted list in LDS, and a merge of a row's segment lists
+constexpr int kTopRows = kHeldoutRowsPerBlock;           // waves per block: a (row, segment) pair each
+constexpr int kTopStep = 64;                             // columns per wave step: a lane each
+constexpr int kTopMaxN = 128;                            // n (BNMTF_TOP_MAX_N): two list slots per lane
+constexpr int kTopMaxSplit = 1024;                       // column segments per row
+struct TopArgs {
+  const double* A;                   // [r][K] the selected rows of the rows factor (U, or F), unpadded
+  const double* S;                   // [K][L], or null (L = 0)
+  double* FS;                        // [r][L] (F S) of the selected rows (top_fs_kernel writes it), or null
+  const double* B;                   // [J][stride] the columns factor (V, or G)
+  int r, J, K, L;                    // K, L <= kObsMaxRank
+  int stride;                        // W = L ? L : K rounded up to 2 doubles: a row of B begins on a 16-byte boundary
+  const uint32_t* exptr;             // [r + 1] the excluded columns of selected row q are [exptr[q], exptr[q + 1])
+  const uint32_t* excol;             // ascending and distinct within a row
+  int n, largest;                    // 1 <= n <= kTopMaxN; the order: higher score first (largest), or lower first
+  int split, seg_steps;              // segments per row and whole kTopStep-column steps per segment
+  double* part_key; int32_t* part_col; int32_t* part_cnt;   // [r][split][n], [r][split]: the segments' lists, best first; key = +-score
+  int32_t* cols; double* scores; int32_t* counts;           // [r][n], [r]: the answer; -1 / nan behind counts[q] slots
+};
+void launch_top(const TopArgs& a, hipStream_t st);        // top_fs_kernel (L > 0), top_kernel, top_merge_kernel
+
 // The variational two-factor model on the same lists (kernel_obs_vb.hip): q = (mu, tau, var) beside the expectation X, and
 // S2 = var + X^2 transposed beside XT for the other direction's second gather
 struct ObsVbSweepArgs {

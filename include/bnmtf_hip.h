@@ -605,6 +605,29 @@ BNMTF_API int bnmtf_predictive_samples(int device, int I, int J, int K, int L, u
  * bnmtf_predictive_samples that returned BNMTF_OK; zeros before one did (tools/predictive_rates.py) */
 BNMTF_API int bnmtf_predictive_times(double* upload_ms, double* kernel_ms);
 
+/* ---- the n best predicted entries per row, selected on the device (bnmtf_amd.top_entries) --------------
+ * No handle: the call makes its own stream and buffers on `device` and frees all of them on every path.  Score of (i, j): L = 0,
+ * S null: A [I][K] . B [J][K]; L >= 1: (A [I][K] S [K][L]) . B [J][L]; 1 <= I, J <= 2^30, 1 <= K <= 256, 0 <= L <= 256, every
+ * value finite.  A score is the fp64 fma chain over the inner index ascending from 0.0 ((A S)_l first, over k ascending): its bits
+ * depend on the pair's factor rows alone.  rows: n_rows distinct rows of the matrix, any order; null: all I rows (n_rows is then
+ * not read).  ex_rows, ex_cols: n_excl < 2^32 entries inside the matrix that are no candidates, any order, repeats allowed; those of
+ * rows not asked for are dropped.  Per row asked for, in the order given, the BNMTF_TOP_MAX_N >= n >= 1 best candidates under the
+ * total order "higher score first (largest = 1; lower first with largest = 0), equal scores: lower column first, -0.0 equal to
+ * 0.0": cols_out [.][n] best first and -1 where the row has fewer than n candidates, scores_out [.][n] with nan there, counts_out
+ * [.] the valid slots.  split: column segments per row, each taken by a wave of its own and merged under the same order (0: the
+ * library chooses; at most 1024); the answer is unique, so its bytes depend on neither split nor the launch.  Everything is
+ * checked, the exclusion list sorted by row and the rows asked for gathered before the first device call. */
+#define BNMTF_TOP_MAX_N 128
+BNMTF_API int bnmtf_top_entries(int device, int I, int J, int K, int L,
+    const double* A, const double* S, const double* B,
+    uint64_t n_rows, const int32_t* rows,
+    uint64_t n_excl, const int32_t* ex_rows, const int32_t* ex_cols,
+    int n, int largest, int split,
+    int32_t* cols_out, double* scores_out, int32_t* counts_out);
+/* upload and kernel time (ms, from events on the call's stream) of the calling host thread's last bnmtf_top_entries that returned
+ * BNMTF_OK; zeros before one did (tools/top_entries_rates.py) */
+BNMTF_API int bnmtf_top_entries_times(double* upload_ms, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
