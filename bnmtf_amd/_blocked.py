@@ -160,10 +160,10 @@ class VBColumnBlocks(ColumnBlocks):
     single-block updates on the residual data R - sum_{b' != b} E[U_b'] E[V_b']^T (the other blocks' part of
     M . (R - E[U] E[V]^T + ...), :189-195, moves to the data side; tauU of a column involves that column alone);
     exp_square_diff (:185-187) = the full-width masked SSE + the blocks' second-moment sums (a sum over columns)."""
-    NAMES = ("muU", "tauU", "expU", "varU", "muV", "tauV", "expV", "varV")
 
     def __init__(self, owner, child_cls):
         ColumnBlocks.__init__(self, owner, child_cls, seeded=False)
+        self.NAMES = owner._NAMES           # the q parameters, in the order of the state calls
 
     def _prepare(self):
         if self._ready:
@@ -184,7 +184,7 @@ class VBColumnBlocks(ColumnBlocks):
 
     def pull(self):
         o = self.owner
-        out = {n: np.zeros((o.I if n.endswith("U") else o.J, o.K)) for n in self.NAMES}
+        out = {n: np.zeros(s) for n, s in zip(self.NAMES, o._shapes())}
         for ch, (c0, c1) in zip(self.children, self.ranges):
             ch._pull()
             for n in self.NAMES:

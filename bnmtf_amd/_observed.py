@@ -110,30 +110,17 @@ class ObservedLayout(object):
 
 
 class ObservedVB(ObservedLayout):
-    """... and of the two variational classes: the q parameters' hand-off, written over the class's _NAMES, _shapes() and the
-    names of its two state calls (_SET_STATE, _GET_STATE), and the hooks of the dense layout's masked product."""
-    _SET_STATE = _GET_STATE = None      # the subclass names them; _shapes() is the dense class's or the subclass's own
+    """... and of the two variational classes, ahead of the dense class (a _variational.Variational) in their MRO: the layout's
+    handle and list metric, as the class's _OBSERVED table names them, and the hooks of the dense layout's masked product.
+    Everything else -- the q hand-over too -- is the dense class's code on the _OBSERVED entry points."""
 
-    def _push(self):
-        # the state the device holds already (nothing touched the q parameters or exptau since the last device call pulled
-        # them): no upload -- run(a); run(b) is the trajectory of run(a + b)
-        exptau = float(getattr(self, "exptau", 1.0))
-        held = getattr(self, "_device_state", None)
-        if held is not None and held[0] is self._h and held[1] == exptau and all(np.array_equal(getattr(self, n), a) for n, a in zip(self._NAMES, held[2])):
-            return
-        self._device_state = None
-        arrs = [_lib.f64(getattr(self, n)) for n in self._NAMES]
-        _lib.check(getattr(_lib.lib(), self._SET_STATE)(self._handle(), *[_lib.ptr(a) for a in arrs], exptau))
-        self._device_state = (self._h, exptau, [np.array(a, dtype=float) for a in arrs])
+    def _handle(self):
+        if self._h is None:
+            self._h = self._OBSERVED["create"](self)
+        return self._h
 
-    def _pull(self):
-        arrs = [np.zeros(s) for s in self._shapes()]
-        _lib.check(getattr(_lib.lib(), self._GET_STATE)(self._handle(), *[_lib.ptr(a) for a in arrs]))
-        held = getattr(self, "_device_state", None)
-        for n, a in zip(self._NAMES, arrs):
-            setattr(self, n, a)
-        # (exptau: the hooks leave the device's as it was pushed; run() fills in the one formed from the device's beta_s)
-        self._device_state = (self._h, None if held is None else held[1], [a.copy() for a in arrs])
+    def _metric_sums(self, M_pred, A, S, B):
+        return self._OBSERVED["metric_sums"](self, M_pred, *self._own(A, S, B))
 
     def masked_sums(self, which):
         refuse(self, "masked_sums")

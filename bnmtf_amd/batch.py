@@ -137,9 +137,10 @@ def run_many(models, iterations, update='draw', store_samples=True, expectation=
 # The lock-step families: kind -> (what puts a model's state on the device, the C entry point, the trailing shapes of its
 # model-major [models][iterations] output arrays, in the order the entry point and the models' _run_finish take them; the batch's
 # clock follows them).  bnmf_vb_optimised.py:121-153, bnmtf_vb_optimised.py:160-205, nmf_np.py:87-107, nmtf_np.py:116-144.
-_LOCKSTEP = {
-    "vb": (lambda m, it: m._push(), "bnmf_vb_run_many", ((), (3,), (10,))),            # exptau, perf, the ELBO's terms
-    "trivb": (lambda m, it: m._push(), "bnmtf_vb_run_many", ((), (3,), (10,))),
+_VARIATIONAL = (lambda m, it: m._push(), None, ((), (3,), (10,)))                      # exptau, perf, the ELBO's terms; the entry point:
+_LOCKSTEP = {                                                                          # the run_many of the models' _DENSE table
+    "vb": _VARIATIONAL,
+    "trivb": _VARIATIONAL,
     "np": (lambda m, it: m._run_prepare(it), "bnmtf_np_run_many", ((3,), ())),         # perf, the I-divergence
 }
 
@@ -171,7 +172,7 @@ def _run_lockstep(kind, ms, it, orders=None, masks=None):
         outs = [np.zeros((n, it) + shape) for shape in shapes] + [np.zeros((n, it))]
         info = np.zeros(2, dtype=np.int32)
         t0 = time.perf_counter()
-        _lib.check(getattr(_lib.lib(), entry)(*args, *[_lib.ptr(o) for o in outs], _lib.ptr(info)))
+        _lib.check(getattr(_lib.lib(), entry or group[0]._DENSE["run_many"])(*args, *[_lib.ptr(o) for o in outs], _lib.ptr(info)))
         dt = time.perf_counter() - t0
         for j, m in enumerate(group):
             if masks is not None:

@@ -12,13 +12,19 @@ import numpy as np
 import scipy.special
 
 from . import _lib
-from ._base import (DeviceModel, broadcast_lambda, check_binary, check_rank, check_R_M, information_criterion, metrics_from_sums,
-                    performances)
-from .distributions import TN_vector_expectation, TN_vector_variance, gamma_expectation, gamma_expectation_log
+from ._base import check_binary, check_rank, check_R_M, metrics_from_sums
 from ._blocked import BLOCK, MAX_BLOCKS, VBColumnBlocks
+from ._variational import Variational, q_names
+from .distributions import gamma_expectation, gamma_expectation_log
 
 
-class bnmf_vb_optimised(DeviceModel):
+class bnmf_vb_optimised(Variational):
+    _FACTORS = ("U", "V")
+    _NAMES = q_names(_FACTORS)
+    _DENSE = {"set_state": "bnmf_vb_set_state", "get_state": "bnmf_vb_get_state", "run": "bnmf_vb_run", "update": "bnmf_vb_update",
+              "exp_square_diff": "bnmf_vb_exp_square_diff", "run_many": "bnmf_vb_run_many", "set_tau": "bnmtf_set_tau"}
+    _ONES_IN_ESD = tuple(n for n in _NAMES if n[:-1] in ("mu", "tau"))      # the test-suite sets exp / var only
+
     def __init__(self, R, M, K, priors, *, device=0, verbose=True, rank=0, world=1, comm_id=None):
         self.R = np.array(R, dtype=float)
         self.M = np.array(M, dtype=float)
@@ -27,19 +33,15 @@ class bnmf_vb_optimised(DeviceModel):
         check_rank("bnmf_vb_optimised", BLOCK * MAX_BLOCKS, K=self.K)
         (self.I, self.J) = self.R.shape
         self.size_Omega = self.M.sum()
-        self.alpha, self.beta = float(priors['alpha']), float(priors['beta'])
-        self.lambdaU = broadcast_lambda(priors['lambdaU'], (self.I, self.K), "lambdaU")
-        self.lambdaV = broadcast_lambda(priors['lambdaV'], (self.J, self.K), "lambdaV")
-        self.verbose = verbose
-        self._init_device(0, device, rank, world, comm_id)      # VB draws nothing: the key is unused, 0 on every rank
+        self._init_priors(priors, device, verbose, rank, world, comm_id)
         # ranks above 64 (the reference has no limit, :53-77): column blocks of at most 64, one device model each (_blocked.py)
         self._blocks = None
         if self.K > BLOCK:
             assert world == 1, "ranks above %d run on one GPU (column blocks: DESIGN.md section 8)" % BLOCK
             self._blocks = VBColumnBlocks(self, bnmf_vb_optimised)
 
-    def _lambda_arrays(self):
-        return self.lambdaU, self.lambdaV, None
+    def _factor_shapes(self):
+        return [(self.I, self.K), (self.J, self.K)]
 
     def close(self):
         if getattr(self, "_blocks", None) is not None:
@@ -64,47 +66,6 @@ class bnmf_vb_optimised(DeviceModel):
             return "column blocks %s: " % (self._blocks.ranges,) + " | ".join(ch.describe() for ch in self._blocks.children)
         return super(bnmf_vb_optimised, self).describe()
 
-    # -- state hand-off -------------------------------------------------------
-    _NAMES = ("muU", "tauU", "expU", "varU", "muV", "tauV", "expV", "varV")
-
-    def _push(self):
-        exptau = float(getattr(self, "exptau", 1.0))
-        if self._blocks is not None:
-            held = getattr(self, "_device_state", None)
-            if held is not None and held[1] == exptau and all(np.array_equal(getattr(self, n), a) for n, a in zip(self._NAMES, held[2])):
-                return
-            self._blocks.push(exptau)
-            self._device_state = (None, exptau, [np.array(getattr(self, n), dtype=float) for n in self._NAMES])
-            return
-        # the state the device holds already (nothing touched the q parameters since the last run() pulled them): no upload,
-        # and the device keeps what it carries between its half sweeps -- run(a); run(b) is the trajectory of run(a + b)
-        held = getattr(self, "_device_state", None)
-        if held is not None and held[0] is self._h and held[1] == exptau and all(np.array_equal(getattr(self, n), a) for n, a in zip(self._NAMES, held[2])):
-            return
-        if held is not None and held[0] is self._h and all(np.array_equal(getattr(self, n), a) for n, a in zip(self._NAMES, held[2])):
-            # only exptau moved (update_tau / update_exp_tau between two device calls): the q parameters on the device stay
-            _lib.check(_lib.lib().bnmtf_set_tau(self._handle(), exptau))
-            self._device_state = (held[0], exptau, held[2])
-            return
-        self._device_state = None
-        arrs = [_lib.f64(getattr(self, n)) for n in self._NAMES]
-        _lib.check(_lib.lib().bnmf_vb_set_state(self._handle(), *[_lib.ptr(a) for a in arrs], exptau))
-        self._device_state = (self._h, exptau, [np.array(a, dtype=float) for a in arrs])      # (what the device holds now -- in fp32; a push of the same arrays would give it the same)
-
-    def _pull(self):
-        if self._blocks is not None:
-            got = self._blocks.pull()
-            for n in self._NAMES:
-                setattr(self, n, got[n])
-            self._device_state = (None, float(getattr(self, "exptau", 1.0)), [got[n].copy() for n in self._NAMES])
-            return
-        shapes = [(self.I, self.K)] * 4 + [(self.J, self.K)] * 4
-        arrs = [np.zeros(s) for s in shapes]
-        _lib.check(_lib.lib().bnmf_vb_get_state(self._handle(), *[_lib.ptr(a) for a in arrs]))
-        for n, a in zip(self._NAMES, arrs):
-            setattr(self, n, a)
-        self._device_state = (self._h, None, [a.copy() for a in arrs])       # (exptau: filled in by run() once it has been formed from the device's beta_s)
-
     def initialise(self, init='exp', tauUV={}):
         """bnmf_vb_optimised.py:93-117."""
         self.tauU = np.array(tauUV['tauU'], dtype=float) if 'tauU' in tauUV else np.ones((self.I, self.K))
@@ -114,14 +75,7 @@ class bnmf_vb_optimised(DeviceModel):
         if init == 'random':
             self.muU = self._rng().exponential(scale=1.0 / self.lambdaU)
             self.muV = self._rng().exponential(scale=1.0 / self.lambdaV)
-        # (update_exp_U(k) / update_exp_V(k) of every column, :111-115: the moments are element-wise -- one device call per factor
-        # instead of two per column; a model search builds dozens of models and their set-up was most of its wall time)
-        from .distributions import _moments
-        muU, muV = np.broadcast_to(self.muU, (self.I, self.K)), np.broadcast_to(self.muV, (self.J, self.K))
-        e, v = _moments(np.ravel(muU), np.ravel(self.tauU))
-        self.expU, self.varU = e.reshape(self.I, self.K), v.reshape(self.I, self.K)
-        e, v = _moments(np.ravel(muV), np.ravel(self.tauV))
-        self.expV, self.varV = e.reshape(self.J, self.K), v.reshape(self.J, self.K)
+        self._initial_moments()            # (update_exp_U(k) / update_exp_V(k) of every column, :111-115)
         self.update_tau()
         self.update_exp_tau()
 
@@ -132,35 +86,18 @@ class bnmf_vb_optimised(DeviceModel):
         it = int(iterations)
         if self._blocks is not None:
             return self._run_blocked(it)
-        self._push()
-        self._set_heldout(Mt)
-        exptau = np.zeros(it); perf = np.zeros((it, 3)); terms = np.zeros((it, 10)); times = np.zeros(it)
-        self._run_device(it, exptau, perf, terms, times)
-        self._finish_heldout(it)
-        self._run_finish(it, exptau, perf, terms, times)
+        self._run(it, Mt)
 
     def _run_device(self, it, exptau, perf, terms, times):
-        """The device call of run() (bnmf_vb_observed: the observed-entry layout's)."""
-        _lib.check(_lib.lib().bnmf_vb_run(self._handle(), it, _lib.ptr(exptau), _lib.ptr(perf), _lib.ptr(terms), _lib.ptr(times)))
+        """The device call of run(), either layout's."""
+        _lib.check(self._entry("run")(self._handle(), it, _lib.ptr(exptau), _lib.ptr(perf), _lib.ptr(terms), _lib.ptr(times)))
 
-    def _run_finish(self, it, exptau, perf, terms, times):
-        """What run() does behind the device call (batch.run_many: behind the call that ran this model among others)."""
-        self._pull()
-        self.all_exp_tau = list(exptau)
-        self.all_times = list(times)
-        self.all_performances = performances(perf)
-        self.all_elbo_terms = terms        # per iteration: exp_square_diff, beta_s, then (quad, log erfc, log tau, lambda E) sums of U and of V
+    def _take_elbo_terms(self, terms):
+        self.all_elbo_terms = terms
         self._all_elbo = None              # (all_elbo: finished from the terms when somebody reads it -- a model search reads the last state only)
-        if it > 0:
-            self.alpha_s = self.alpha + self.size_Omega / 2.0
-            self.beta_s = terms[-1, 1]
-            self.update_exp_tau()
-            if getattr(self, "_device_state", None) is not None:      # alpha_s / beta_s from the device's own beta_s: the exptau it holds
-                self._device_state = (self._device_state[0], float(self.exptau), self._device_state[2])
-        if self.verbose:
-            for i in range(it):
-                print("Iteration %s. ELBO: %s. MSE: %s. R^2: %s. Rp: %s." % (i + 1, self.all_elbo[i], perf[i, 0], perf[i, 1], perf[i, 2]))
-        return
+
+    def _iteration_line(self, i, perf):
+        return "Iteration %s. ELBO: %s. MSE: %s. R^2: %s. Rp: %s." % (i + 1, self.all_elbo[i], perf[i, 0], perf[i, 1], perf[i, 2])
 
     def _run_blocked(self, it):
         """run() of a model wider than 64 columns (_blocked.py): per iteration the blocks' half sweeps in turn (:134-141), then
@@ -239,12 +176,7 @@ class bnmf_vb_optimised(DeviceModel):
                                       sums(self.muU, self.tauU, self.expU, self.varU, self.lambdaU),
                                       sums(self.muV, self.tauV, self.expV, self.varV, self.lambdaV))
 
-    # -- updates ----------------------------------------------------------------
-    def update_tau(self):
-        """:181-183."""
-        self.alpha_s = self.alpha + self.size_Omega / 2.0
-        self.beta_s = self.beta + 0.5 * self.exp_square_diff()
-
+    # -- hooks and updates -------------------------------------------------------
     def masked_sums(self, which):
         """Hook (tests): sum over the MISSING entries of a unit of the other factor's S2 = var + exp^2 and of its exp^2, per column --
         the chain-independent parts of tauU / muU (which = 0) or tauV / muV (which = 1), from the matrix-core product run() uses."""
@@ -269,27 +201,6 @@ class bnmf_vb_optimised(DeviceModel):
         assert not posted.reshape(2, KP)[:, self.K:].any() and not own.reshape(2, KP)[:, self.K:].any(), "a padding column has a maximum"
         return posted.reshape(2, KP)[:, :self.K].copy(), own.reshape(2, KP)[:, :self.K].copy(), bool(flag.value)
 
-    def exp_square_diff(self):
-        """:185-187 (fp64 on the device)."""
-        for n in ("muU", "tauU", "muV", "tauV"):          # the test-suite sets exp/var only
-            if not hasattr(self, n):
-                setattr(self, n, np.ones((self.I if n.endswith("U") else self.J, self.K)))
-        self._push()
-        if self._blocks is not None:
-            return self._blocks.esd(self.expU, self.expV)[0]
-        out = C.c_double()
-        _lib.check(_lib.lib().bnmf_vb_exp_square_diff(self._handle(), C.byref(out)))
-        return out.value
-
-    def _update(self, which, k, moments):
-        self._push()
-        if self._blocks is not None:
-            self._blocks.update(which, k, moments)
-            self._pull()
-            return
-        _lib.check(_lib.lib().bnmf_vb_update(self._handle(), which, int(k), int(moments)))
-        self._pull()
-
     def update_U(self, k):
         """:189-191."""
         self._update(0, k, 0)
@@ -300,35 +211,11 @@ class bnmf_vb_optimised(DeviceModel):
 
     def update_exp_U(self, k):
         """:199-204."""
-        self.expU[:, k] = TN_vector_expectation(self.muU[:, k], self.tauU[:, k])
-        self.varU[:, k] = TN_vector_variance(self.muU[:, k], self.tauU[:, k])
+        self._update_exp("U", np.s_[:, k])
 
     def update_exp_V(self, k):
         """:206-211."""
-        self.expV[:, k] = TN_vector_expectation(self.muV[:, k], self.tauV[:, k])
-        self.varV[:, k] = TN_vector_variance(self.muV[:, k], self.tauV[:, k])
-
-    def update_exp_tau(self):
-        """:213-215."""
-        self.exptau = gamma_expectation(self.alpha_s, self.beta_s)
-        self.explogtau = gamma_expectation_log(self.alpha_s, self.beta_s)
-
-    # -- prediction / model quality ----------------------------------------------
-    def predict(self, M_pred):
-        """:219-224."""
-        return metrics_from_sums(self._metric_sums(M_pred, self.expU, None, self.expV))
-
-    def quality(self, metric):
-        """:247-262."""
-        return information_criterion(metric, tuple, self.log_likelihood,
-                                     lambda: metrics_from_sums(self._metric_sums(None, self.expU, None, self.expV))['MSE'],
-                                     self.I * self.K + self.J * self.K, self.size_Omega, self.elbo)
-
-    def log_likelihood(self):
-        """:264-266."""
-        s = self._metric_sums(None, self.expU, None, self.expV)
-        sse = s[2] - 2.0 * s[5] + s[4]
-        return self.size_Omega / 2. * (self.explogtau - math.log(2 * math.pi)) - self.exptau / 2. * sse
+        self._update_exp("V", np.s_[:, k])
 
 
 bnmf_vb = bnmf_vb_optimised

@@ -9,7 +9,6 @@ Per iteration (bnmtf_vb_optimised.py:170-192): the K.L entries of S, the K colum
 each updated in a freshly shuffled order.  The orders are drawn HERE with `random.shuffle` -- the same three calls on
 the same lists as the reference, so `random.seed(s)` reproduces its trajectory -- and handed to the device, which
 runs all iterations in one call.  K, L <= 32."""
-import ctypes as C
 import itertools
 import math
 import random
@@ -18,12 +17,20 @@ import numpy as np
 import scipy.special
 
 from . import _lib
-from ._base import DeviceModel, broadcast_lambda, check_rank, check_R_M, information_criterion, metrics_from_sums, performances
-from .distributions import TN_vector_expectation, TN_vector_variance, gamma_expectation, gamma_expectation_log
+from ._base import check_rank, check_R_M
+from ._variational import Variational, q_names
 from .kmeans import KMeans
 
 
-class bnmtf_vb_optimised(DeviceModel):
+class bnmtf_vb_optimised(Variational):
+    _FACTORS = ("F", "S", "G")
+    _NAMES = q_names(_FACTORS)
+    # (esd_rest: bnmtf_vb_exp_square_diff also offers the six sums of the training mask -- nobody takes them)
+    _DENSE = {"set_state": "bnmtf_vb_set_state", "get_state": "bnmtf_vb_get_state", "run": "bnmtf_vb_run", "update": "bnmtf_vb_update",
+              "exp_square_diff": "bnmtf_vb_exp_square_diff", "esd_rest": (None,), "run_many": "bnmtf_vb_run_many"}
+    _KEEPS_DEVICE_STATE = False         # (with the record the device would keep derived state across calls: not compared yet)
+    _ONES_IN_PUSH = _NAMES              # the reference's tests set only some of the attributes
+
     def __init__(self, R, M, K, L, priors, *, device=0, verbose=True, rank=0, world=1, comm_id=None):
         self.R = np.array(R, dtype=float)
         self.M = np.array(M, dtype=float)
@@ -32,35 +39,10 @@ class bnmtf_vb_optimised(DeviceModel):
         check_rank("bnmtf_vb_optimised", 32, K=self.K, L=self.L)
         (self.I, self.J) = self.R.shape
         self.size_Omega = self.M.sum()
-        self.alpha, self.beta = float(priors['alpha']), float(priors['beta'])
-        self.lambdaF = broadcast_lambda(priors['lambdaF'], (self.I, self.K), "lambdaF")
-        self.lambdaS = broadcast_lambda(priors['lambdaS'], (self.K, self.L), "lambdaS")
-        self.lambdaG = broadcast_lambda(priors['lambdaG'], (self.J, self.L), "lambdaG")
-        self.verbose = verbose
-        # (VB draws nothing on the device; rank / world / comm_id: rows of F and columns of G over several GPUs, round 6)
-        self._init_device(0, device, rank, world, comm_id)
+        self._init_priors(priors, device, verbose, rank, world, comm_id)
 
-    def _lambda_arrays(self):
-        return self.lambdaF, self.lambdaG, self.lambdaS
-
-    # -- state hand-off -------------------------------------------------------
-    _NAMES = ("muF", "tauF", "expF", "varF", "muS", "tauS", "expS", "varS", "muG", "tauG", "expG", "varG")
-
-    def _shapes(self):
-        return [(self.I, self.K)] * 4 + [(self.K, self.L)] * 4 + [(self.J, self.L)] * 4
-
-    def _push(self):
-        for n, s in zip(self._NAMES, self._shapes()):      # the reference's tests set only some of the attributes
-            if not hasattr(self, n):
-                setattr(self, n, np.ones(s))
-        arrs = [_lib.f64(getattr(self, n)) for n in self._NAMES]
-        _lib.check(_lib.lib().bnmtf_vb_set_state(self._handle(), *[_lib.ptr(a) for a in arrs], float(getattr(self, "exptau", 1.0))))
-
-    def _pull(self):
-        arrs = [np.zeros(s) for s in self._shapes()]
-        _lib.check(_lib.lib().bnmtf_vb_get_state(self._handle(), *[_lib.ptr(a) for a in arrs]))
-        for n, a in zip(self._NAMES, arrs):
-            setattr(self, n, a)
+    def _factor_shapes(self):
+        return [(self.I, self.K), (self.K, self.L), (self.J, self.L)]
 
     # -- initialise / run -------------------------------------------------------
     def train(self, init_S, init_FG, iterations):
@@ -93,15 +75,7 @@ class bnmtf_vb_optimised(DeviceModel):
             kmeans_G.initialise()
             kmeans_G.cluster()
             self.muG = kmeans_G.clustering_results
-        self.expF, self.varF = np.zeros((self.I, self.K)), np.zeros((self.I, self.K))
-        self.expS, self.varS = np.zeros((self.K, self.L)), np.zeros((self.K, self.L))
-        self.expG, self.varG = np.zeros((self.J, self.L)), np.zeros((self.J, self.L))
-        for k in range(self.K):
-            self.update_exp_F(k)
-        for k, l in itertools.product(range(self.K), range(self.L)):
-            self.update_exp_S(k, l)
-        for l in range(self.L):
-            self.update_exp_G(l)
+        self._initial_moments()            # (update_exp_F(k), update_exp_S(k, l), update_exp_G(l) of every column and entry, :147-153)
         self.update_tau()
         self.update_exp_tau()
 
@@ -128,34 +102,13 @@ class bnmtf_vb_optimised(DeviceModel):
         it = int(iterations)
         orders = self._draw_orders(it) if orders is None else np.ascontiguousarray(orders, dtype=np.int32)
         assert orders.shape == (it, self.K * self.L + self.K + self.L)
-        self._push()
-        self._set_heldout(Mt)
-        exptau = np.zeros(it); perf = np.zeros((it, 3)); terms = np.zeros((it, 10)); times = np.zeros(it)
-        self._run_device(it, orders, exptau, perf, terms, times)
-        self._finish_heldout(it)
-        self._run_finish(it, exptau, perf, terms, times)
+        # (all_elbo_terms: of the ELBO the reference prints per iteration only the last one can be finished -- the K.L terms of S
+        # need the q(S) of that iteration; earlier iterations carry the F / G / tau part)
+        self._run(it, Mt, orders)
 
     def _run_device(self, it, orders, exptau, perf, terms, times):
-        """The device call of run() (bnmtf_vb_observed: the observed-entry layout's)."""
-        _lib.check(_lib.lib().bnmtf_vb_run(self._handle(), it, _lib.ptr(orders), _lib.ptr(exptau), _lib.ptr(perf), _lib.ptr(terms), _lib.ptr(times)))
-
-    def _run_finish(self, it, exptau, perf, terms, times):
-        """What run() does behind the device call (batch.run_many: behind the call that ran this model among others)."""
-        self._pull()
-        self.all_exp_tau = list(exptau)
-        self.all_times = list(times)
-        self.all_performances = performances(perf)
-        if it > 0:
-            self.alpha_s = self.alpha + self.size_Omega / 2.0
-            self.beta_s = terms[-1, 1]
-            self.update_exp_tau()
-        # the ELBO the reference prints per iteration: only the last one can be finished here (the K.L terms of S need
-        # the q(S) of that iteration); earlier iterations carry the F / G / tau part
-        self.all_elbo_terms = terms
-        if self.verbose:
-            for i in range(it):
-                print("Iteration %s. MSE: %s. R^2: %s. Rp: %s." % (i + 1, perf[i, 0], perf[i, 1], perf[i, 2]))
-        return
+        """The device call of run(), either layout's."""
+        _lib.check(self._entry("run")(self._handle(), it, _lib.ptr(orders), _lib.ptr(exptau), _lib.ptr(perf), _lib.ptr(terms), _lib.ptr(times)))
 
     # -- ELBO -------------------------------------------------------------------
     def elbo(self):
@@ -179,26 +132,6 @@ class bnmtf_vb_optimised(DeviceModel):
         return np.dot(M1, np.dot(M2, M3))
 
     # -- updates ----------------------------------------------------------------
-    def update_tau(self):
-        """:231-233."""
-        self.alpha_s = self.alpha + self.size_Omega / 2.0
-        self.beta_s = self.beta + 0.5 * self.exp_square_diff()
-
-    def _esd_and_sums(self):
-        self._push()
-        esd = C.c_double(); sums = np.zeros(6)
-        _lib.check(_lib.lib().bnmtf_vb_exp_square_diff(self._handle(), C.byref(esd), _lib.ptr(sums)))
-        return esd.value, sums
-
-    def exp_square_diff(self):
-        """:235-239 (fp64 on the device)."""
-        return self._esd_and_sums()[0]
-
-    def _update(self, which, k, l, moments):
-        self._push()
-        _lib.check(_lib.lib().bnmtf_vb_update(self._handle(), which, int(k), int(l), int(moments)))
-        self._pull()
-
     def update_F(self, k):
         """:241-250."""
         self._update(0, k, 0, 0)
@@ -213,40 +146,15 @@ class bnmtf_vb_optimised(DeviceModel):
 
     def update_exp_F(self, k):
         """:276-278."""
-        self.expF[:, k] = TN_vector_expectation(self.muF[:, k], self.tauF[:, k])
-        self.varF[:, k] = TN_vector_variance(self.muF[:, k], self.tauF[:, k])
+        self._update_exp("F", np.s_[:, k])
 
     def update_exp_S(self, k, l):
         """:280-282."""
-        self.expS[k, l] = TN_vector_expectation([self.muS[k, l]], [self.tauS[k, l]])[0]
-        self.varS[k, l] = TN_vector_variance([self.muS[k, l]], [self.tauS[k, l]])[0]
+        self._update_exp("S", (k, l))
 
     def update_exp_G(self, l):
         """:284-285."""
-        self.expG[:, l] = TN_vector_expectation(self.muG[:, l], self.tauG[:, l])
-        self.varG[:, l] = TN_vector_variance(self.muG[:, l], self.tauG[:, l])
-
-    def update_exp_tau(self):
-        """:286-288."""
-        self.exptau = gamma_expectation(self.alpha_s, self.beta_s)
-        self.explogtau = gamma_expectation_log(self.alpha_s, self.beta_s)
-
-    # -- prediction / model quality ----------------------------------------------
-    def predict(self, M_pred):
-        """:292-297."""
-        return metrics_from_sums(self._metric_sums(M_pred, self.expF, self.expS, self.expG))
-
-    def quality(self, metric):
-        """:320-337."""
-        return information_criterion(metric, tuple, self.log_likelihood,
-                                     lambda: metrics_from_sums(self._metric_sums(None, self.expF, self.expS, self.expG))['MSE'],
-                                     self.I * self.K + self.K * self.L + self.J * self.L, self.size_Omega, self.elbo)
-
-    def log_likelihood(self):
-        """:339-342."""
-        s = self._metric_sums(None, self.expF, self.expS, self.expG)
-        sse = s[2] - 2.0 * s[5] + s[4]
-        return self.size_Omega / 2. * (self.explogtau - math.log(2 * math.pi)) - self.exptau / 2. * sse
+        self._update_exp("G", np.s_[:, l])
 
 
 bnmtf_vb = bnmtf_vb_optimised

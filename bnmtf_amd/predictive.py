@@ -145,11 +145,10 @@ def posterior_predictive(model, at, burn_in, thinning, *, device=None):
     bnmf_gibbs_optimised or bnmtf_gibbs_optimised that has run with store_samples=True, either layout, any rank; at: an Entries of
     the model's shape (its values are ignored) or (rows, cols), any order, repeats allowed; device: defaults to the model's."""
     from ._sampler import GibbsSampler, ICMRules
-    from .bnmf_vb import bnmf_vb_optimised
-    from .bnmtf_vb import bnmtf_vb_optimised
+    from ._variational import Variational
     from .nmf_np import NPDevice
     who = type(model).__name__ + ": posterior_predictive"
-    if isinstance(model, (bnmf_vb_optimised, bnmtf_vb_optimised)):
+    if isinstance(model, Variational):
         _refuse(who, "a variational model has no posterior samples: its predictive variance is a closed form of q, not a sample "
                      "statistic, and is out of scope here (bnmf_gibbs_optimised and bnmtf_gibbs_optimised are taken)")
     if isinstance(model, (ICMRules, NPDevice)):

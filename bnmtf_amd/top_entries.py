@@ -160,23 +160,17 @@ def from_factors(factors, n, *, rows=None, exclude=None, largest=True, device=0,
 def _model_factors(who, model, burn_in, thinning):
     """the factors the class's predict() multiplies, in the order (A, B) or (A, S, B)"""
     from ._sampler import GibbsSampler, ICMRules
-    from .bnmf_vb import bnmf_vb_optimised
-    from .bnmtf_vb import bnmtf_vb_optimised
+    from ._variational import Variational
     from .nmf_np import NPDevice
     gibbs = isinstance(model, GibbsSampler) and not isinstance(model, ICMRules)
     if not gibbs:
-        if not isinstance(model, (GibbsSampler, bnmf_vb_optimised, bnmtf_vb_optimised, NPDevice)):
+        if not isinstance(model, (GibbsSampler, Variational, NPDevice)):
             _refuse(who, "not a model of this package")
         if burn_in is not None or thinning is not None:
             _refuse(who, "burn_in and thinning select the samples of a Gibbs model (bnmf_gibbs_optimised, bnmtf_gibbs_optimised); "
                          "this class has one estimate and takes neither")
-        if isinstance(model, bnmf_vb_optimised):
-            names = ("expU", "expV")
-        elif isinstance(model, bnmtf_vb_optimised):
-            names = ("expF", "expS", "expG")
-        else:
-            names = None
-        if names is not None:
+        if isinstance(model, Variational):
+            names = ["exp" + f for f in model._FACTORS]
             if not all(hasattr(model, a) for a in names):
                 _refuse(who, "no factors yet: initialise() has not been called")
             return [getattr(model, a) for a in names]
