@@ -1723,4 +1723,5 @@ int bnmtf_gamma_sample(double alpha, double beta, uint64_t seed, uint64_t it, in
 #include "api_obs_np.inc"
 #include "api_many.inc"
 #include "api_top.inc"
+#include "api_foldin.inc"
 #include "api_predictive.inc"

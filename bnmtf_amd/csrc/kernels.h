@@ -6,7 +6,7 @@
 namespace bnmtf {
 
 // RNG stream ids (counter word 3, low 4 bits) -- same numbers as oracle/rng.py
-constexpr uint32_t kStreamRows = 0, kStreamCols = 1, kStreamS = 2, kStreamTau = 3, kStreamHook = 8;
+constexpr uint32_t kStreamRows = 0, kStreamCols = 1, kStreamS = 2, kStreamTau = 3, kStreamFoldIn = 4, kStreamHook = 8;
 
 // ---------------------------------------------------------------------------
 // K1/K2: masked contraction  out[n][KP] = sum_inner big[inner][n] * X[inner][KP]
@@ -657,6 +657,31 @@ struct TopArgs {
   int32_t* cols; double* scores; int32_t* counts;           // [r][n], [r]: the answer; -1 / nan behind counts[q] slots
 };
 void launch_top(const TopArgs& a, hipStream_t st);        // top_fs_kernel (L > 0), top_kernel, top_merge_kernel
+
+// Fold new units into a fitted model (kernel_foldin.hip; bnmtf_fold_in): the other factor fixed, the whole
+// chain of a unit in one wave of one launch, the statistics of its factor row kept in fp64 in that wave's LDS
+constexpr int kFoldInWaves = 4;            // units (waves) per block
+constexpr int kFoldInMaxRank = 256;        // W (BNMTF_FOLDIN_MAX_RANK): a unit's x, rates, a and statistics take 9 KiB of LDS per wave
+constexpr int kFoldInMaxSlots = 8;         // register form: entries per lane (1, 2, 4, 8); a unit of more than 512 entries runs the long form
+struct FoldInArgs {
+  const uint32_t* ptr;               // [n + 1] the entries of unit u are [ptr[u], ptr[u + 1]), at least one each
+  const uint32_t* idx;               // their indices into the fixed factor, ascending within a unit, all < m
+  const float* val;                  // their values
+  int n, m, W, KP;                   // units, rows of the fixed factor, rank, its row stride (W rounded up to 4; padding columns zero)
+  const float* Xo; const float* XoT; int ldT;   // the fixed factor [m][KP] and [W][ldT], ldT > m: XoT[k][m] is zero
+  const float* lambda; const float* init;       // [n][W]
+  const uint32_t* ids;               // [n] the element word of each unit's Philox counter
+  float tau, min_x;
+  uint32_t key0, key1, it0;          // the seed's halves and the iteration word of the first sweep
+  int T, discard, keep_every;        // sweeps; the kept ones are discard, discard + keep_every, ... < T
+  int mode;                          // kSweepDraw / kSweepMode
+  int force_long;                    // every unit down the long form
+  float* escratch;                   // [entries] the long form's residual, at the entry's list position
+  double* stats;                     // [3][n][W]: the first kept x, sum (x_t - first), sum (x_t - first)^2 over the kept sweeps
+  float* samples;                    // null, or [T][n][W]
+};
+inline int foldin_blocks(int n) { return (n + kFoldInWaves - 1) / kFoldInWaves; }
+void launch_foldin(const FoldInArgs& a, hipStream_t st);
 
 // The variational two-factor model on the same lists (kernel_obs_vb.hip): q = (mu, tau, var) beside the expectation X, and
 // S2 = var + X^2 transposed beside XT for the other direction's second gather

@@ -628,6 +628,31 @@ BNMTF_API int bnmtf_top_entries(int device, int I, int J, int K, int L,
  * BNMTF_OK; zeros before one did (tools/top_entries_rates.py) */
 BNMTF_API int bnmtf_top_entries_times(double* upload_ms, double* kernel_ms);
 
+/* ---- fold new rows or columns into a fitted model, the chains on the device (bnmtf_amd.fold_in) --------
+ * No handle: the call makes its own stream and buffers on `device` and frees all of them on every path.  other [m][W]: the factor
+ * that stays fixed, 1 <= m <= 2^30, 1 <= W <= BNMTF_FOLDIN_MAX_RANK; the device takes it in fp32.  The new units' entries: 1 <= n <
+ * 2^31 triples (unit[e], idx[e], values[e]) with 0 <= unit < n_units and 0 <= idx < m, sorted by (unit, idx), no entry twice, every
+ * unit at least once.  lambda, init [n_units][W]: each unit's prior rates (>= 0) and the start of its chain; tau > 0; ids [n_units]:
+ * the element word of each unit's Philox counter (null: 0 .. n_units - 1).  Per unit, for t = 0 .. iterations - 1 and then k = 0 ..
+ * W - 1, the conditional of x_k given the fixed factor, fp32: update 0 draws from TN(mu, tau_p) -- counter
+ * (id, k, first_iteration + t, stream 4 | candidate), key = seed, first accepted candidate --, update 1 sets max(max(0, mu), min_x).
+ * Outputs [n_units][W] over the kept sweeps discard, discard + keep_every, ... < iterations, in that order: first_out = x of the
+ * first kept sweep, sum_d_out = sum (x_t - first), sum_d2_out = sum (x_t - first)^2, in fp64; the caller finishes mean = first +
+ * sum_d / count and variance = max(0, sum_d2 / count - (sum_d / count)^2).  update 1 takes discard = 0 and keep_every = 1 and keeps
+ * the final state alone.  samples_out: null, or [iterations][n_units][W] fp32, every sweep's x.  One launch, a wave per unit.  form:
+ * 0 -- a unit of at most 512 entries keeps its residual in registers, a longer one in device memory --, 1 -- every unit the second
+ * way; a unit's numbers depend on its own entries, rates, start, id, tau, seed, the fixed factor and the chain's parameters alone:
+ * not on form, not on the other units or its place among them.  Everything is checked before the first device call. */
+#define BNMTF_FOLDIN_MAX_RANK 256
+BNMTF_API int bnmtf_fold_in(int device, int n_units, int m, int W, const double* other,
+    uint64_t n, const int32_t* unit, const int32_t* idx, const float* values,
+    const double* lambda, double tau, const double* init, const uint32_t* ids, uint64_t seed,
+    int iterations, int first_iteration, int discard, int keep_every, int update, double min_x, int form,
+    double* first_out, double* sum_d_out, double* sum_d2_out, float* samples_out);
+/* upload and kernel time (ms, from events on the call's stream) of the calling host thread's last bnmtf_fold_in that returned
+ * BNMTF_OK; zeros before one did (tools/fold_in_rates.py) */
+BNMTF_API int bnmtf_fold_in_times(double* upload_ms, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
