@@ -148,6 +148,38 @@ struct DevBuf {
   int alloc(size_t count, bool zero = false) { return dalloc(&p, count, zero); }
   ~DevBuf() { dfree(p); }
 };
+// the stream and the three events of one call that takes no handle (api_predictive.inc, api_top.inc, api_foldin.inc): event 0
+// before an upload, 1 behind it, 2 behind the kernel; released on every return path
+struct CallScope {
+  hipStream_t s = nullptr;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  int open(int device) {
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+    return BNMTF_OK;
+  }
+  int mark(int i) { HIPCHK(hipEventRecord(ev[i], s)); return BNMTF_OK; }
+  int elapsed(double* upload_ms, double* kernel_ms) const {      // (events 0 - 1 and 1 - 2, which the caller has waited for)
+    float up = 0.f, kn = 0.f;
+    HIPCHK(hipEventElapsedTime(&up, ev[0], ev[1]));
+    HIPCHK(hipEventElapsedTime(&kn, ev[1], ev[2]));
+    *upload_ms = up; *kernel_ms = kn;
+    return BNMTF_OK;
+  }
+  ~CallScope() {
+    for (int i = 2; i >= 0; --i) if (ev[i]) (void)hipEventDestroy(ev[i]);
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+// upload and kernel time of this host thread's last call of each of the three, from the events (bnmtf_*_times)
+enum CallKind { kCallPredictive, kCallTop, kCallFoldIn, kCallKinds };
+static thread_local double g_call_ms[kCallKinds][2] = {};
+static int call_times(const char* who, CallKind kind, double* upload_ms, double* kernel_ms) {
+  if (!upload_ms || !kernel_ms) { set_error("%s: null argument", who); return BNMTF_EINVAL; }
+  *upload_ms = g_call_ms[kind][0]; *kernel_ms = g_call_ms[kind][1];
+  return BNMTF_OK;
+}
 
 // ------------------------------------------------------------------ layout
 // Fill one direction: the contraction's split geometry, the I x J passes on the device (kernel_layout.hip: masked / transposed

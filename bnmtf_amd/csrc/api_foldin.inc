@@ -10,17 +10,6 @@ namespace bnmtf {
 
 constexpr int kFoldInMaxDim = 1 << 30;               // m: an index and the zero word behind a column stay inside an int
 
-struct FoldInStream {
-  hipStream_t s = nullptr;
-  ~FoldInStream() { if (s) (void)hipStreamDestroy(s); }
-};
-struct FoldInEvent {
-  hipEvent_t e = nullptr;
-  ~FoldInEvent() { if (e) (void)hipEventDestroy(e); }
-};
-// upload and kernel time of this host thread's last bnmtf_fold_in, from the events (bnmtf_fold_in_times)
-static thread_local double g_foldin_ms[2] = {0.0, 0.0};
-
 }  // namespace bnmtf
 
 extern "C" {
@@ -101,14 +90,11 @@ int bnmtf_fold_in(int device, int n_units, int m, int W, const double* other,
   const uint32_t* const use_ids = ids ? ids : own_ids.data();
 
   // ---- the device's side: all of it owned here
-  HIPCHK(hipSetDevice(device));
-  FoldInStream st;
-  FoldInEvent ev[3];
+  CallScope cs;
   DevBuf<uint32_t> d_ptr, d_idx, d_ids;
   DevBuf<float> d_val, d_Xo, d_XoT, d_lam, d_x0, d_es, d_samples;
   DevBuf<double> d_stats;
-  HIPCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e.e));
+  CHK(cs.open(device));
   const size_t nsamp = samples_out ? (size_t)iterations * nW : 0;
   CHK(d_ptr.alloc(ptr.size())); CHK(d_idx.alloc((size_t)n)); CHK(d_val.alloc((size_t)n)); CHK(d_ids.alloc((size_t)n_units));
   CHK(d_Xo.alloc(Xo.size())); CHK(d_XoT.alloc(XoT.size())); CHK(d_lam.alloc(nW)); CHK(d_x0.alloc(nW));
@@ -116,16 +102,16 @@ int bnmtf_fold_in(int device, int n_units, int m, int W, const double* other,
   CHK(d_stats.alloc(3 * nW));
   if (nsamp) CHK(d_samples.alloc(nsamp));
 
-  HIPCHK(hipEventRecord(ev[0].e, st.s));
-  HIPCHK(hipMemcpyAsync(d_ptr.p, ptr.data(), ptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st.s));
-  HIPCHK(hipMemcpyAsync(d_idx.p, idu.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st.s));
-  HIPCHK(hipMemcpyAsync(d_val.p, values, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st.s));
-  HIPCHK(hipMemcpyAsync(d_ids.p, use_ids, (size_t)n_units * sizeof(uint32_t), hipMemcpyHostToDevice, st.s));
-  HIPCHK(hipMemcpyAsync(d_Xo.p, Xo.data(), Xo.size() * sizeof(float), hipMemcpyHostToDevice, st.s));
-  HIPCHK(hipMemcpyAsync(d_XoT.p, XoT.data(), XoT.size() * sizeof(float), hipMemcpyHostToDevice, st.s));
-  HIPCHK(hipMemcpyAsync(d_lam.p, lam.data(), nW * sizeof(float), hipMemcpyHostToDevice, st.s));
-  HIPCHK(hipMemcpyAsync(d_x0.p, x0.data(), nW * sizeof(float), hipMemcpyHostToDevice, st.s));
-  HIPCHK(hipEventRecord(ev[1].e, st.s));
+  CHK(cs.mark(0));
+  HIPCHK(hipMemcpyAsync(d_ptr.p, ptr.data(), ptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, cs.s));
+  HIPCHK(hipMemcpyAsync(d_idx.p, idu.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, cs.s));
+  HIPCHK(hipMemcpyAsync(d_val.p, values, (size_t)n * sizeof(float), hipMemcpyHostToDevice, cs.s));
+  HIPCHK(hipMemcpyAsync(d_ids.p, use_ids, (size_t)n_units * sizeof(uint32_t), hipMemcpyHostToDevice, cs.s));
+  HIPCHK(hipMemcpyAsync(d_Xo.p, Xo.data(), Xo.size() * sizeof(float), hipMemcpyHostToDevice, cs.s));
+  HIPCHK(hipMemcpyAsync(d_XoT.p, XoT.data(), XoT.size() * sizeof(float), hipMemcpyHostToDevice, cs.s));
+  HIPCHK(hipMemcpyAsync(d_lam.p, lam.data(), nW * sizeof(float), hipMemcpyHostToDevice, cs.s));
+  HIPCHK(hipMemcpyAsync(d_x0.p, x0.data(), nW * sizeof(float), hipMemcpyHostToDevice, cs.s));
+  CHK(cs.mark(1));
 
   FoldInArgs a; memset(&a, 0, sizeof(a));
   a.ptr = d_ptr.p; a.idx = d_idx.p; a.val = d_val.p;
@@ -142,27 +128,24 @@ int bnmtf_fold_in(int device, int n_units, int m, int W, const double* other,
   a.escratch = d_es.p;
   a.stats = d_stats.p;
   a.samples = nsamp ? d_samples.p : nullptr;
-  launch_foldin(a, st.s);
+  launch_foldin(a, cs.s);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ev[2].e, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  CHK(cs.mark(2));
+  HIPCHK(hipStreamSynchronize(cs.s));
   HIPCHK(hipGetLastError());
-  float up = 0.f, kn = 0.f;
-  HIPCHK(hipEventElapsedTime(&up, ev[0].e, ev[1].e));
-  HIPCHK(hipEventElapsedTime(&kn, ev[1].e, ev[2].e));
+  double up = 0.0, kn = 0.0;
+  CHK(cs.elapsed(&up, &kn));
 
   HIPCHK(hipMemcpy(first_out, d_stats.p, nW * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(sum_d_out, d_stats.p + nW, nW * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(sum_d2_out, d_stats.p + 2 * nW, nW * sizeof(double), hipMemcpyDeviceToHost));
   if (nsamp) HIPCHK(hipMemcpy(samples_out, d_samples.p, nsamp * sizeof(float), hipMemcpyDeviceToHost));
-  g_foldin_ms[0] = up; g_foldin_ms[1] = kn;
+  g_call_ms[kCallFoldIn][0] = up; g_call_ms[kCallFoldIn][1] = kn;
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
 int bnmtf_fold_in_times(double* upload_ms, double* kernel_ms) try {
-  if (!upload_ms || !kernel_ms) { set_error("bnmtf_fold_in_times: null argument"); return BNMTF_EINVAL; }
-  *upload_ms = g_foldin_ms[0]; *kernel_ms = g_foldin_ms[1];
-  return BNMTF_OK;
+  return call_times("bnmtf_fold_in_times", kCallFoldIn, upload_ms, kernel_ms);
 } BNMTF_ABI_GUARD
 
 }  // extern "C"

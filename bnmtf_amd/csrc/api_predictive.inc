@@ -12,17 +12,6 @@ namespace bnmtf {
 
 constexpr size_t kPredictiveStageBytes = (size_t)256 << 20;      // chunk_samples = 0: as many samples as fit this, at least one
 
-struct PredictiveStream {
-  hipStream_t s = nullptr;
-  ~PredictiveStream() { if (s) (void)hipStreamDestroy(s); }
-};
-struct PredictiveEvent {
-  hipEvent_t e = nullptr;
-  ~PredictiveEvent() { if (e) (void)hipEventDestroy(e); }
-};
-// upload and kernel time of this host thread's last bnmtf_predictive_samples, from the events (bnmtf_predictive_times)
-static thread_local double g_predictive_ms[2] = {0.0, 0.0};
-
 // samples [t0, t0 + c) of the call, array indices first + t * step, `per` floats each, onto dst
 static int predictive_upload(float* dst, const float* src, size_t per, uint64_t first, uint64_t step, int t0, int c, hipStream_t st) {
   if (step == 1) {
@@ -77,20 +66,17 @@ int bnmtf_predictive_samples(int device, int I, int J, int K, int L, uint64_t n,
   if (chunk > T) chunk = T;
 
   // ---- the device's side: all of it owned here
-  HIPCHK(hipSetDevice(device));
-  PredictiveStream st;
-  PredictiveEvent ev[3];
+  CallScope cs;
   DevBuf<uint32_t> d_rowptr, d_col;
   DevBuf<float> dA, dS, dB;
   DevBuf<double> d_first, d_sum, d_sum2;
-  HIPCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e.e));
+  CHK(cs.open(device));
   CHK(d_rowptr.alloc(rowptr.size())); CHK(d_col.alloc(n));
   CHK(dA.alloc((size_t)chunk * perA)); CHK(dB.alloc((size_t)chunk * perB));
   if (L > 0) CHK(dS.alloc((size_t)chunk * perS));
   CHK(d_first.alloc(n, true)); CHK(d_sum.alloc(n, true)); CHK(d_sum2.alloc(n, true));
-  HIPCHK(hipMemcpyAsync(d_rowptr.p, rowptr.data(), rowptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st.s));
-  HIPCHK(hipMemcpyAsync(d_col.p, col.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st.s));
+  HIPCHK(hipMemcpyAsync(d_rowptr.p, rowptr.data(), rowptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, cs.s));
+  HIPCHK(hipMemcpyAsync(d_col.p, col.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, cs.s));
 
   PredictiveArgs a; memset(&a, 0, sizeof(a));
   a.rowptr = d_rowptr.p; a.col = d_col.p;
@@ -100,22 +86,21 @@ int bnmtf_predictive_samples(int device, int I, int J, int K, int L, uint64_t n,
   double upload_ms = 0.0, kernel_ms = 0.0;
   for (int t0 = 0; t0 < T; t0 += chunk) {
     const int c = T - t0 < chunk ? T - t0 : chunk;
-    HIPCHK(hipEventRecord(ev[0].e, st.s));
-    CHK(predictive_upload(dA.p, A, perA, first, step, t0, c, st.s));
-    if (L > 0) CHK(predictive_upload(dS.p, S, perS, first, step, t0, c, st.s));
-    CHK(predictive_upload(dB.p, B, perB, first, step, t0, c, st.s));
-    HIPCHK(hipEventRecord(ev[1].e, st.s));
+    CHK(cs.mark(0));
+    CHK(predictive_upload(dA.p, A, perA, first, step, t0, c, cs.s));
+    if (L > 0) CHK(predictive_upload(dS.p, S, perS, first, step, t0, c, cs.s));
+    CHK(predictive_upload(dB.p, B, perB, first, step, t0, c, cs.s));
+    CHK(cs.mark(1));
     a.C = c; a.first = t0 == 0 ? 1 : 0;
-    launch_predictive(a, st.s);
+    launch_predictive(a, cs.s);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev[2].e, st.s));
-    HIPCHK(hipEventSynchronize(ev[2].e));          // (the staging buffers are the next chunk's; the stream orders that by itself)
-    float up = 0.f, kn = 0.f;
-    HIPCHK(hipEventElapsedTime(&up, ev[0].e, ev[1].e));
-    HIPCHK(hipEventElapsedTime(&kn, ev[1].e, ev[2].e));
+    CHK(cs.mark(2));
+    HIPCHK(hipEventSynchronize(cs.ev[2]));         // (the staging buffers are the next chunk's; the stream orders that by itself)
+    double up = 0.0, kn = 0.0;
+    CHK(cs.elapsed(&up, &kn));
     upload_ms += up; kernel_ms += kn;
   }
-  HIPCHK(hipStreamSynchronize(st.s));
+  HIPCHK(hipStreamSynchronize(cs.s));
   HIPCHK(hipGetLastError());
 
   // ---- back, from list order to the given order
@@ -126,14 +111,12 @@ int bnmtf_predictive_samples(int device, int I, int J, int K, int L, uint64_t n,
     HIPCHK(hipMemcpy(sorted.data(), devs[m], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     for (uint64_t q = 0; q < n; ++q) outs[m][perm[q]] = sorted[q];
   }
-  g_predictive_ms[0] = upload_ms; g_predictive_ms[1] = kernel_ms;
+  g_call_ms[kCallPredictive][0] = upload_ms; g_call_ms[kCallPredictive][1] = kernel_ms;
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
 int bnmtf_predictive_times(double* upload_ms, double* kernel_ms) try {
-  if (!upload_ms || !kernel_ms) { set_error("bnmtf_predictive_times: null argument"); return BNMTF_EINVAL; }
-  *upload_ms = g_predictive_ms[0]; *kernel_ms = g_predictive_ms[1];
-  return BNMTF_OK;
+  return call_times("bnmtf_predictive_times", kCallPredictive, upload_ms, kernel_ms);
 } BNMTF_ABI_GUARD
 
 }  // extern "C"

@@ -12,17 +12,6 @@ namespace bnmtf {
 constexpr int kTopMaxDim = 1 << 30;                  // I and J: column indices and their 64-column steps stay inside an int
 constexpr long long kTopFillPairs = 256 * 8;         // split = 0: (row, segment) pairs that fill 256 CUs with eight waves each
 
-struct TopStream {
-  hipStream_t s = nullptr;
-  ~TopStream() { if (s) (void)hipStreamDestroy(s); }
-};
-struct TopEvent {
-  hipEvent_t e = nullptr;
-  ~TopEvent() { if (e) (void)hipEventDestroy(e); }
-};
-// upload and kernel time of this host thread's last bnmtf_top_entries, from the events (bnmtf_top_entries_times)
-static thread_local double g_top_ms[2] = {0.0, 0.0};
-
 static bool top_all_finite(const double* p, size_t count) {
   for (size_t t = 0; t < count; ++t)
     if (!std::isfinite(p[t])) return false;
@@ -131,14 +120,11 @@ int bnmtf_top_entries(int device, int I, int J, int K, int L, const double* A, c
   }
 
   // ---- the device's side: all of it owned here
-  HIPCHK(hipSetDevice(device));
-  TopStream st;
-  TopEvent ev[3];
+  CallScope cs;
   DevBuf<double> dA, dS, dFS, dB, d_key, d_scores;
   DevBuf<uint32_t> d_exptr, d_excol;
   DevBuf<int32_t> d_pcol, d_pcnt, d_cols, d_counts;
-  HIPCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e.e));
+  CHK(cs.open(device));
   const size_t nA = (size_t)r * K, nB = (size_t)J * stride, nout = (size_t)r * n, npart = (size_t)pairs * n;
   CHK(dA.alloc(nA)); CHK(dB.alloc(nB));
   if (L > 0) { CHK(dS.alloc((size_t)K * L)); CHK(dFS.alloc((size_t)r * L)); }
@@ -146,13 +132,13 @@ int bnmtf_top_entries(int device, int I, int J, int K, int L, const double* A, c
   CHK(d_key.alloc(npart)); CHK(d_pcol.alloc(npart)); CHK(d_pcnt.alloc((size_t)pairs));
   CHK(d_cols.alloc(nout)); CHK(d_scores.alloc(nout)); CHK(d_counts.alloc((size_t)r));
 
-  HIPCHK(hipEventRecord(ev[0].e, st.s));
-  HIPCHK(hipMemcpyAsync(dA.p, Ause, nA * sizeof(double), hipMemcpyHostToDevice, st.s));
-  if (L > 0) HIPCHK(hipMemcpyAsync(dS.p, S, (size_t)K * L * sizeof(double), hipMemcpyHostToDevice, st.s));
-  HIPCHK(hipMemcpyAsync(dB.p, Buse, nB * sizeof(double), hipMemcpyHostToDevice, st.s));
-  HIPCHK(hipMemcpyAsync(d_exptr.p, exptr.data(), exptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st.s));
-  if (!excol.empty()) HIPCHK(hipMemcpyAsync(d_excol.p, excol.data(), excol.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st.s));
-  HIPCHK(hipEventRecord(ev[1].e, st.s));
+  CHK(cs.mark(0));
+  HIPCHK(hipMemcpyAsync(dA.p, Ause, nA * sizeof(double), hipMemcpyHostToDevice, cs.s));
+  if (L > 0) HIPCHK(hipMemcpyAsync(dS.p, S, (size_t)K * L * sizeof(double), hipMemcpyHostToDevice, cs.s));
+  HIPCHK(hipMemcpyAsync(dB.p, Buse, nB * sizeof(double), hipMemcpyHostToDevice, cs.s));
+  HIPCHK(hipMemcpyAsync(d_exptr.p, exptr.data(), exptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, cs.s));
+  if (!excol.empty()) HIPCHK(hipMemcpyAsync(d_excol.p, excol.data(), excol.size() * sizeof(uint32_t), hipMemcpyHostToDevice, cs.s));
+  CHK(cs.mark(1));
 
   TopArgs a; memset(&a, 0, sizeof(a));
   a.A = dA.p; a.S = L > 0 ? dS.p : nullptr; a.FS = L > 0 ? dFS.p : nullptr; a.B = dB.p;
@@ -161,26 +147,23 @@ int bnmtf_top_entries(int device, int I, int J, int K, int L, const double* A, c
   a.n = n; a.largest = largest; a.split = use_split; a.seg_steps = seg_steps;
   a.part_key = d_key.p; a.part_col = d_pcol.p; a.part_cnt = d_pcnt.p;
   a.cols = d_cols.p; a.scores = d_scores.p; a.counts = d_counts.p;
-  launch_top(a, st.s);
+  launch_top(a, cs.s);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ev[2].e, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  CHK(cs.mark(2));
+  HIPCHK(hipStreamSynchronize(cs.s));
   HIPCHK(hipGetLastError());
-  float up = 0.f, kn = 0.f;
-  HIPCHK(hipEventElapsedTime(&up, ev[0].e, ev[1].e));
-  HIPCHK(hipEventElapsedTime(&kn, ev[1].e, ev[2].e));
+  double up = 0.0, kn = 0.0;
+  CHK(cs.elapsed(&up, &kn));
 
   HIPCHK(hipMemcpy(cols_out, d_cols.p, nout * sizeof(int32_t), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(scores_out, d_scores.p, nout * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(counts_out, d_counts.p, (size_t)r * sizeof(int32_t), hipMemcpyDeviceToHost));
-  g_top_ms[0] = up; g_top_ms[1] = kn;
+  g_call_ms[kCallTop][0] = up; g_call_ms[kCallTop][1] = kn;
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
 int bnmtf_top_entries_times(double* upload_ms, double* kernel_ms) try {
-  if (!upload_ms || !kernel_ms) { set_error("bnmtf_top_entries_times: null argument"); return BNMTF_EINVAL; }
-  *upload_ms = g_top_ms[0]; *kernel_ms = g_top_ms[1];
-  return BNMTF_OK;
+  return call_times("bnmtf_top_entries_times", kCallTop, upload_ms, kernel_ms);
 } BNMTF_ABI_GUARD
 
 }  // extern "C"

@@ -24,9 +24,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BnmtfError
+from ._postfit import device_of, factors_fit, integer, kind_of, model_factors, refuse, shifted_moments
 from .entries import Entries
-from .top_entries import _model_factors
 
 MAX_RANK = 256          # BNMTF_FOLDIN_MAX_RANK
 STREAM = 4              # kStreamFoldIn: the stream word of a fold-in draw
@@ -46,20 +45,6 @@ class FoldIn(object):
         return "FoldIn(%d units, rank %d, %d kept sweeps)" % (len(self.ids), self.mean.shape[1], self.count)
 
 
-def _refuse(who, why):
-    raise BnmtfError("%s: %s" % (who, why))
-
-
-def _integer(who, name, v, low):
-    try:
-        i = int(v)
-    except (TypeError, ValueError):
-        _refuse(who, "%s is an integer >= %d, not %r" % (name, low, v))
-    if i != v or i < low:
-        _refuse(who, "%s is an integer >= %d, not %r" % (name, low, v))
-    return i
-
-
 def fixed_side(factors, axis):
     """The factor that stays fixed, fp64 [m][W]: (A, B) -> B (axis=1: A); (F, S, G) -> G S^T (axis=1: F S), the inner index
     ascending, one product and one addition per term."""
@@ -77,24 +62,24 @@ def fixed_side(factors, axis):
 def _units(who, new, axis, m):
     """(unit, idx, values in fp32) sorted by (unit, idx), and the number of units"""
     if not isinstance(new, Entries):
-        _refuse(who, "new is an Entries, not %s" % type(new).__name__)
+        refuse(who, "new is an Entries, not %s" % type(new).__name__)
     if new.shape[1 - axis] != m:
-        _refuse(who, "with axis=%d new has shape %s over the %d rows of the fixed factor, not %s"
+        refuse(who, "with axis=%d new has shape %s over the %d rows of the fixed factor, not %s"
                 % (axis, "(n_new, %d)" % m if axis == 0 else "(%d, n_new)" % m, m, tuple(new.shape)))
     E = new if axis == 0 else Entries((new.shape[1], new.shape[0]), new.cols, new.rows, new.values)
     unit, idx, val = E.row_major()
     n_units = E.shape[0]
     if len(unit) == 0:
-        _refuse(who, "new holds no entry: every new %s needs at least one" % ("row", "column")[axis])
+        refuse(who, "new holds no entry: every new %s needs at least one" % ("row", "column")[axis])
     per = np.bincount(unit, minlength=n_units)
     if (per == 0).any():
-        _refuse(who, "new %s %d has no entry: every one needs at least one" % (("row", "column")[axis], int(np.flatnonzero(per == 0)[0])))
+        refuse(who, "new %s %d has no entry: every one needs at least one" % (("row", "column")[axis], int(np.flatnonzero(per == 0)[0])))
     same = (unit[1:] == unit[:-1]) & (idx[1:] == idx[:-1])
     if same.any():
         e = int(np.flatnonzero(same)[0])
-        _refuse(who, "entry (%d, %d) of new is given twice" % ((unit[e], idx[e]) if axis == 0 else (idx[e], unit[e])))
+        refuse(who, "entry (%d, %d) of new is given twice" % ((unit[e], idx[e]) if axis == 0 else (idx[e], unit[e])))
     if len(unit) >= 2 ** 31:
-        _refuse(who, "fewer than 2^31 entries (%d given)" % len(unit))
+        refuse(who, "fewer than 2^31 entries (%d given)" % len(unit))
     return (np.ascontiguousarray(unit, dtype=np.int32), np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(val, dtype=np.float32),
             n_units)
 
@@ -102,74 +87,74 @@ def _units(who, new, axis, m):
 def _compute(who, other, new, axis, lambdas, tau, iterations, update, discard, keep_every, init, seed, ids, first_iteration,
              store_samples, minimum_TN, device, form):
     if axis not in (0, 1):
-        _refuse(who, "axis is 0 (new rows) or 1 (new columns), not %r" % (axis,))
+        refuse(who, "axis is 0 (new rows) or 1 (new columns), not %r" % (axis,))
     other = np.ascontiguousarray(other, dtype=np.float64)
     if other.ndim != 2 or other.shape[0] < 1:
-        _refuse(who, "the fixed factor is two-dimensional [m][W], not %s" % (other.shape,))
+        refuse(who, "the fixed factor is two-dimensional [m][W], not %s" % (other.shape,))
     m, W = other.shape
     if not (1 <= W <= MAX_RANK):
-        _refuse(who, "ranks 1 .. %d (BNMTF_FOLDIN_MAX_RANK; W=%d)" % (MAX_RANK, W))
+        refuse(who, "ranks 1 .. %d (BNMTF_FOLDIN_MAX_RANK; W=%d)" % (MAX_RANK, W))
     if m > 2 ** 30:
-        _refuse(who, "at most 2^30 rows of the fixed factor (%d)" % m)
+        refuse(who, "at most 2^30 rows of the fixed factor (%d)" % m)
     if not np.isfinite(other).all():
-        _refuse(who, "the fixed factor holds a value that is not finite")
+        refuse(who, "the fixed factor holds a value that is not finite")
     unit, idx, val, n_units = _units(who, new, axis, m)
     if update not in ('draw', 'mode'):
-        _refuse(who, "update is 'draw' (a Gibbs chain) or 'mode' (the ICM rule), not %r: a variational fold-in is not offered" % (update,))
-    iterations = _integer(who, "iterations", iterations, 1)
-    first_iteration = _integer(who, "first_iteration", first_iteration, 0)
+        refuse(who, "update is 'draw' (a Gibbs chain) or 'mode' (the ICM rule), not %r: a variational fold-in is not offered" % (update,))
+    iterations = integer(who, "iterations", iterations, 1)
+    first_iteration = integer(who, "first_iteration", first_iteration, 0)
     if iterations + first_iteration >= 2 ** 31:
-        _refuse(who, "first_iteration + iterations stays below 2^31 (%d + %d)" % (first_iteration, iterations))
-    keep_every = _integer(who, "keep_every", keep_every, 1)
-    discard = _integer(who, "discard", discard, 0)
+        refuse(who, "first_iteration + iterations stays below 2^31 (%d + %d)" % (first_iteration, iterations))
+    keep_every = integer(who, "keep_every", keep_every, 1)
+    discard = integer(who, "discard", discard, 0)
     if discard >= iterations:
-        _refuse(who, "discard must lie below iterations (discard=%d, iterations=%d)" % (discard, iterations))
+        refuse(who, "discard must lie below iterations (discard=%d, iterations=%d)" % (discard, iterations))
     try:
         minimum_TN = float(minimum_TN)
     except (TypeError, ValueError):
-        _refuse(who, "minimum_TN is a number >= 0, not %r" % (minimum_TN,))
+        refuse(who, "minimum_TN is a number >= 0, not %r" % (minimum_TN,))
     if not (np.isfinite(minimum_TN) and minimum_TN >= 0.0):
-        _refuse(who, "minimum_TN is a finite number >= 0, not %r" % minimum_TN)
+        refuse(who, "minimum_TN is a finite number >= 0, not %r" % minimum_TN)
     if update == 'mode':
         if discard != 0 or keep_every != 1:
-            _refuse(who, "update='mode' has one answer, its final state, and takes neither discard nor keep_every")
+            refuse(who, "update='mode' has one answer, its final state, and takes neither discard nor keep_every")
     elif minimum_TN != 0.0:
-        _refuse(who, "minimum_TN belongs to update='mode'")
+        refuse(who, "minimum_TN belongs to update='mode'")
     try:
         tau = float(tau)
     except (TypeError, ValueError):
-        _refuse(who, "tau is a number > 0, not %r" % (tau,))
+        refuse(who, "tau is a number > 0, not %r" % (tau,))
     if not (np.isfinite(tau) and tau > 0.0):
-        _refuse(who, "tau is finite and positive, not %r" % tau)
+        refuse(who, "tau is finite and positive, not %r" % tau)
     lam = np.asarray(lambdas, dtype=np.float64)
     if lam.ndim > 2 or (lam.ndim >= 1 and lam.shape[-1] != W) or (lam.ndim == 2 and lam.shape[0] != n_units):
-        _refuse(who, "lambdas is a scalar, [W] or [n_new][W] with W=%d and n_new=%d, not %s" % (W, n_units, lam.shape))
+        refuse(who, "lambdas is a scalar, [W] or [n_new][W] with W=%d and n_new=%d, not %s" % (W, n_units, lam.shape))
     lam = np.ascontiguousarray(np.broadcast_to(lam, (n_units, W)))
     if not np.isfinite(lam).all() or (lam < 0).any():
-        _refuse(who, "lambdas holds a value that is not finite or is negative")
+        refuse(who, "lambdas holds a value that is not finite or is negative")
     if isinstance(init, str):
         if init != 'exp':
-            _refuse(who, "init is 'exp' (1 / lambda) or an array [n_new][W], not %r" % init)
+            refuse(who, "init is 'exp' (1 / lambda) or an array [n_new][W], not %r" % init)
         if (lam <= 0).any():
-            _refuse(who, "init='exp' is 1 / lambda and needs positive rates: give init as an array")
+            refuse(who, "init='exp' is 1 / lambda and needs positive rates: give init as an array")
         x0 = 1.0 / lam
     else:
         x0 = np.asarray(init, dtype=np.float64)
         if x0.shape != (n_units, W):
-            _refuse(who, "init is 'exp' or an array [n_new][W] = %s, not %s" % ((n_units, W), x0.shape))
+            refuse(who, "init is 'exp' or an array [n_new][W] = %s, not %s" % ((n_units, W), x0.shape))
         x0 = np.ascontiguousarray(x0)
     if not np.isfinite(x0).all() or not np.isfinite(x0.astype(np.float32)).all():
-        _refuse(who, "init holds a value that is not finite")
+        refuse(who, "init holds a value that is not finite")
     if ids is None:
         ids = np.arange(n_units, dtype=np.uint32)
     else:
         ids = np.asarray(ids)
         if ids.shape != (n_units,) or not np.issubdtype(ids.dtype, np.integer) or (ids.size and (ids.min() < 0 or ids.max() >= 2 ** 32)):
-            _refuse(who, "ids is a uint32 [n_new] = [%d], not %s of %s" % (n_units, ids.shape, ids.dtype))
+            refuse(who, "ids is a uint32 [n_new] = [%d], not %s of %s" % (n_units, ids.shape, ids.dtype))
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
-    seed = _integer(who, "seed", seed, 0) & (2 ** 64 - 1)
+    seed = integer(who, "seed", seed, 0) & (2 ** 64 - 1)
     if form not in (0, 1):
-        _refuse(who, "form is 0 (by the unit's entry count) or 1 (the long form for every unit), not %r" % (form,))
+        refuse(who, "form is 0 (by the unit's entry count) or 1 (the long form for every unit), not %r" % (form,))
 
     first, sum_d, sum_d2 = np.zeros((n_units, W)), np.zeros((n_units, W)), np.zeros((n_units, W))
     samples = np.zeros((iterations, n_units, W), dtype=np.float32) if store_samples else None
@@ -178,8 +163,8 @@ def _compute(who, other, new, axis, lambdas, tau, iterations, update, discard, k
                                         iterations, first_iteration, discard, keep_every, 1 if update == 'mode' else 0, minimum_TN, int(form),
                                         _lib.ptr(first), _lib.ptr(sum_d), _lib.ptr(sum_d2), _lib.ptr(samples)))
     count = 1 if update == 'mode' else len(range(discard, iterations, keep_every))
-    md = sum_d / count
-    return FoldIn(ids, first + md, np.maximum(0.0, sum_d2 / count - md * md), count, tau, other, samples)
+    mean, variance = shifted_moments(first, sum_d, sum_d2, count)
+    return FoldIn(ids, mean, variance, count, tau, other, samples)
 
 
 def from_factors(other, new, lambdas, tau, iterations, *, update='draw', axis=0, discard=0, keep_every=1, init='exp', seed=0, ids=None,
@@ -198,48 +183,35 @@ def fold_in(model, new, iterations, *, update='draw', axis=0, burn_in=None, thin
     included; burn_in, thinning: select the model's stored samples -- required for the Gibbs classes, refused for every other;
     discard, keep_every: the fold-in chain's own burn-in and thinning; lambdas: defaults to the row the model's rate matrix of the
     folded side repeats; tau: defaults to the class's estimate; seed, device: default to the model's."""
-    from ._sampler import GibbsSampler, ICMRules
-    from ._variational import Variational
-    from .nmf_np import NPDevice
     who = type(model).__name__ + ": fold_in"
-    if isinstance(model, NPDevice):
-        _refuse(who, "a non-probabilistic model has neither prior rates nor tau: give them to fold_in.from_factors with its factors")
+    kind = kind_of(model)
+    if kind == 'np':
+        refuse(who, "a non-probabilistic model has neither prior rates nor tau: give them to fold_in.from_factors with its factors")
     if axis not in (0, 1):
-        _refuse(who, "axis is 0 (new rows) or 1 (new columns), not %r" % (axis,))
-    factors = _model_factors(who, model, burn_in, thinning)
-    shapes = [np.shape(f) for f in factors]
-    fit = all(len(s) == 2 for s in shapes) and shapes[0][0] == int(model.I) and shapes[-1][0] == int(model.J)
-    if fit and len(shapes) == 2:
-        fit = shapes[0][1] == shapes[1][1]
-    elif fit:
-        fit = shapes[0][1] == shapes[1][0] and shapes[1][1] == shapes[2][1]
-    if not fit:
-        _refuse(who, "factor arrays of shapes %s do not fit each other and the %d x %d matrix" % (", ".join(str(s) for s in shapes), model.I, model.J))
+        refuse(who, "axis is 0 (new rows) or 1 (new columns), not %r" % (axis,))
+    factors = model_factors(who, model, burn_in, thinning)
+    factors_fit(who, factors, int(model.I), int(model.J), each_other=True)
     for f in factors:
         if not np.isfinite(np.asarray(f, dtype=np.float64)).all():
-            _refuse(who, "a factor holds a value that is not finite")
+            refuse(who, "a factor holds a value that is not finite")
     other = fixed_side(factors, axis)
-    gibbs = isinstance(model, GibbsSampler) and not isinstance(model, ICMRules)
     if tau is None:
-        tau = model.approx_expectation(burn_in, thinning)[-1] if gibbs else model.exptau if isinstance(model, Variational) else model.tau
+        tau = model.approx_expectation(burn_in, thinning)[-1] if kind == 'gibbs' else model.exptau if kind == 'variational' else model.tau
     if lambdas is None:
         name = "lambda" + model._FACTORS[0 if axis == 0 else -1]
         rates = np.asarray(getattr(model, name), dtype=np.float64)
         if rates.ndim == 2 and not (rates == rates[0]).all():
-            _refuse(who, "the rows of %s differ, so a new %s has no rate of its own: give lambdas=" % (name, ("row", "column")[axis]))
+            refuse(who, "the rows of %s differ, so a new %s has no rate of its own: give lambdas=" % (name, ("row", "column")[axis]))
         lambdas = rates[0] if rates.ndim == 2 else rates
     minimum_TN = 0.0
-    if update == 'mode' and isinstance(model, ICMRules):
+    if update == 'mode' and kind == 'icm':
         minimum_TN = getattr(model, "minimum_TN", 0.0)
     if seed is None:
         seed = getattr(model, "_seed", None)
         if seed is None:
-            _refuse(who, "the model has no seed yet: give seed=")
-    dev = device
-    if dev is None:
-        dev = getattr(model, "_device", 0)
+            refuse(who, "the model has no seed yet: give seed=")
     return _compute(who, other, new, axis, lambdas, tau, iterations, update, discard, keep_every, init, seed, ids, first_iteration,
-                    store_samples, minimum_TN, dev, 0)
+                    store_samples, minimum_TN, device_of(model, device), 0)
 
 
 fold_in.from_factors = from_factors              # (the package exports the function under the module's name: bnmtf_amd.fold_in.from_factors)

@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BnmtfError
+from ._postfit import device_of, entry_lists, kind_of, refuse, shifted_moments, stored_samples
 from .entries import Entries
 
 MAX_RANK = 256          # K and L of bnmtf_predictive_samples
@@ -40,62 +40,35 @@ class Predictive(object):
         return np.sqrt(self.variance + self.noise) if noise else np.sqrt(self.variance)
 
 
-def _refuse(who, why):
-    raise BnmtfError("%s: %s" % (who, why))
-
-
 def _progression(who, indices, stored):
     """(first, step, T) of `indices`, which must be first, first + step, ... with step >= 1, inside the stored samples"""
     idx = np.asarray(list(indices) if isinstance(indices, range) else indices)
     if idx.ndim != 1 or idx.size == 0:
-        _refuse(who, "no sample selected (%d stored)" % stored)
+        refuse(who, "no sample selected (%d stored)" % stored)
     if not np.issubdtype(idx.dtype, np.integer):
-        _refuse(who, "the sample indices are integers, not %s" % idx.dtype)
+        refuse(who, "the sample indices are integers, not %s" % idx.dtype)
     first, step = int(idx[0]), int(idx[1] - idx[0]) if idx.size > 1 else 1
     if step < 1 or (idx.size > 1 and not (np.diff(idx) == step).all()):
-        _refuse(who, "the sample indices must be an arithmetic progression first, first + step, ... with step >= 1 "
-                     "(the device call takes first and step)")
+        refuse(who, "the sample indices must be an arithmetic progression first, first + step, ... with step >= 1 "
+                    "(the device call takes first and step)")
     if first < 0 or int(idx[-1]) >= stored:
-        _refuse(who, "sample indices %d .. %d lie outside the %d stored samples" % (first, int(idx[-1]), stored))
+        refuse(who, "sample indices %d .. %d lie outside the %d stored samples" % (first, int(idx[-1]), stored))
     return first, step, int(idx.size)
-
-
-def _list(who, shape, rows, cols):
-    lists = []
-    for name, a in (("rows", rows), ("cols", cols)):
-        a = np.asarray(a)
-        if a.ndim != 1:
-            _refuse(who, "%s is one-dimensional, not %d-dimensional" % (name, a.ndim))
-        if a.size and not np.issubdtype(a.dtype, np.integer):
-            _refuse(who, "%s holds integers, not %s" % (name, a.dtype))
-        lists.append(a)
-    rows, cols = lists
-    if len(rows) != len(cols):
-        _refuse(who, "rows and cols have different lengths: %d and %d" % (len(rows), len(cols)))
-    if len(rows) == 0:
-        _refuse(who, "the list of entries is empty")
-    if len(rows) >= 2 ** 31:
-        _refuse(who, "at most 2^31 - 1 entries (%d given)" % len(rows))
-    bad = (rows < 0) | (rows >= shape[0]) | (cols < 0) | (cols >= shape[1])
-    if bad.any():
-        e = int(np.flatnonzero(bad)[0])
-        _refuse(who, "entry %d (%d, %d) lies outside the %d x %d matrix" % (e, rows[e], cols[e], shape[0], shape[1]))
-    return np.ascontiguousarray(rows, dtype=np.int32), np.ascontiguousarray(cols, dtype=np.int32)
 
 
 def _compute(who, factors, taus, shape, rows, cols, indices, device, chunk_samples):
     if len(factors) not in (2, 3):
-        _refuse(who, "factors is (all_A, all_B) or (all_A, all_S, all_B), not %d arrays" % len(factors))
+        refuse(who, "factors is (all_A, all_B) or (all_A, all_S, all_B), not %d arrays" % len(factors))
     I, J = int(shape[0]), int(shape[1])
     stored = len(factors[0])
     if stored == 0:
-        _refuse(who, "no stored samples")
+        refuse(who, "no stored samples")
     if any(len(f) != stored for f in factors):
-        _refuse(who, "the sample arrays hold different numbers of samples: %s" % ", ".join(str(len(f)) for f in factors))
+        refuse(who, "the sample arrays hold different numbers of samples: %s" % ", ".join(str(len(f)) for f in factors))
     first, step, T = _progression(who, indices, stored)
-    rows, cols = _list(who, (I, J), rows, cols)
+    rows, cols = entry_lists(who, (I, J), rows, cols)
     if int(chunk_samples) < 0:
-        _refuse(who, "chunk_samples >= 0 (0: the library's default), not %d" % chunk_samples)
+        refuse(who, "chunk_samples >= 0 (0: the library's default), not %d" % chunk_samples)
     # the samples in their own precision; what is no contiguous fp32 array is cast -- its selected samples only
     stop = first + (T - 1) * step + 1
     if all(isinstance(f, np.ndarray) and f.dtype == np.float32 and f.flags["C_CONTIGUOUS"] for f in factors):
@@ -106,17 +79,17 @@ def _compute(who, factors, taus, shape, rows, cols, indices, device, chunk_sampl
         c_first, c_step = 0, 1
     A, S, B = arrays[0], (arrays[1] if len(arrays) == 3 else None), arrays[-1]
     if any(a.ndim != 3 for a in arrays):
-        _refuse(who, "every sample array is three-dimensional [samples][rows][columns], not %s" % ", ".join(str(a.shape) for a in arrays))
+        refuse(who, "every sample array is three-dimensional [samples][rows][columns], not %s" % ", ".join(str(a.shape) for a in arrays))
     K = A.shape[2]
     L = S.shape[2] if S is not None else 0
     W = L if S is not None else K
     if A.shape[1] != I or B.shape[1] != J or B.shape[2] != W or (S is not None and S.shape[1] != K):
-        _refuse(who, "sample arrays of shapes %s do not belong to a %d x %d matrix" % (", ".join(str(a.shape[1:]) for a in arrays), I, J))
+        refuse(who, "sample arrays of shapes %s do not belong to a %d x %d matrix" % (", ".join(str(a.shape[1:]) for a in arrays), I, J))
     if not (1 <= K <= MAX_RANK) or (S is not None and not (1 <= L <= MAX_RANK)):
-        _refuse(who, "ranks 1 .. %d (K=%d, L=%d)" % (MAX_RANK, K, L))
+        refuse(who, "ranks 1 .. %d (K=%d, L=%d)" % (MAX_RANK, K, L))
     taus = np.asarray(taus, dtype=np.float64)
     if taus.ndim != 1 or len(taus) < stop:
-        _refuse(who, "taus holds a value per stored sample, not %s" % (taus.shape,))
+        refuse(who, "taus holds a value per stored sample, not %s" % (taus.shape,))
     noise = float(np.mean(1.0 / taus[first:stop:step]))
 
     n = len(rows)
@@ -124,10 +97,7 @@ def _compute(who, factors, taus, shape, rows, cols, indices, device, chunk_sampl
     _lib.check(_lib.lib().bnmtf_predictive_samples(int(device), I, J, int(K), int(L), C.c_uint64(n), _lib.ptr(rows), _lib.ptr(cols),
                                                    _lib.ptr(A), _lib.ptr(S), _lib.ptr(B), C.c_uint64(c_first), C.c_uint64(c_step), int(T),
                                                    int(chunk_samples), _lib.ptr(p_first), _lib.ptr(sum_d), _lib.ptr(sum_d2)))
-    # shifted by the first sample: a spread far below the mean survives fp64
-    md = sum_d / T
-    mean = p_first + md
-    variance = np.maximum(0.0, sum_d2 / T - md * md)
+    mean, variance = shifted_moments(p_first, sum_d, sum_d2, T)
     return Predictive(rows, cols, mean, variance, noise, T)
 
 
@@ -144,37 +114,25 @@ def posterior_predictive(model, at, burn_in, thinning, *, device=None):
     and the mean noise variance 1 / tau over the same samples: a Predictive (see the module's text).  model: a
     bnmf_gibbs_optimised or bnmtf_gibbs_optimised that has run with store_samples=True, either layout, any rank; at: an Entries of
     the model's shape (its values are ignored) or (rows, cols), any order, repeats allowed; device: defaults to the model's."""
-    from ._sampler import GibbsSampler, ICMRules
-    from ._variational import Variational
-    from .nmf_np import NPDevice
     who = type(model).__name__ + ": posterior_predictive"
-    if isinstance(model, Variational):
-        _refuse(who, "a variational model has no posterior samples: its predictive variance is a closed form of q, not a sample "
-                     "statistic, and is out of scope here (bnmf_gibbs_optimised and bnmtf_gibbs_optimised are taken)")
-    if isinstance(model, (ICMRules, NPDevice)):
-        _refuse(who, "a point estimate has no posterior samples (bnmf_gibbs_optimised and bnmtf_gibbs_optimised are taken)")
-    if not isinstance(model, GibbsSampler):
-        _refuse(who, "not a bnmf_gibbs_optimised or bnmtf_gibbs_optimised")
-    names = ["all_" + f for f in model._FACTORS]
-    if not all(hasattr(model, a) for a in names + ["all_tau"]):
-        _refuse(who, "no stored samples: run() has not been called")
-    stored = len(getattr(model, names[0]))
-    if stored == 0:
-        _refuse(who, "no stored samples: the last run() was called with store_samples=False")
-    burn_in, thinning = int(burn_in), int(thinning)
-    if thinning < 1:
-        _refuse(who, "thinning >= 1, not %d" % thinning)
-    if not (0 <= burn_in < stored):
-        _refuse(who, "burn_in must lie below the number of stored samples (burn_in=%d, %d stored)" % (burn_in, stored))
+    kind = kind_of(model)
+    if kind == 'variational':
+        refuse(who, "a variational model has no posterior samples: its predictive variance is a closed form of q, not a sample "
+                    "statistic, and is out of scope here (bnmf_gibbs_optimised and bnmtf_gibbs_optimised are taken)")
+    if kind in ('icm', 'np'):
+        refuse(who, "a point estimate has no posterior samples (bnmf_gibbs_optimised and bnmtf_gibbs_optimised are taken)")
+    if kind != 'gibbs':
+        refuse(who, "not a bnmf_gibbs_optimised or bnmtf_gibbs_optimised")
+    names, stored, burn_in, thinning = stored_samples(who, model, burn_in, thinning)
     shape = (int(model.I), int(model.J))
     if isinstance(at, Entries):
         if tuple(at.shape) != shape:
-            _refuse(who, "the Entries and the model's matrix have different shapes: %s and %s" % (tuple(at.shape), shape))
+            refuse(who, "the Entries and the model's matrix have different shapes: %s and %s" % (tuple(at.shape), shape))
         rows, cols = at.rows, at.cols
     else:
         try:
             rows, cols = at
         except (TypeError, ValueError):
-            _refuse(who, "at is an Entries or a pair (rows, cols), not %s" % type(at).__name__)
+            refuse(who, "at is an Entries or a pair (rows, cols), not %s" % type(at).__name__)
     return _compute(who, [getattr(model, a) for a in names], model.all_tau, shape, rows, cols, range(burn_in, stored, thinning),
-                    model._device if device is None else device, 0)
+                    device_of(model, device), 0)

@@ -26,7 +26,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, _observed
-from ._lib import BnmtfError
+from ._postfit import device_of, entry_lists, factors_fit, index_list, model_factors, refuse
 from .entries import Entries
 
 MAX_N = 128             # BNMTF_TOP_MAX_N
@@ -54,86 +54,64 @@ class TopEntries(object):
         return (other, own) if self.axis == 1 else (own, other)
 
 
-def _refuse(who, why):
-    raise BnmtfError("%s: %s" % (who, why))
-
-
-def _index_list(who, name, a):
-    a = np.asarray(a)
-    if a.ndim != 1:
-        _refuse(who, "%s is one-dimensional, not %d-dimensional" % (name, a.ndim))
-    if a.size and not np.issubdtype(a.dtype, np.integer):
-        _refuse(who, "%s holds integers, not %s" % (name, a.dtype))
-    return a
-
-
 def _exclusion(who, shape, exclude):
     """(ex_rows, ex_cols) as int32 lists inside the matrix, or two empty ones"""
     if exclude is None:
         return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
     if isinstance(exclude, Entries):
         if tuple(exclude.shape) != tuple(shape):
-            _refuse(who, "the excluded Entries and the matrix have different shapes: %s and %s" % (tuple(exclude.shape), tuple(shape)))
+            refuse(who, "the excluded Entries and the matrix have different shapes: %s and %s" % (tuple(exclude.shape), tuple(shape)))
         return exclude.rows, exclude.cols
     if isinstance(exclude, str):
-        _refuse(who, "exclude is 'observed' (a model's training entries), None, an Entries or a pair (rows, cols), not %r" % exclude)
+        refuse(who, "exclude is 'observed' (a model's training entries), None, an Entries or a pair (rows, cols), not %r" % exclude)
     try:
         er, ec = exclude
     except (TypeError, ValueError):
-        _refuse(who, "exclude is 'observed' (a model's training entries), None, an Entries or a pair (rows, cols), not %s" % type(exclude).__name__)
-    er, ec = _index_list(who, "the excluded rows", er), _index_list(who, "the excluded cols", ec)
-    if len(er) != len(ec):
-        _refuse(who, "the excluded rows and cols have different lengths: %d and %d" % (len(er), len(ec)))
-    if len(er) >= 2 ** 32:
-        _refuse(who, "at most 2^32 - 1 excluded entries (%d given)" % len(er))
-    bad = (er < 0) | (er >= shape[0]) | (ec < 0) | (ec >= shape[1])
-    if bad.any():
-        e = int(np.flatnonzero(bad)[0])
-        _refuse(who, "excluded entry %d (%d, %d) lies outside the %d x %d matrix" % (e, er[e], ec[e], shape[0], shape[1]))
-    return np.ascontiguousarray(er, dtype=np.int32), np.ascontiguousarray(ec, dtype=np.int32)
+        refuse(who, "exclude is 'observed' (a model's training entries), None, an Entries or a pair (rows, cols), not %s" % type(exclude).__name__)
+    return entry_lists(who, shape, er, ec, noun="excluded ", bits=32, empty=True)
 
 
 def _compute(who, factors, n, rows, exclude, largest, device, split, axis=0):
     if len(factors) not in (2, 3):
-        _refuse(who, "factors is (A, B) or (A, S, B), not %d arrays" % len(factors))
+        refuse(who, "factors is (A, B) or (A, S, B), not %d arrays" % len(factors))
     arrays = [np.ascontiguousarray(f, dtype=np.float64) for f in factors]
     if any(a.ndim != 2 for a in arrays):
-        _refuse(who, "every factor is two-dimensional, not %s" % ", ".join(str(a.shape) for a in arrays))
+        refuse(who, "every factor is two-dimensional, not %s" % ", ".join(str(a.shape) for a in arrays))
     A, S, B = arrays[0], (arrays[1] if len(arrays) == 3 else None), arrays[-1]
     I, K = A.shape
     J, W = B.shape
     L = S.shape[1] if S is not None else 0
     if I < 1 or J < 1 or (S is None and W != K) or (S is not None and (S.shape[0] != K or W != L)):
-        _refuse(who, "factor arrays of shapes %s do not fit each other: (A [I][K], B [J][K]) or (A [I][K], S [K][L], B [J][L])"
+        refuse(who, "factor arrays of shapes %s do not fit each other: (A [I][K], B [J][K]) or (A [I][K], S [K][L], B [J][L])"
                 % ", ".join(str(a.shape) for a in arrays))
     if not (1 <= K <= MAX_RANK) or (S is not None and not (1 <= L <= MAX_RANK)):
-        _refuse(who, "ranks 1 .. %d (K=%d, L=%d)" % (MAX_RANK, K, L))
+        refuse(who, "ranks 1 .. %d (K=%d, L=%d)" % (MAX_RANK, K, L))
     try:
         n_int = int(n)
     except (TypeError, ValueError):
-        _refuse(who, "n is an integer 1 .. %d (BNMTF_TOP_MAX_N), not %r" % (MAX_N, n))
+        refuse(who, "n is an integer 1 .. %d (BNMTF_TOP_MAX_N), not %r" % (MAX_N, n))
     if n_int != n or not (1 <= n_int <= MAX_N):
-        _refuse(who, "n is an integer 1 .. %d (BNMTF_TOP_MAX_N), not %r" % (MAX_N, n))
+        refuse(who, "n is an integer 1 .. %d (BNMTF_TOP_MAX_N), not %r" % (MAX_N, n))
     split = int(split)
     if split < 0 or split > 1024:
-        _refuse(who, "0 <= split <= 1024 column segments per row (0: the library chooses), not %d" % split)
+        refuse(who, "0 <= split <= 1024 column segments per row (0: the library chooses), not %d" % split)
     for name, a in (("A", A), ("S", S), ("B", B)):
         if a is not None and not np.isfinite(a).all():
-            _refuse(who, "factor %s holds a value that is not finite (the total order needs finite scores)" % name)
+            refuse(who, "factor %s holds a value that is not finite (the total order needs finite scores)" % name)
     if rows is None:
         sel = np.arange(I, dtype=np.int32)
     else:
-        sel = _index_list(who, "rows", rows)
+        sel = index_list(who, "rows", rows)
         if sel.size == 0:
-            _refuse(who, "rows is empty (None: all rows)")
+            refuse(who, "rows is empty (None: all rows)")
         bad = (sel < 0) | (sel >= I)
         if bad.any():
             e = int(np.flatnonzero(bad)[0])
-            _refuse(who, "rows[%d] = %d lies outside the %d rows" % (e, sel[e], I))
+            refuse(who, "rows[%d] = %d lies outside the %d rows" % (e, sel[e], I))
         uniq, first = np.unique(sel, return_index=True)
         if len(uniq) != len(sel):
             twice = int(sel[np.setdiff1d(np.arange(len(sel)), first)[0]])
-            _refuse(who, "rows holds distinct indices: %d occurs twice" % twice)
+            refuse(who, "rows holds distinct indices: %d occurs twice" % twice)
         sel = np.ascontiguousarray(sel, dtype=np.int32)
     er, ec = _exclusion(who, (I, J), exclude)
 
@@ -153,49 +131,8 @@ def from_factors(factors, n, *, rows=None, exclude=None, largest=True, device=0,
     fp64); exclude: None, an Entries of shape (I, J) or a pair (rows, cols); split: column segments per row, each taken by a wave
     of its own (0: the library chooses; the answer's bytes do not depend on it).  Returns a TopEntries."""
     if isinstance(exclude, str):
-        _refuse("top_entries.from_factors", "exclude is None, an Entries or a pair (rows, cols): plain factors have no training entries (%r)" % exclude)
+        refuse("top_entries.from_factors", "exclude is None, an Entries or a pair (rows, cols): plain factors have no training entries (%r)" % exclude)
     return _compute("top_entries.from_factors", factors, n, rows, exclude, largest, device, split)
-
-
-def _model_factors(who, model, burn_in, thinning):
-    """the factors the class's predict() multiplies, in the order (A, B) or (A, S, B)"""
-    from ._sampler import GibbsSampler, ICMRules
-    from ._variational import Variational
-    from .nmf_np import NPDevice
-    gibbs = isinstance(model, GibbsSampler) and not isinstance(model, ICMRules)
-    if not gibbs:
-        if not isinstance(model, (GibbsSampler, Variational, NPDevice)):
-            _refuse(who, "not a model of this package")
-        if burn_in is not None or thinning is not None:
-            _refuse(who, "burn_in and thinning select the samples of a Gibbs model (bnmf_gibbs_optimised, bnmtf_gibbs_optimised); "
-                         "this class has one estimate and takes neither")
-        if isinstance(model, Variational):
-            names = ["exp" + f for f in model._FACTORS]
-            if not all(hasattr(model, a) for a in names):
-                _refuse(who, "no factors yet: initialise() has not been called")
-            return [getattr(model, a) for a in names]
-        try:
-            return list(model._factors())
-        except AttributeError:
-            _refuse(who, "no factors yet: initialise() has not been called")
-    # a Gibbs model: posterior_predictive's checks and texts
-    if burn_in is None or thinning is None:
-        _refuse(who, "burn_in and thinning are required for a Gibbs model: they select the samples whose mean is ranked "
-                     "(approx_expectation(burn_in, thinning))")
-    names = ["all_" + f for f in model._FACTORS]
-    if not all(hasattr(model, a) for a in names + ["all_tau"]):
-        _refuse(who, "no stored samples: run() has not been called")
-    stored = len(getattr(model, names[0]))
-    if stored == 0:
-        _refuse(who, "no stored samples: the last run() was called with store_samples=False")
-    burn_in, thinning = int(burn_in), int(thinning)
-    if thinning < 1:
-        _refuse(who, "thinning >= 1, not %d" % thinning)
-    if not (0 <= burn_in < stored):
-        _refuse(who, "burn_in must lie below the number of stored samples (burn_in=%d, %d stored)" % (burn_in, stored))
-    # what predict(M_pred, burn_in, thinning) multiplies: the mean of the stored samples, formed on the host in fp64 (only a model
-    # whose last run() was given expectation=(burn_in, thinning) answers from its handle's sums instead, as it does for predict())
-    return list(model.approx_expectation(burn_in, thinning)[:-1])
 
 
 def top_entries(model, n, *, burn_in=None, thinning=None, rows=None, axis=0, largest=True, exclude='observed', device=None):
@@ -207,25 +144,20 @@ def top_entries(model, n, *, burn_in=None, thinning=None, rows=None, axis=0, lar
     device: defaults to the model's."""
     who = type(model).__name__ + ": top_entries"
     if axis not in (0, 1):
-        _refuse(who, "axis is 0 (per row the best columns) or 1 (per column the best rows), not %r" % (axis,))
-    factors = _model_factors(who, model, burn_in, thinning)
+        refuse(who, "axis is 0 (per row the best columns) or 1 (per column the best rows), not %r" % (axis,))
+    factors = model_factors(who, model, burn_in, thinning)
     shape = (int(model.I), int(model.J))
-    shapes = [np.shape(f) for f in factors]
-    if len(shapes[0]) != 2 or len(shapes[-1]) != 2 or shapes[0][0] != shape[0] or shapes[-1][0] != shape[1]:
-        _refuse(who, "factor arrays of shapes %s do not fit each other and the %d x %d matrix" % (", ".join(str(s) for s in shapes), shape[0], shape[1]))
+    factors_fit(who, factors, shape[0], shape[1], each_other=False)           # (_compute checks the inner dimensions, with its own text)
     if isinstance(exclude, str):
         if exclude != 'observed':
-            _refuse(who, "exclude is 'observed' (the model's training entries), None, an Entries or a pair (rows, cols), not %r" % exclude)
+            refuse(who, "exclude is 'observed' (the model's training entries), None, an Entries or a pair (rows, cols), not %r" % exclude)
         er, ec = _observed.entries_of(model)[:2]
     else:
         er, ec = _exclusion(who, shape, exclude)
     if axis == 1:                       # the swapped problem: (B, A), or (G, S^T, F), and the exclusion transposed
         factors = [factors[-1]] + ([np.asarray(factors[1]).T] if len(factors) == 3 else []) + [factors[0]]
         er, ec = ec, er
-    dev = device
-    if dev is None:
-        dev = getattr(model, "_device", 0)
-    return _compute(who, factors, n, rows, (er, ec), largest, dev, 0, axis)
+    return _compute(who, factors, n, rows, (er, ec), largest, device_of(model, device), 0, axis)
 
 
 top_entries.from_factors = from_factors          # (the package exports the function under the module's name: bnmtf_amd.top_entries.from_factors)

@@ -272,7 +272,10 @@ def test_header_exports_map_and_binding_list_the_new_entry_points():
     assert api.count('#include "api_foldin.inc"') == 1 and api.index('#include "api_foldin.inc"') > api.index('#include "api_top.inc"')
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert re.search(r"^SRCS = .*\bkernel_foldin\.hip\b", mk, flags=re.M) and re.search(r"^asan_foldin:", mk, flags=re.M)
-    assert mk.count("api_predictive.inc api_top.inc api_foldin.inc ") == mk.count("api_top.inc ") == 3        # every dependency list names it
+    deps = re.search(r"^APIDEPS = (.*)$", mk, flags=re.M).group(1).split()
+    assert {"api_predictive.inc", "api_top.inc", "api_foldin.inc"} <= set(deps)                      # every dependency list names it
+    for rule in (r"build/%\.o", r"build/san/%_asan\.o", r"build/san/%_tsan\.o"):
+        assert re.search(r"^%s: %%\.hip \$\(APIDEPS\)" % rule, mk, flags=re.M), rule
     kh = open(os.path.join(CSRC, "kernels.h")).read()
     assert re.search(r"\bkStreamFoldIn = 4\b", kh) and re.search(r"constexpr int kFoldInMaxRank = 256;", kh)
 

@@ -282,7 +282,10 @@ def test_header_exports_map_and_binding_list_the_new_entry_points():
     assert api.count('#include "api_top.inc"') == 1 and api.index('#include "api_top.inc"') > api.index('#include "api_many.inc"')
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert re.search(r"^SRCS = .*\bkernel_top\.hip\b", mk, flags=re.M) and re.search(r"^asan_top:", mk, flags=re.M)
-    assert mk.count("api_predictive.inc api_top.inc") == mk.count("api_predictive.inc ") == 3       # every dependency list names it
+    deps = re.search(r"^APIDEPS = (.*)$", mk, flags=re.M).group(1).split()
+    assert "api_predictive.inc" in deps and "api_top.inc" in deps                                    # every dependency list names it
+    for rule in (r"build/%\.o", r"build/san/%_asan\.o", r"build/san/%_tsan\.o"):
+        assert re.search(r"^%s: %%\.hip \$\(APIDEPS\)" % rule, mk, flags=re.M), rule
 
 
 def test_the_c_call_answers_null_pointers_and_bad_limits_with_an_error_code():
