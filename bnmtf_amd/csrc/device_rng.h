@@ -100,6 +100,22 @@ __device__ __forceinline__ float tn_draw_serial(float mu, float tau_p, uint32_t 
   return 0.0f;
 }
 
+// Wave form (one 64-lane wave per draw, every lane calls it with the same arguments but its own lane): up to 64 rounds of 64
+// candidates, candidate round * 64 + lane on the lane, the first accepted one in candidate order -- what the serial form returns.
+// 0 when nothing is accepted or the parameters are not live.
+__device__ __forceinline__ float tn_draw_wave(const TnParams& p, uint32_t elem, uint32_t col, uint32_t it, uint32_t stream,
+                                              int lane, uint32_t k0, uint32_t k1) {
+  if (!p.live) return 0.0f;
+#pragma unroll 1
+  for (uint32_t round = 0; round < 64u; ++round) {
+    float xc;
+    const bool acc = tn_candidate(p, elem, col, it, stream, round * 64u + (uint32_t)lane, k0, k1, &xc);
+    const unsigned long long m = __ballot(acc);
+    if (m) return tn_guard(__shfl(xc, __ffsll((long long)m) - 1, 64));
+  }
+  return 0.0f;
+}
+
 // Gamma(shape, 1) by Marsaglia-Tsang in fp64 (one thread).  The variate depends on (shape, seed, iteration) only --
 // not on the rate -- so run() computes it on the host ahead of the iteration and the device divides by the rate.
 __host__ __device__ inline double gamma_unit_draw(double shape, uint32_t it, uint32_t stream, uint32_t k0, uint32_t k1) {

@@ -17,7 +17,8 @@
 //            then e -= delta v.  A kept sweep adds x to the statistics, lane l those of columns l, l + 64, l + 128, l + 192, in fp64:
 //            the first kept x, sum d and sum d^2 with d = x - first (exact in fp64), in sweep order (kernel_predictive.hip's shifted
 //            form; the host makes the two divisions).  The sweep's x goes to samples[t][u][.] when asked for, lanes along k.
-// Two forms of the same arithmetic, as in kernel_obs.hip.  A unit of at most kFoldInMaxSlots x 64 entries keeps e, j and v in
+// Two forms of the same arithmetic, under obs_common.h's contract, in this file's own loops (written on ObsForm the kernel took
+// 128 / 120 VGPRs for 126 / 118 and ran 2 to 3 % longer on batches of 1 and 256 units; the draw loop is this file's own too).  A unit of at most kFoldInMaxSlots x 64 entries keeps e, j and v in
 // registers: S slots per lane, S = 1, 2, 4, 8 by the unit's entry count (wave-uniform).  A slot without an entry holds e = 0 and the
 // index m, where the transposed factor keeps a zero behind every column (ldT > m): it adds +0 to sums that are never -0.  A longer
 // unit keeps e in a global scratch array at the entry's own list position and gathers j and v again.  Both run the same operations

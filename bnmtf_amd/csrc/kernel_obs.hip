@@ -15,12 +15,8 @@
 //            wave (every lane ends with the same bits), the wave-uniform conditional, the candidates of a draw 64 at a time across
 //            the lanes -- Philox counter (unit, column, iteration, stream | candidate), first accepted candidate: oracle/rng.py's
 //            chain, as sweep_generic_kernel draws it -- then e -= delta v.
-// Two forms of the same arithmetic.  A unit of at most kObsMaxSlots x 64 entries keeps e, j and v in registers: S slots per lane,
-// S = 1, 2, 4, 8 by the unit's entry count (wave-uniform).  A slot without an entry holds e = 0 and the inner index m, where the
-// transposed factor keeps a zero behind every column (ld > m): it adds +0 to sums that are never -0, so no per-slot predicate lives
-// across the column loop.  A longer unit keeps e in a global scratch array at the entry's own list position and gathers j and v
-// again.  Both run the same operations on the same operands in the same order (explicit fmaf, contraction off), so a unit's result
-// does not depend on the form: ObsSweepArgs::force_long sends every unit down the long one.
+// Every per-entry loop is written once, on the unit's two forms (obs_common.h, "the contract": registers for a unit of at most
+// kObsMaxSlots x 64 entries, escratch behind that or under ObsSweepArgs::force_long; the same bits either way).
 // End of the iteration (the V half sweep, part != null): per lane SSE = sum e^2, sum P, sum P^2, sum R P with P = R - e, fp64, in
 // entry order; butterfly; the block's waves in wave order; obs_finish_kernel folds the blocks' partials -- thread t the blocks t,
 // t + 256, ..., then a tree -- and makes tau and the record as finish_kernel does.  No floating-point atomics anywhere.
@@ -34,31 +30,19 @@ namespace bnmtf {
 
 namespace {
 
-// One unit.  S > 0: the register form with S slots per lane; S == 0: the long form.  xs / ls: the unit's factor row and prior
-// rates in LDS.  sums (part != null): the lane's share of SSE, sum P, sum P^2, sum R P.
+// One unit in the form S (obs_common.h).  xs / ls: the unit's factor row and prior rates in LDS.  sums (part != null): the lane's
+// share of SSE, sum P, sum P^2, sum R P.
 template <int S, int MODE>
 __device__ __forceinline__ void obs_unit(const ObsSweepArgs& a, int u, int lane, float* xs, const float* ls, double* sums) {
 #pragma clang fp contract(off)
-  constexpr int SS = S > 0 ? S : 1;
-  const uint32_t beg = a.ptr[u], cnt = a.ptr[u + 1] - beg;
-  const uint32_t* idx = a.idx + beg;
-  const float* val = a.val + beg;
-  float* es = a.escratch + beg;
+  ObsForm<S> F(a.ptr, a.idx, a.val, a.escratch, u, lane);
   const int K = a.K, KP = a.KP;
-  float e[SS], v[SS];
-  uint32_t jj[SS];
 
   // ---- phase 1: the residual of every entry
-  if (S > 0) {
-#pragma unroll
-    for (int s = 0; s < SS; ++s) {
-      const uint32_t t = (uint32_t)(s * 64 + lane);
-      e[s] = 0.f; v[s] = 0.f; jj[s] = (uint32_t)a.m;                 // (a slot without an entry: the zero word behind the other factor's columns)
-      if (t < cnt) { jj[s] = idx[t]; e[s] = obs_residual(xs, a.Xo, KP, jj[s], val[t]); }
-    }
-  } else {
-    for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) es[t] = obs_residual(xs, a.Xo, KP, idx[t], val[t]);
-  }
+  F.init((uint32_t)a.m, 0.f);
+  F.each([&](int s, uint32_t t) __attribute__((always_inline)) {
+    if (F.has(t)) F.E(s, t) = obs_residual(xs, a.Xo, KP, F.J(s, t), F.val[t]);
+  });
 
   // ---- phase 2: the columns
   const float tau = *a.tau;
@@ -67,12 +51,12 @@ __device__ __forceinline__ void obs_unit(const ObsSweepArgs& a, int u, int lane,
   for (int k = kbeg; k < kend; ++k) {
     const float* vcol = a.XoT + (size_t)k * a.ldT_o;
     float se = 0.f, sa = 0.f;
-    if (S > 0) {
-#pragma unroll
-      for (int s = 0; s < SS; ++s) { v[s] = vcol[jj[s]]; se = fmaf(e[s], v[s], se); sa = fmaf(v[s], v[s], sa); }
-    } else {
-      for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) { const float vv = vcol[idx[t]]; se = fmaf(es[t], vv, se); sa = fmaf(vv, vv, sa); }
-    }
+    F.each([&](int s, uint32_t t) __attribute__((always_inline)) {
+      const float vv = F.hold(s, vcol[F.J(s, t)]);
+      // (two independent sums; in this order the compiler pairs them so that the long form's load of e is issued beside the
+      // index's and not behind it -- 3 to 8 % of a half sweep of long units)
+      sa = fmaf(vv, vv, sa); se = fmaf(F.E(s, t), vv, se);
+    });
     se = wave_sum(se); sa = wave_sum(sa);
     const float xk = xs[k];
     const float num = fmaf(xk, sa, se);
@@ -85,30 +69,17 @@ __device__ __forceinline__ void obs_unit(const ObsSweepArgs& a, int u, int lane,
     const float mu = numer / tau_p;
     float xnew = 0.f;
     if (MODE == kSweepDraw) {
-      const TnParams tp = tn_params(mu, tau_p);
       // the key and the iteration word in vector registers: as wave-uniform values the compiler keeps the ten round keys of
       // Philox in scalar registers across the column loop, more than there are (seen as scalar spills in tools/kres.sh)
       uint32_t k0 = a.key0, k1 = a.key1, itw = a.it;
       asm volatile("" : "+v"(k0), "+v"(k1), "+v"(itw));
-      if (tp.live) {
-        for (uint32_t round = 0; round < 64u; ++round) {
-          float xc;
-          const bool acc = tn_candidate(tp, (uint32_t)u, (uint32_t)k, itw, a.stream, round * 64u + (uint32_t)lane, k0, k1, &xc);
-          const unsigned long long m = __ballot(acc);
-          if (m) { xnew = tn_guard(__shfl(xc, __ffsll((long long)m) - 1, 64)); break; }
-        }
-      }
+      xnew = tn_draw_wave(tn_params(mu, tau_p), (uint32_t)u, (uint32_t)k, itw, a.stream, lane, k0, k1);
     } else {
       xnew = fmaxf((tau_p > 0.f && mu > 0.f) ? mu : 0.f, a.min_x);
     }
     const float nd = xk - xnew;                 // e -= (x' - x) v
     xs[k] = xnew;                               // (every lane stores the same value, and reads back its own store)
-    if (S > 0) {
-#pragma unroll
-      for (int s = 0; s < SS; ++s) e[s] = fmaf(nd, v[s], e[s]);
-    } else {
-      for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) es[t] = fmaf(nd, vcol[idx[t]], es[t]);
-    }
+    F.each([&](int s, uint32_t t) __attribute__((always_inline)) { F.E(s, t) = fmaf(nd, F.V(s, t, vcol), F.E(s, t)); });
   }
 
   // ---- the unit's new row: row major, transposed, and packed into the sample slot
@@ -124,21 +95,12 @@ __device__ __forceinline__ void obs_unit(const ObsSweepArgs& a, int u, int lane,
   // ---- end of the iteration: the lane's sums over its entries, in entry order
   if (a.part) {
     double sse = 0.0, sp = 0.0, spp = 0.0, srp = 0.0;
-    if (S > 0) {
-#pragma unroll
-      for (int s = 0; s < SS; ++s) {
-        const uint32_t t = (uint32_t)(s * 64 + lane);
-        if (t < cnt) {
-          const double ed = (double)e[s], r = (double)val[t], p = r - ed;
-          sse = fma(ed, ed, sse); sp += p; spp = fma(p, p, spp); srp = fma(r, p, srp);
-        }
-      }
-    } else {
-      for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) {
-        const double ed = (double)es[t], r = (double)val[t], p = r - ed;
+    F.each([&](int s, uint32_t t) __attribute__((always_inline)) {
+      if (F.has(t)) {
+        const double ed = (double)F.E(s, t), r = (double)F.val[t], p = r - ed;
         sse = fma(ed, ed, sse); sp += p; spp = fma(p, p, spp); srp = fma(r, p, srp);
       }
-    }
+    });
     sums[0] = sse; sums[1] = sp; sums[2] = spp; sums[3] = srp;
   }
 }
@@ -147,38 +109,24 @@ template <int MODE>
 __global__ __launch_bounds__(kObsWaves * 64) void obs_sweep_kernel(ObsSweepArgs a) {
   __shared__ float xsh[kObsWaves][kObsMaxRank];
   __shared__ float lsh[kObsWaves][kObsMaxRank];
-  __shared__ double red[kObsWaves][4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int u = blockIdx.x * kObsWaves + wave;
   const bool ok = u < a.n;
   float* xs = xsh[wave];
   float* ls = lsh[wave];
-  if (ok)
-    for (int k = lane; k < a.KP; k += 64) {
-      xs[k] = k < a.K ? a.X[(size_t)u * a.KP + k] : 0.f;
-      ls[k] = k < a.K ? a.lambda[(size_t)u * a.KP + k] : 0.f;
-    }
+  if (ok) {
+    obs_stage_row(xs, a.X + (size_t)u * a.KP, a.K, a.KP, lane);
+    obs_stage_row(ls, a.lambda + (size_t)u * a.KP, a.K, a.KP, lane);
+  }
   __syncthreads();
   double sums[4] = {0.0, 0.0, 0.0, 0.0};
-  if (ok) {
-    const uint32_t cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.ptr[u + 1] - a.ptr[u]));
-    if (a.force_long || cnt > (uint32_t)kObsMaxSlots * 64u) obs_unit<0, MODE>(a, u, lane, xs, ls, sums);
-    else if (cnt <= 64u) obs_unit<1, MODE>(a, u, lane, xs, ls, sums);
-    else if (cnt <= 128u) obs_unit<2, MODE>(a, u, lane, xs, ls, sums);
-    else if (cnt <= 256u) obs_unit<4, MODE>(a, u, lane, xs, ls, sums);
-    else obs_unit<8, MODE>(a, u, lane, xs, ls, sums);
-  }
+  if (ok)
+    obs_dispatch<kObsMaxSlots>(obs_count(a.ptr, u), a.force_long, [&](auto form) __attribute__((always_inline)) {
+      obs_unit<decltype(form)::value, MODE>(a, u, lane, xs, ls, sums);
+    });
   if (a.part) {                      // (wave-uniform, and the same in every wave: all of them reach the barrier)
-#pragma unroll
-    for (int m = 0; m < 4; ++m) sums[m] = wave_sum_d(sums[m]);
-    if (lane == 0)
-      for (int m = 0; m < 4; ++m) red[wave][m] = sums[m];
-    __syncthreads();
-    if (threadIdx.x < 4) {
-      double s = 0.0;
-      for (int w = 0; w < kObsWaves; ++w) s += red[w][threadIdx.x];
-      a.part[(size_t)blockIdx.x * 4 + threadIdx.x] = s;
-    }
+    const double s = obs_block_sums<4, kObsWaves>(sums, 4);
+    if (threadIdx.x < 4) a.part[(size_t)blockIdx.x * 4 + threadIdx.x] = s;
   }
 }
 
@@ -207,7 +155,6 @@ __global__ __launch_bounds__(256) void obs_finish_kernel(ObsFinishArgs a) {
 }
 
 __global__ __launch_bounds__(256) void obs_metric_kernel(ObsMetricArgs a) {
-  __shared__ double red[6][256];
   const int tid = threadIdx.x;
   double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   const size_t stride = (size_t)gridDim.x * 256;
@@ -219,19 +166,9 @@ __global__ __launch_bounds__(256) void obs_metric_kernel(ObsMetricArgs a) {
     const double r = (double)a.val[e];
     s[0] += 1.0; s[1] += r; s[2] = fma(r, r, s[2]); s[3] += p; s[4] = fma(p, p, s[4]); s[5] = fma(r, p, s[5]);
   }
-  for (int m = 0; m < 6; ++m) red[m][tid] = s[m];
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (tid < w) for (int m = 0; m < 6; ++m) red[m][tid] += red[m][tid + w];
-    __syncthreads();
-  }
-  if (tid < 8) a.part[(size_t)blockIdx.x * 8 + tid] = tid < 6 ? red[tid][0] : 0.0;
-}
-__global__ __launch_bounds__(256) void obs_metric_fold_kernel(const double* part, int nb, double* out) {
-  double t[8];
-  obs_fold<8>(part, nb, t);
-  if (threadIdx.x == 0)
-    for (int m = 0; m < 8; ++m) out[m] = t[m];
+  obs_tree_sums<6>(s);
+  if (tid == 0)
+    for (int m = 0; m < 8; ++m) a.part[(size_t)blockIdx.x * 8 + m] = m < 6 ? s[m] : 0.0;
 }
 
 }  // namespace
@@ -249,7 +186,7 @@ void launch_obs_finish(const ObsFinishArgs& a, hipStream_t st) {
 void launch_obs_metric(const ObsMetricArgs& a, double* out8, hipStream_t st) {
   const int nb = obs_metric_blocks(a.n);
   hipLaunchKernelGGL(obs_metric_kernel, dim3(nb), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(obs_metric_fold_kernel, dim3(1), dim3(256), 0, st, a.part, nb, out8);
+  hipLaunchKernelGGL(obs_fold_kernel<8>, dim3(1), dim3(256), 0, st, a.part, nb, out8);
 }
 
 }  // namespace bnmtf

@@ -17,21 +17,14 @@
 //
 // Order of the sums (fixed: two runs give the same bits, no floating-point atomics): a lane's entries in list order; a butterfly
 // over the wave; the block's waves in wave order; heldout_fold_kernel (launch_fold) over the blocks' partials.
-#include "kernels.h"
+#include "obs_common.h"
 
 namespace bnmtf {
 
 namespace {
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void obs_heldout_kernel(ObsHeldoutArgs a) {
   __shared__ __attribute__((aligned(16))) double rowf[kObsHeldoutRows][kObsMaxRank];     // the waves' factor rows
-  __shared__ double red[kObsHeldoutRows][6];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x * kObsHeldoutRows + wave;
   const bool row_ok = i < a.I;
@@ -79,17 +72,8 @@ __global__ __launch_bounds__(256) void obs_heldout_kernel(ObsHeldoutArgs a) {
   }
 
   // ---- wave, then block
-#pragma unroll
-  for (int m = 0; m < 6; ++m) s[m] = wave_sum(s[m]);
-  if (lane == 0)
-    for (int m = 0; m < 6; ++m) red[wave][m] = s[m];
-  __syncthreads();
-  if (threadIdx.x < 8) {
-    double v = 0.0;
-    if (threadIdx.x < 6)
-      for (int w = 0; w < kObsHeldoutRows; ++w) v += red[w][threadIdx.x];
-    a.part[(size_t)blockIdx.x * 8 + threadIdx.x] = v;
-  }
+  const double v = obs_block_sums<6, kObsHeldoutRows>(s, 6);
+  if (threadIdx.x < 8) a.part[(size_t)blockIdx.x * 8 + threadIdx.x] = v;           // (0 in the two words of padding)
 }
 
 }  // namespace

@@ -10,15 +10,12 @@
 //   Phase 2  per column: gather v = XoT[k][j], per-lane fp32 partials of sum v (r rcp(p)) and sum v in entry order -- the quotient
 //            as np_sweep_kernel takes it, r times the hardware reciprocal of p --, a butterfly over the wave (every lane ends with
 //            the same bits), x_k' = (float)((double)x_k num / den) in every lane alike, then p += (x_k' - x_k) v.
-// Two forms of the same arithmetic.  A unit of at most kObsMaxSlots x 64 entries keeps p, r, j and v in registers (1, 2, 4 or 8
-// slots per lane); a slot without an entry holds the inner index m -- the zero word behind every transposed column, so v = 0 --,
-// r = 0 and p = 1: it adds +0 to both sums and no per-slot predicate lives across the column loop.  A longer unit keeps p in
-// escratch at the entry's own list position and gathers j, r and v again.  Same operations on the same operands in the same order
-// (explicit fmaf, contraction off): a unit's result does not depend on the form, OnpSweepArgs::force_long sends every unit down
-// the long one.  The single-column form is the same kernel on [k, k + 1); resume / keep hand P from one such call to the next
+// Every per-entry loop is written once, on the unit's two forms (obs_common.h, "the contract"), with P in the place of the
+// residual: the register form keeps p, r, j and v, and a slot without an entry holds r = 0 and p = 1 -- it adds +0 to both sums;
+// OnpSweepArgs::force_long sends every unit down the long form.  The single-column form is the same kernel on [k, k + 1); resume / keep hand P from one such call to the next
 // through escratch, so the columns one by one are the half sweep.
 // End of the iteration (part != null: the V / G half sweep): per lane the eight sums of np_entry_stats from the final P, fp64, in
-// entry order; butterfly; the block's waves in wave order; onp_fold_kernel folds the blocks' partials -- thread t the blocks t,
+// entry order; butterfly; the block's waves in wave order; obs_fold_kernel<8> folds the blocks' partials -- thread t the blocks t,
 // t + 256, ..., then a tree -- into the iteration's record.  No floating-point atomics anywhere.
 //
 // onp_eff_kernel: NMTF's effective factors G S^T and F S, fp32, any K, L <= 256, in both forms.
@@ -34,19 +31,6 @@ namespace bnmtf {
 
 namespace {
 
-// x . Xo_j, the columns in order (the padding columns of both are zero)
-__device__ __forceinline__ float onp_dot(const float* xs, const float* Xo, int KP, uint32_t j) {
-#pragma clang fp contract(off)
-  const float4* row = reinterpret_cast<const float4*>(Xo + (size_t)j * KP);
-  float acc = 0.f;
-  for (int q = 0; q < KP / 4; ++q) {
-    const float4 b = row[q];
-    acc = fmaf(xs[4 * q + 0], b.x, acc); acc = fmaf(xs[4 * q + 1], b.y, acc);
-    acc = fmaf(xs[4 * q + 2], b.z, acc); acc = fmaf(xs[4 * q + 3], b.w, acc);
-  }
-  return acc;
-}
-
 // the eight sums of one observed entry (kernel_np.hip np_entry_stats), fp64
 __device__ __forceinline__ void onp_entry_stats(double* s, double r, double p) {
 #pragma clang fp contract(off)
@@ -56,52 +40,32 @@ __device__ __forceinline__ void onp_entry_stats(double* s, double r, double p) {
   s[7] = fma(d, d, s[7]);
 }
 
-// One unit.  S > 0: the register form with S slots per lane; S == 0: the long form.  xs: the unit's factor row in LDS.
+// One unit in the form S (obs_common.h): the form's e is P, an empty slot holds P = 1 and r = 0.  xs: the unit's factor row in LDS.
 template <int S>
 __device__ __forceinline__ void onp_unit(const OnpSweepArgs& a, int u, int lane, float* xs, double* sums) {
 #pragma clang fp contract(off)
-  constexpr int SS = S > 0 ? S : 1;
-  const uint32_t beg = a.ptr[u], cnt = a.ptr[u + 1] - beg;
-  const uint32_t* idx = a.idx + beg;
-  const float* val = a.val + beg;
-  float* es = a.escratch + beg;
+  ObsForm<S> F(a.ptr, a.idx, a.val, a.escratch, u, lane);
   const int K = a.K, KP = a.KP;
-  float p[SS], r[SS], v[SS];
-  uint32_t jj[SS];
 
-  // ---- phase 1: P of every entry
-  if (S > 0) {
-#pragma unroll
-    for (int s = 0; s < SS; ++s) {
-      const uint32_t t = (uint32_t)(s * 64 + lane);
-      p[s] = 1.f; r[s] = 0.f; v[s] = 0.f; jj[s] = (uint32_t)a.m;     // (a slot without an entry: the zero word behind the other factor's columns)
-      if (t < cnt) { jj[s] = idx[t]; r[s] = val[t]; p[s] = a.resume ? es[t] : onp_dot(xs, a.Xo, KP, jj[s]); }
-    }
-  } else if (!a.resume) {
-    for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) es[t] = onp_dot(xs, a.Xo, KP, idx[t]);
-  }
+  // ---- phase 1: P of every entry -- or, in the single-column form, the P the previous column's call left in escratch
+  F.init((uint32_t)a.m, 1.f);
+  if (a.resume) F.from_scratch();
+  else F.each([&](int s, uint32_t t) __attribute__((always_inline)) { if (F.has(t)) F.E(s, t) = obs_dot(xs, a.Xo, KP, F.J(s, t)); });
 
   // ---- phase 2: the columns
   for (int k = a.k0; k < a.k1; ++k) {
     const float* vcol = a.XoT + (size_t)k * a.ldT_o;
     float sn = 0.f, sd = 0.f;
-    if (S > 0) {
-#pragma unroll
-      for (int s = 0; s < SS; ++s) { v[s] = vcol[jj[s]]; sn = fmaf(v[s], r[s] * __builtin_amdgcn_rcpf(p[s]), sn); sd = sd + v[s]; }
-    } else {
-      for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) { const float vv = vcol[idx[t]]; sn = fmaf(vv, val[t] * __builtin_amdgcn_rcpf(es[t]), sn); sd = sd + vv; }
-    }
+    F.each([&](int s, uint32_t t) __attribute__((always_inline)) {
+      const float vv = F.hold(s, vcol[F.J(s, t)]);
+      sn = fmaf(vv, F.R(s, t) * __builtin_amdgcn_rcpf(F.E(s, t)), sn); sd = sd + vv;
+    });
     sn = wave_sum(sn); sd = wave_sum(sd);
     const float xk = xs[k];
     const float xnew = (float)((double)xk * (double)sn / (double)sd);
     const float d = xnew - xk;
     xs[k] = xnew;                               // (every lane stores the same value, and reads back its own store)
-    if (S > 0) {
-#pragma unroll
-      for (int s = 0; s < SS; ++s) p[s] = fmaf(d, v[s], p[s]);
-    } else {
-      for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) es[t] = fmaf(d, vcol[idx[t]], es[t]);
-    }
+    F.each([&](int s, uint32_t t) __attribute__((always_inline)) { F.E(s, t) = fmaf(d, F.V(s, t, vcol), F.E(s, t)); });
   }
 
   // ---- the unit's new row: row major and transposed
@@ -112,67 +76,30 @@ __device__ __forceinline__ void onp_unit(const OnpSweepArgs& a, int u, int lane,
   }
 
   // ---- the single-column form: P for the next column's call
-  if (S > 0 && a.keep) {
-#pragma unroll
-    for (int s = 0; s < SS; ++s) {
-      const uint32_t t = (uint32_t)(s * 64 + lane);
-      if (t < cnt) es[t] = p[s];
-    }
-  }
+  if (a.keep) F.to_scratch();
 
   // ---- end of the iteration: the lane's sums over its entries, in entry order
-  if (a.part) {
-    if (S > 0) {
-#pragma unroll
-      for (int s = 0; s < SS; ++s) {
-        const uint32_t t = (uint32_t)(s * 64 + lane);
-        if (t < cnt) onp_entry_stats(sums, (double)r[s], (double)p[s]);
-      }
-    } else {
-      for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) onp_entry_stats(sums, (double)val[t], (double)es[t]);
-    }
-  }
+  if (a.part)
+    F.each([&](int s, uint32_t t) __attribute__((always_inline)) { if (F.has(t)) onp_entry_stats(sums, (double)F.R(s, t), (double)F.E(s, t)); });
 }
 
 __global__ __launch_bounds__(kObsWaves * 64) void onp_sweep_kernel(OnpSweepArgs a) {
   __shared__ float xsh[kObsWaves][kObsMaxRank];
-  __shared__ double red[kObsWaves][8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int u = blockIdx.x * kObsWaves + wave;
   const bool ok = u < a.n;
   float* xs = xsh[wave];
-  if (ok)
-    for (int k = lane; k < a.KP; k += 64) xs[k] = k < a.K ? a.X[(size_t)u * a.KP + k] : 0.f;
+  if (ok) obs_stage_row(xs, a.X + (size_t)u * a.KP, a.K, a.KP, lane);
   __syncthreads();
   double sums[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  if (ok) {
-    const uint32_t cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.ptr[u + 1] - a.ptr[u]));
-    if (a.force_long || cnt > (uint32_t)kObsMaxSlots * 64u) onp_unit<0>(a, u, lane, xs, sums);
-    else if (cnt <= 64u) onp_unit<1>(a, u, lane, xs, sums);
-    else if (cnt <= 128u) onp_unit<2>(a, u, lane, xs, sums);
-    else if (cnt <= 256u) onp_unit<4>(a, u, lane, xs, sums);
-    else onp_unit<8>(a, u, lane, xs, sums);
-  }
+  if (ok)
+    obs_dispatch<kObsMaxSlots>(obs_count(a.ptr, u), a.force_long, [&](auto form) __attribute__((always_inline)) {
+      onp_unit<decltype(form)::value>(a, u, lane, xs, sums);
+    });
   if (a.part) {                      // (wave-uniform, and the same in every wave: all of them reach the barrier)
-#pragma unroll
-    for (int m = 0; m < 8; ++m) sums[m] = wave_sum_d(sums[m]);
-    if (lane == 0)
-      for (int m = 0; m < 8; ++m) red[wave][m] = sums[m];
-    __syncthreads();
-    if (threadIdx.x < 8) {
-      double s = 0.0;
-      for (int w = 0; w < kObsWaves; ++w) s += red[w][threadIdx.x];
-      a.part[(size_t)blockIdx.x * 8 + threadIdx.x] = s;
-    }
+    const double s = obs_block_sums<8, kObsWaves>(sums, 8);
+    if (threadIdx.x < 8) a.part[(size_t)blockIdx.x * 8 + threadIdx.x] = s;
   }
-}
-
-// the blocks' partial sums in a fixed order into the record (or the metric call's out8)
-__global__ __launch_bounds__(256) void onp_fold_kernel(const double* part, int nb, double* out) {
-  double t[8];
-  obs_fold<8>(part, nb, t);
-  if (threadIdx.x == 0)
-    for (int m = 0; m < 8; ++m) out[m] = t[m];
 }
 
 // element (x, c) of X . S or X . S^T, the inner index in order; the padding columns of the row-major form are written as zeros
@@ -196,23 +123,16 @@ __global__ __launch_bounds__(256) void onp_eff_kernel(OnpEffArgs a) {
 template <bool BUILD>
 __global__ __launch_bounds__(kObsWaves * 64) void onp_s_pass_kernel(OnpSPassArgs a) {
 #pragma clang fp contract(off)
-  __shared__ double red[2][256];
   __shared__ double wred[kObsWaves][2];
   __shared__ float s_delta;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   float d = 0.f;
   if (a.prev >= 0) {                 // finish entry prev: every block sums the previous pass's partials in the same order
-    double nu = 0.0, de = 0.0;
-    for (int b = t; b < a.nb; b += 256) { nu += a.part_prev[(size_t)b * 2]; de += a.part_prev[(size_t)b * 2 + 1]; }
-    red[0][t] = nu; red[1][t] = de;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-      if (t < h) { red[0][t] += red[0][t + h]; red[1][t] += red[1][t + h]; }
-      __syncthreads();
-    }
+    double nd[2];                    // numerator and denominator
+    obs_fold<2>(a.part_prev, a.nb, nd);
     if (t == 0) {
       const float s0 = a.S_in[a.prev];
-      const float s1 = (float)((double)s0 * red[0][0] / red[1][0]);
+      const float s1 = (float)((double)s0 * nd[0] / nd[1]);
       s_delta = s1 - s0;
       if (blockIdx.x == 0) a.S_out[a.prev] = s1;
     }
@@ -231,7 +151,7 @@ __global__ __launch_bounds__(kObsWaves * 64) void onp_s_pass_kernel(OnpSPassArgs
     const float fp = d * frow[kp], fk = frow[k];
     for (uint32_t e = beg + (uint32_t)lane; e < end; e += 64) {
       const uint32_t j = a.idx[e];
-      float p = BUILD ? onp_dot(frow, a.Xo, a.ldF, j) : a.P[e];
+      float p = BUILD ? obs_dot(frow, a.Xo, a.ldF, j) : a.P[e];
       if (a.prev >= 0) p = fmaf(fp, gp[j], p);
       if (BUILD || a.prev >= 0) a.P[e] = p;
       if (a.cur >= 0) {
@@ -254,7 +174,6 @@ __global__ __launch_bounds__(kObsWaves * 64) void onp_s_pass_kernel(OnpSPassArgs
 
 __global__ __launch_bounds__(256) void onp_metric_kernel(OnpMetricArgs a) {
 #pragma clang fp contract(off)
-  __shared__ double red[8][256];
   const int tid = threadIdx.x;
   double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   const size_t stride = (size_t)gridDim.x * 256;
@@ -280,13 +199,9 @@ __global__ __launch_bounds__(256) void onp_metric_kernel(OnpMetricArgs a) {
     }
     onp_entry_stats(s, (double)a.val[e], p);
   }
-  for (int m = 0; m < 8; ++m) red[m][tid] = s[m];
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (tid < w) for (int m = 0; m < 8; ++m) red[m][tid] += red[m][tid + w];
-    __syncthreads();
-  }
-  if (tid < 8) a.part[(size_t)blockIdx.x * 8 + tid] = red[tid][0];
+  obs_tree_sums<8>(s);
+  if (tid == 0)
+    for (int m = 0; m < 8; ++m) a.part[(size_t)blockIdx.x * 8 + m] = s[m];
 }
 
 }  // namespace
@@ -296,7 +211,7 @@ void launch_onp_sweep(const OnpSweepArgs& a, hipStream_t st) {
 }
 
 void launch_onp_fold(const double* part, int nb, double* out8, hipStream_t st) {
-  hipLaunchKernelGGL(onp_fold_kernel, dim3(1), dim3(256), 0, st, part, nb, out8);
+  hipLaunchKernelGGL(obs_fold_kernel<8>, dim3(1), dim3(256), 0, st, part, nb, out8);
 }
 
 void launch_onp_eff(const OnpEffArgs& a, hipStream_t st) {
@@ -313,7 +228,7 @@ void launch_onp_s_pass(const OnpSPassArgs& a, hipStream_t st) {
 void launch_onp_metric(const OnpMetricArgs& a, double* out8, hipStream_t st) {
   const int nb = obs_metric_blocks(a.n);
   hipLaunchKernelGGL(onp_metric_kernel, dim3(nb), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(onp_fold_kernel, dim3(1), dim3(256), 0, st, (const double*)a.part, nb, out8);
+  hipLaunchKernelGGL(obs_fold_kernel<8>, dim3(1), dim3(256), 0, st, (const double*)a.part, nb, out8);
 }
 
 }  // namespace bnmtf

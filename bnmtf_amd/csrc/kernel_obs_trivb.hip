@@ -192,10 +192,9 @@ __global__ __launch_bounds__(256) void obs_trivb_finish_kernel(ObsTriVbFinishArg
 __global__ __launch_bounds__(256) void obs_trivb_esd_kernel(ObsTriVbEsdArgs a) {
   __shared__ double Sd[32 * 32], S2d[32 * 32];                     // E[S], E[S]^2 as [k][l], row stride L
   __shared__ double al[32], bl[32], cl[32], dl[32], vf[32];
-  __shared__ double red[256];
   const int tid = threadIdx.x, K = a.K, L = a.L;
   for (int t = tid; t < K * L; t += 256) { const double sv = (double)a.S[t]; Sd[t] = sv; S2d[t] = sv * sv; }
-  double s = 0.0;
+  double s[1] = {0.0};
   for (int u = blockIdx.x; u < a.n; u += gridDim.x) {
     __syncthreads();
     if (tid < L) {
@@ -227,21 +226,11 @@ __global__ __launch_bounds__(256) void obs_trivb_esd_kernel(ObsTriVbEsdArgs a) {
         t3 = fma(vf[k], m * m - sq, t3);
       }
       const double d = (double)a.val[t] - p;
-      s += d * d + t2 + t3 + t4;
+      s[0] += d * d + t2 + t3 + t4;
     }
   }
-  red[tid] = s;
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (tid < w) red[tid] += red[tid + w];
-    __syncthreads();
-  }
-  if (tid == 0) a.part[blockIdx.x] = red[0];
-}
-__global__ __launch_bounds__(256) void obs_trivb_esd_fold_kernel(const double* part, int nb, double* out) {
-  double t[1];
-  obs_fold<1>(part, nb, t);
-  if (threadIdx.x == 0) out[0] = t[0];
+  obs_tree_sums<1>(s);
+  if (tid == 0) a.part[blockIdx.x] = s[0];
 }
 
 }  // namespace
@@ -268,7 +257,7 @@ void launch_obs_trivb_finish(const ObsTriVbFinishArgs& a, hipStream_t st) {
 void launch_obs_trivb_esd(const ObsTriVbEsdArgs& a, double* out, hipStream_t st) {
   const int nb = obs_vb_esd_blocks(a.n);
   hipLaunchKernelGGL(obs_trivb_esd_kernel, dim3(nb), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(obs_trivb_esd_fold_kernel, dim3(1), dim3(256), 0, st, a.part, nb, out);
+  hipLaunchKernelGGL(obs_fold_kernel<1>, dim3(1), dim3(256), 0, st, a.part, nb, out);
 }
 
 }  // namespace bnmtf

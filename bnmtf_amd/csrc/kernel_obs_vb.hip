@@ -7,10 +7,8 @@
 // columns in order k = 0 .. K - 1; the V half sweep is the same on the column lists.
 //
 // obs_vb_sweep_kernel: one 64-lane wave per unit, kObsWaves units per block, lane l the unit's entries l, l + 64, ... in list
-// order; the register form with S = 1, 2, 4, 8 slots per lane and the long form through escratch, as obs_sweep_kernel has them
-// (a slot without an entry gathers the zero word behind the columns of both transposed operands).  Every per-lane sum runs in
-// entry order, every wave sum is the butterfly, fmaf is explicit and contraction is off: a unit's result does not depend on
-// the form.  The wave-uniform results of a column -- mu, tau, var, sa, sb; the expectation replaces x in the unit's row -- are
+// order; every per-entry loop written once on the unit's two forms (obs_common.h: a slot without an entry gathers the zero word
+// behind the columns of both transposed operands).  The wave-uniform results of a column -- mu, tau, var, sa, sb; the expectation replaces x in the unit's row -- are
 // parked in LDS (every lane stores the same value and reads back its own store); behind the column loop lane k mod 64 forms the
 // fp64 pieces of column k: the four sums elbo() needs of q(x) (quad, log erfc, log tau, lambda E: kernel_sweep.hip's pieces) and,
 // in the V half sweep, q2 = (var + E^2) sa and q3 = E^2 sb, whose difference summed over all (unit, column) is the variance
@@ -32,8 +30,8 @@ namespace {
 constexpr int kVbParked = 5;           // mu, tau, var, sa, sb of every column, beside the unit's row and its prior rates
 constexpr int kVbSums = 10;            // quad, log erfc, log tau, lambda E, q2, q3; SSE, sum P, sum P^2, sum R P
 
-// One unit.  S > 0: the register form with S slots per lane; S == 0: the long form.  xs / ls: the unit's expectations and prior
-// rates in LDS, pk: the parked column results.  sums (part != null): the lane's share of SSE, sum P, sum P^2, sum R P in sums[6 .. 9].
+// One unit in the form S (obs_common.h).  xs / ls: the unit's expectations and prior rates in LDS, pk: the parked column results.
+// sums (part != null): the lane's share of SSE, sum P, sum P^2, sum R P in sums[6 .. 9].
 // COV: the tri-factorisation's F / G half sweep against an effective factor (bnmtf_vb_optimised.py:241-250 / :264-273): the columns in
 // the order handed over, and the numerator less  sum_t S(k,t) mv_t (fs_t - x_k S(k,t)),  lane t holding mv_t (the other factor's
 // variance summed over the unit's entries: fixed for the half sweep) and fs_t = sum_c x_c S(c,t) (from the unit's current row; one
@@ -41,27 +39,15 @@ constexpr int kVbSums = 10;            // quad, log erfc, log tau, lambda E, q2,
 template <int S, bool COV>
 __device__ __forceinline__ void obs_vb_unit(const ObsVbSweepArgs& a, int u, int lane, float* xs, const float* ls, float* pk, double* sums) {
 #pragma clang fp contract(off)
-  constexpr int SS = S > 0 ? S : 1;
-  const uint32_t beg = a.ptr[u], cnt = a.ptr[u + 1] - beg;
-  const uint32_t* idx = a.idx + beg;
-  const float* val = a.val + beg;
-  float* es = a.escratch + beg;
+  ObsForm<S> F(a.ptr, a.idx, a.val, a.escratch, u, lane);
   const int K = a.K, KP = a.KP;
   float* mus = pk; float* tps = pk + kObsMaxRank; float* vrs = pk + 2 * kObsMaxRank; float* sas = pk + 3 * kObsMaxRank; float* sbs = pk + 4 * kObsMaxRank;
-  float e[SS], v[SS];
-  uint32_t jj[SS];
 
   // ---- phase 1: the residual of every entry
-  if (S > 0) {
-#pragma unroll
-    for (int s = 0; s < SS; ++s) {
-      const uint32_t t = (uint32_t)(s * 64 + lane);
-      e[s] = 0.f; v[s] = 0.f; jj[s] = (uint32_t)a.m;                 // (a slot without an entry: the zero word behind the other factor's columns)
-      if (t < cnt) { jj[s] = idx[t]; e[s] = obs_residual(xs, a.Xo, KP, jj[s], val[t]); }
-    }
-  } else {
-    for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) es[t] = obs_residual(xs, a.Xo, KP, idx[t], val[t]);
-  }
+  F.init((uint32_t)a.m, 0.f);
+  F.each([&](int s, uint32_t t) __attribute__((always_inline)) {
+    if (F.has(t)) F.E(s, t) = obs_residual(xs, a.Xo, KP, F.J(s, t), F.val[t]);
+  });
 
   // ---- phase 2: the columns
   const float exptau = *a.tau;
@@ -78,12 +64,16 @@ __device__ __forceinline__ void obs_vb_unit(const ObsVbSweepArgs& a, int u, int 
     const float* vcol = a.XoT + (size_t)k * a.ldT_o;
     const float* wcol = a.S2oT + (size_t)k * a.ldT_o;
     float se = 0.f, sb = 0.f, sa = 0.f;
-    if (S > 0) {
-#pragma unroll
-      for (int s = 0; s < SS; ++s) { v[s] = vcol[jj[s]]; const float w = wcol[jj[s]]; se = fmaf(e[s], v[s], se); sb = fmaf(v[s], v[s], sb); sa += w; }
-    } else {
-      for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) { const uint32_t j = idx[t]; const float vv = vcol[j], w = wcol[j]; se = fmaf(es[t], vv, se); sb = fmaf(vv, vv, sb); sa += w; }
-    }
+    F.each([&](int s, uint32_t t) __attribute__((always_inline)) {
+      const uint32_t j = F.J(s, t);
+      const float vv = F.hold(s, vcol[j]), w = wcol[j];
+      // (two independent sums; their order decides how the compiler pairs them, and with that when the long form's load of e is
+      // issued -- kernel_obs.hip, the same place.  Each instantiation has the order in which its rates were level with those of
+      // the hand-copied loops: the other order cost COV 1 % on long units and the two-factor kernel 0.5 to 1 % on short ones)
+      if (COV) { sb = fmaf(vv, vv, sb); se = fmaf(F.E(s, t), vv, se); }
+      else { se = fmaf(F.E(s, t), vv, se); sb = fmaf(vv, vv, sb); }
+      sa += w;
+    });
     se = wave_sum(se); sb = wave_sum(sb); sa = wave_sum(sa);
     const float xk = xs[k];
     const float tau_p = exptau * sa;
@@ -111,32 +101,18 @@ __device__ __forceinline__ void obs_vb_unit(const ObsVbSweepArgs& a, int u, int 
     xs[k] = ef;
     const float nd = xk - ef;                   // e -= (x' - x) v
     if (COV) fs = fmaf(-nd, sc, fs);
-    if (S > 0) {
-#pragma unroll
-      for (int s = 0; s < SS; ++s) e[s] = fmaf(nd, v[s], e[s]);
-    } else {
-      for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) es[t] = fmaf(nd, vcol[idx[t]], es[t]);
-    }
+    F.each([&](int s, uint32_t t) __attribute__((always_inline)) { F.E(s, t) = fmaf(nd, F.V(s, t, vcol), F.E(s, t)); });
   }
 
   // ---- end of the iteration: the lane's sums over its entries, in entry order
   if (a.part) {
     double sse = 0.0, sp = 0.0, spp = 0.0, srp = 0.0;
-    if (S > 0) {
-#pragma unroll
-      for (int s = 0; s < SS; ++s) {
-        const uint32_t t = (uint32_t)(s * 64 + lane);
-        if (t < cnt) {
-          const double ed = (double)e[s], r = (double)val[t], p = r - ed;
-          sse = fma(ed, ed, sse); sp += p; spp = fma(p, p, spp); srp = fma(r, p, srp);
-        }
-      }
-    } else {
-      for (uint32_t t = (uint32_t)lane; t < cnt; t += 64) {
-        const double ed = (double)es[t], r = (double)val[t], p = r - ed;
+    F.each([&](int s, uint32_t t) __attribute__((always_inline)) {
+      if (F.has(t)) {
+        const double ed = (double)F.E(s, t), r = (double)F.val[t], p = r - ed;
         sse = fma(ed, ed, sse); sp += p; spp = fma(p, p, spp); srp = fma(r, p, srp);
       }
-    }
+    });
     sums[6] = sse; sums[7] = sp; sums[8] = spp; sums[9] = srp;
   }
 }
@@ -180,42 +156,30 @@ __device__ __forceinline__ void obs_vb_sweep_body(const ObsVbSweepArgs& a) {
   __shared__ float xsh[kObsWaves][kObsMaxRank];
   __shared__ float lsh[kObsWaves][kObsMaxRank];
   __shared__ float pkh[kObsWaves][kVbParked * kObsMaxRank];
-  __shared__ double red[kObsWaves][kVbSums];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int u = blockIdx.x * kObsWaves + wave;
   const bool ok = u < a.n;
   float* xs = xsh[wave];
   float* ls = lsh[wave];
-  if (ok)
-    for (int k = lane; k < a.KP; k += 64) {
-      xs[k] = k < a.K ? a.X[(size_t)u * a.KP + k] : 0.f;
-      ls[k] = k < a.K ? a.lambda[(size_t)u * a.KP + k] : 0.f;
-    }
+  if (ok) {
+    obs_stage_row(xs, a.X + (size_t)u * a.KP, a.K, a.KP, lane);
+    obs_stage_row(ls, a.lambda + (size_t)u * a.KP, a.K, a.KP, lane);
+  }
   __syncthreads();
   double sums[kVbSums];
 #pragma unroll
   for (int m = 0; m < kVbSums; ++m) sums[m] = 0.0;
   if (ok) {
-    const uint32_t cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.ptr[u + 1] - a.ptr[u]));
-    if (a.force_long || cnt > (uint32_t)kObsMaxSlots * 64u) obs_vb_unit<0, COV>(a, u, lane, xs, ls, pkh[wave], sums);
-    else if (cnt <= 64u) obs_vb_unit<1, COV>(a, u, lane, xs, ls, pkh[wave], sums);
-    else if (cnt <= 128u) obs_vb_unit<2, COV>(a, u, lane, xs, ls, pkh[wave], sums);
-    else if (cnt <= 256u) obs_vb_unit<4, COV>(a, u, lane, xs, ls, pkh[wave], sums);
-    else obs_vb_unit<8, COV>(a, u, lane, xs, ls, pkh[wave], sums);
+    obs_dispatch<kObsMaxSlots>(obs_count(a.ptr, u), a.force_long, [&](auto form) __attribute__((always_inline)) {
+      obs_vb_unit<decltype(form)::value, COV>(a, u, lane, xs, ls, pkh[wave], sums);
+    });
     if (a.only_k < 0) obs_vb_pieces<COV>(a, u, lane, xs, ls, pkh[wave], sums);
   }
   if (a.stat) {                      // (wave-uniform, and the same in every wave: all of them reach the barrier)
     const int nsum = a.part ? kVbSums : 4;
-#pragma unroll
-    for (int m = 0; m < kVbSums; ++m)
-      if (m < nsum) sums[m] = wave_sum_d(sums[m]);
-    if (lane == 0)
-      for (int m = 0; m < kVbSums; ++m) red[wave][m] = sums[m];
-    __syncthreads();
+    const double s = obs_block_sums<kVbSums, kObsWaves>(sums, nsum);
     const int t = threadIdx.x;
     if (t < nsum) {
-      double s = 0.0;
-      for (int w = 0; w < kObsWaves; ++w) s += red[w][t];
       if (!a.part) a.stat[(size_t)blockIdx.x * 4 + t] = s;                   // the U half sweep: the four ELBO sums
       else if (t < 6) a.stat[(size_t)blockIdx.x * 6 + t] = s;                // the V half sweep: those, q2 and q3 ...
       else a.part[(size_t)blockIdx.x * 4 + (t - 6)] = s;                     // ... and the residual's four sums
@@ -253,9 +217,8 @@ __global__ __launch_bounds__(256) void obs_vb_finish_kernel(ObsVbFinishArgs a) {
 
 // sum over the observed entries of (R_ij - E_i . E_j)^2 + sum_k [(var + E^2)_ik (var + E^2)_jk - E_ik^2 E_jk^2], fp64
 __global__ __launch_bounds__(256) void obs_vb_esd_kernel(ObsVbEsdArgs a) {
-  __shared__ double red[256];
   const int tid = threadIdx.x;
-  double s = 0.0;
+  double s[1] = {0.0};
   for (int u = blockIdx.x; u < a.n; u += gridDim.x) {
     const float* xr = a.X + (size_t)u * a.KP;
     const float* vr = a.var + (size_t)u * a.KP;
@@ -270,21 +233,11 @@ __global__ __launch_bounds__(256) void obs_vb_esd_kernel(ObsVbEsdArgs a) {
         vs += ((double)vr[k] + x2) * ((double)vo[k] + y2) - x2 * y2;
       }
       const double d = (double)a.val[t] - p;
-      s += d * d + vs;
+      s[0] += d * d + vs;
     }
   }
-  red[tid] = s;
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (tid < w) red[tid] += red[tid + w];
-    __syncthreads();
-  }
-  if (tid == 0) a.part[blockIdx.x] = red[0];
-}
-__global__ __launch_bounds__(256) void obs_vb_esd_fold_kernel(const double* part, int nb, double* out) {
-  double t[1];
-  obs_fold<1>(part, nb, t);
-  if (threadIdx.x == 0) out[0] = t[0];
+  obs_tree_sums<1>(s);
+  if (tid == 0) a.part[blockIdx.x] = s[0];
 }
 
 }  // namespace
@@ -304,7 +257,7 @@ void launch_obs_vb_finish(const ObsVbFinishArgs& a, hipStream_t st) {
 void launch_obs_vb_esd(const ObsVbEsdArgs& a, double* out, hipStream_t st) {
   const int nb = obs_vb_esd_blocks(a.n);
   hipLaunchKernelGGL(obs_vb_esd_kernel, dim3(nb), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(obs_vb_esd_fold_kernel, dim3(1), dim3(256), 0, st, a.part, nb, out);
+  hipLaunchKernelGGL(obs_fold_kernel<1>, dim3(1), dim3(256), 0, st, a.part, nb, out);
 }
 
 }  // namespace bnmtf

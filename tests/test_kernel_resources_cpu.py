@@ -29,6 +29,15 @@ LIMITS = [
     ("kernel_np.hip", "np_sweep_kernelILi4ELi8EE", 128, 0),
     ("kernel_np.hip", "np_sweep_kernelILi8ELi4EE", 128, 0),
     ("kernel_np.hip", "np_sweep_kernelILi16ELi1EE", 128, 0),
+    # the observed-entry layout's sweeps (written on obs_common.h's ObsForm) and fold-in: 256-thread blocks meant to run four
+    # waves per SIMD, and 512 / 4 = 128 -- the hardware's ceiling, not a measurement; nothing to spill
+    ("kernel_obs.hip", "obs_sweep_kernelILi0EE", 128, 0),                         # Gibbs draws (kSweepDraw)
+    ("kernel_obs.hip", "obs_sweep_kernelILi1EE", 128, 0),                         # mode updates and the single-column hook (kSweepMode)
+    ("kernel_obs_vb.hip", "obs_vb_sweep_kernelE", 128, 0),
+    ("kernel_obs_vb.hip", "obs_trivb_sweep_kernelE", 128, 0),
+    ("kernel_obs_np.hip", "onp_sweep_kernelE", 128, 0),
+    ("kernel_foldin.hip", "foldin_kernelILi0EE", 128, 0),
+    ("kernel_foldin.hip", "foldin_kernelILi1EE", 128, 0),
 ]
 
 

@@ -207,7 +207,7 @@ def test_the_new_kernels_compile_for_gfx950_without_spills_or_scratch():
         m = re.search(r"remark:\s+(VGPRs Spill|SGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
         if m and name:
             found[name][m.group(1)] = int(m.group(2))
-    kernels = {"onp_sweep_kernel": 1, "onp_fold_kernel": 1, "onp_eff_kernel": 1, "onp_s_pass_kernel": 2, "onp_metric_kernel": 1}
+    kernels = {"onp_sweep_kernel": 1, "obs_fold_kernel": 1, "onp_eff_kernel": 1, "onp_s_pass_kernel": 2, "onp_metric_kernel": 1}
     assert len(found) == sum(kernels.values()), sorted(found)
     for kernel, count in kernels.items():
         hits = [r for n, r in found.items() if kernel in n]

@@ -209,7 +209,7 @@ def _resources(source):
 @pytest.mark.parametrize("source,kernels", [
     ("kernel_obs_vb.hip", ("obs_trivb_sweep_kernel",)),
     ("kernel_obs_tri.hip", ("obs_tri_gram_kernel",)),          # (untouched: the variational form is a sibling in the new unit)
-    ("kernel_obs_trivb.hip", ("obs_tri_gram_vb_kernel", "obs_trivb_eff_kernel", "obs_mv_kernel", "obs_trivb_finish_kernel", "obs_trivb_esd_kernel", "obs_trivb_esd_fold_kernel")),
+    ("kernel_obs_trivb.hip", ("obs_tri_gram_vb_kernel", "obs_trivb_eff_kernel", "obs_mv_kernel", "obs_trivb_finish_kernel", "obs_trivb_esd_kernel", "obs_fold_kernel")),          # (obs_fold_kernel<1>: obs_common.h's fold, instantiated here)
 ])
 def test_the_new_kernels_compile_for_gfx950_without_spills_or_scratch(source, kernels):
     found = _resources(source)
