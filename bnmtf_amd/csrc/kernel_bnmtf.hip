@@ -53,43 +53,40 @@ void launch_small_product(const SmallProductArgs& a, hipStream_t st) {
 // out[j][c] = sum_t (sum_s slabs[s][j][t]) S[t][c]: the G sweep's contraction R~^T (F S) as (R~^T F) S -- R~^T F is there
 // already (the S step's own contraction, F has not changed since), so the second pass over R~ shrinks to a K x L product per
 // column.  Half wave per unit: lane c holds the summed slab entry t = c and column c of the product.
-// (LIST: the list form's own instantiation -- a body shared by two kernels is inlined differently into each)
-template <int LIST>
-__device__ __forceinline__ void slab_product_body(SlabProductArgs a, unsigned block) {
-  __shared__ float Ss[64 * 64];                 // [inner index][output column], row stride 64, either way round
-  for (int t = threadIdx.x; t < a.K * a.L; t += 256) {
-    const int k = t / a.L, l = t % a.L;
-    Ss[a.transposeS ? l * 64 + k : k * 64 + l] = a.S[t];
-  }
-  __syncthreads();
-  const int l5 = threadIdx.x & 31;
-  const int u = block * 8 + (threadIdx.x >> 5);
-  if (u >= a.n) return;
-  const size_t stride = (size_t)a.n_pad * a.KPin;
-  const int inner = a.transposeS ? a.L : a.K, outw = a.transposeS ? a.K : a.L;      // (transposeS: out = slabs . S^T)
-  for (int c0 = 0; c0 < a.KPout; c0 += 32) {
-    float acc = 0.f;
-    for (int t0 = 0; t0 < inner; t0 += 32) {
-      const float tv = t0 + l5 < inner ? slab_sum_ordered(a.slabs, a.split, stride, (size_t)u * a.KPin + t0 + l5) : 0.f;
-      for (int t = 0; t < 32 && t0 + t < inner; ++t) {
-        const float x = __shfl(tv, t, 32);
-        if (c0 + l5 < outw) acc = fmaf(x, Ss[(t0 + t) * 64 + c0 + l5], acc);
-      }
+struct SlabProduct {
+  typedef SlabProductArgs Args;
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& a) { return (a.n + 7) / 8; }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) {
+    const unsigned block = blockIdx.x;
+    __shared__ float Ss[64 * 64];                 // [inner index][output column], row stride 64, either way round
+    for (int t = threadIdx.x; t < a.K * a.L; t += 256) {
+      const int k = t / a.L, l = t % a.L;
+      Ss[a.transposeS ? l * 64 + k : k * 64 + l] = a.S[t];
     }
-    a.out[(size_t)u * a.KPout + c0 + l5] = c0 + l5 < outw ? acc : 0.f;
+    __syncthreads();
+    const int l5 = threadIdx.x & 31;
+    const int u = block * 8 + (threadIdx.x >> 5);
+    if (u >= a.n) return;
+    const size_t stride = (size_t)a.n_pad * a.KPin;
+    const int inner = a.transposeS ? a.L : a.K, outw = a.transposeS ? a.K : a.L;      // (transposeS: out = slabs . S^T)
+    for (int c0 = 0; c0 < a.KPout; c0 += 32) {
+      float acc = 0.f;
+      for (int t0 = 0; t0 < inner; t0 += 32) {
+        const float tv = t0 + l5 < inner ? slab_sum_ordered(a.slabs, a.split, stride, (size_t)u * a.KPin + t0 + l5) : 0.f;
+        for (int t = 0; t < 32 && t0 + t < inner; ++t) {
+          const float x = __shfl(tv, t, 32);
+          if (c0 + l5 < outw) acc = fmaf(x, Ss[(t0 + t) * 64 + c0 + l5], acc);
+        }
+      }
+      a.out[(size_t)u * a.KPout + c0 + l5] = c0 + l5 < outw ? acc : 0.f;
+    }
   }
-}
-__global__ __launch_bounds__(256) void slab_product_kernel(SlabProductArgs a) { slab_product_body<0>(a, blockIdx.x); }
-// list form (many.h): blockIdx.z = model; a model with fewer blocks than the launch leaves
-__global__ __launch_bounds__(256) void slab_product_many(const SlabProductArgs* list, int) {
-  const SlabProductArgs a = load_pack(list, blockIdx.z);
-  if ((int)blockIdx.x >= (a.n + 7) / 8) return;
-  slab_product_body<1>(a, blockIdx.x);
-}
+};
 void launch_slab_product(const SlabProductArgs& a, hipStream_t st) {
   if (a.n <= 0) return;
-  if (record_launch((const void*)slab_product_many, dim3((a.n + 7) / 8), dim3(256), 0, a, true)) return;
-  hipLaunchKernelGGL(slab_product_kernel, dim3((a.n + 7) / 8), dim3(256), 0, st, a);
+  launch_forms<SlabProduct>(a, st);
 }
 
 // CfS[k][l] = sum_k' Cf[k][k'] S[k'][l]

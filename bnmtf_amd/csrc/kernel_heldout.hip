@@ -13,18 +13,17 @@
 // in LDS), K fused multiply-adds per held column, never through the sweeps' fp32 effective factor.
 // Order of the sums (fixed: two runs give the same bits, no floating-point atomics): lane 0 of a group adds its entries in list
 // order; a butterfly over the wave; the block's four waves in wave order (LDS [4][6]: consecutive doubles, one bank pair each);
-// heldout_fold_kernel adds the blocks' partials, thread t blocks t, t + 256, ..., then a tree over LDS [6][256] (thread-major:
+// HeldoutFold adds the blocks' partials, thread t blocks t, t + 256, ..., then a tree over LDS [6][256] (thread-major:
 // conflict-free).
 //
-// Column-major factors of rank up to 256 (the handles of bnmtf_np_create: U [K][I], V [K][J], or F, S, G): heldout_np_kernel.
+// Column-major factors of rank up to 256 (the handles of bnmtf_np_create: U [K][I], V [K][J], or F, S, G): HeldoutNp.
 // Same grid, same partials, same fold.  The lanes run along the row's entries instead -- lane l takes entries beg + l, beg + l + 64,
 // ... -- and for a fixed k the 64 addresses V[k J + j_l] ascend within one stretch of column k.  The row's own factor row (U_ik, or
 // (F_i S)_l formed in fp64 from the fp32 F_i and S, lanes along l) is staged once per row in LDS as doubles ([4][256], 8 KiB) and
 // read by broadcast.  Order of the sums: the lane's entries in list order, then as above.
 //
-// List forms (many.h): blockIdx.z = model, the arguments through load_pack, the single-model kernels' bodies.  The main kernels
-// leave with blockIdx.x >= the model's own heldout_blocks(I); the fold finds its record `it` records behind the run's first, so a
-// model's argument bytes are the same in every iteration.
+// Both forms of the three kernels: many.h.  The main kernels run heldout_blocks(I) blocks; the fold finds its record `it` records
+// behind the run's first, so a model's argument bytes are the same in every iteration.
 #include "kernels.h"
 #include "many.h"
 
@@ -39,197 +38,185 @@ __device__ inline double wave_sum(double v) {
 }
 
 template <int KP, bool TRI>
-__device__ __forceinline__ void heldout_body(const HeldoutArgs& a) {
-  constexpr int LPE = KP / 4;          // lanes per entry
-  constexpr int EPS = 64 / LPE;        // entries per wave step
-  __shared__ __attribute__((aligned(16))) float Ssh[TRI ? 64 * KP : 4];     // S [K][KP], zero beyond column L
-  __shared__ __attribute__((aligned(16))) float Fsh[TRI ? 4 * 64 : 4];      // the waves' rows of F
-  __shared__ double red[kHeldoutRowsPerBlock][6];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sub = lane % LPE, grp = lane / LPE;
-  const int i = blockIdx.x * kHeldoutRowsPerBlock + wave;
-  const bool row_ok = i < a.I;
+struct Heldout {
+  typedef HeldoutArgs Args;
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& a) { return heldout_blocks(a.I); }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) {
+    constexpr int LPE = KP / 4;          // lanes per entry
+    constexpr int EPS = 64 / LPE;        // entries per wave step
+    __shared__ __attribute__((aligned(16))) float Ssh[TRI ? 64 * KP : 4];     // S [K][KP], zero beyond column L
+    __shared__ __attribute__((aligned(16))) float Fsh[TRI ? 4 * 64 : 4];      // the waves' rows of F
+    __shared__ double red[kHeldoutRowsPerBlock][6];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane % LPE, grp = lane / LPE;
+    const int i = blockIdx.x * kHeldoutRowsPerBlock + wave;
+    const bool row_ok = i < a.I;
 
-  // ---- the row's held factor: columns 4 sub .. 4 sub + 3 of A_i (or of F_i S), fp64
-  double av[4] = {0.0, 0.0, 0.0, 0.0};
-  if (TRI) {
-    for (int t = threadIdx.x; t < a.K * KP; t += 256) {
-      const int k = t / KP, l = t % KP;
-      Ssh[t] = l < a.L ? a.S[k * a.L + l] : 0.f;
-    }
-    if (row_ok && lane < a.KPa / 4)
-      *reinterpret_cast<float4*>(&Fsh[wave * 64 + 4 * lane]) = *reinterpret_cast<const float4*>(a.A + (size_t)i * a.KPa + 4 * lane);
-    __syncthreads();
-    if (row_ok)
-      for (int k = 0; k < a.K; ++k) {
-        const double f = (double)Fsh[wave * 64 + k];
-        const float4 s4 = *reinterpret_cast<const float4*>(&Ssh[k * KP + 4 * sub]);
-        av[0] = fma(f, (double)s4.x, av[0]); av[1] = fma(f, (double)s4.y, av[1]);
-        av[2] = fma(f, (double)s4.z, av[2]); av[3] = fma(f, (double)s4.w, av[3]);
+    // ---- the row's held factor: columns 4 sub .. 4 sub + 3 of A_i (or of F_i S), fp64
+    double av[4] = {0.0, 0.0, 0.0, 0.0};
+    if (TRI) {
+      for (int t = threadIdx.x; t < a.K * KP; t += 256) {
+        const int k = t / KP, l = t % KP;
+        Ssh[t] = l < a.L ? a.S[k * a.L + l] : 0.f;
       }
-  } else if (row_ok) {
-    const float4 a4 = *reinterpret_cast<const float4*>(a.A + (size_t)i * KP + 4 * sub);
-    av[0] = (double)a4.x; av[1] = (double)a4.y; av[2] = (double)a4.z; av[3] = (double)a4.w;
-  }
-
-  // ---- the row's entries, EPS per step
-  const uint32_t beg = row_ok ? a.rowptr[i] : 0u, end = row_ok ? a.rowptr[i + 1] : 0u;
-  double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  uint32_t e = beg + (uint32_t)grp;
-  bool live = e < end;
-  uint32_t j = live ? a.col[e] : 0u;
-  float r32 = live ? a.rval[e] : 0.f;
-  for (uint32_t base = beg; base < end; base += EPS) {
-    const float4 b4 = *reinterpret_cast<const float4*>(a.B + (size_t)j * KP + 4 * sub);
-    const uint32_t en = e + EPS;
-    const bool ln = en < end;
-    const uint32_t jn = ln ? a.col[en] : 0u;
-    const float rn = ln ? a.rval[en] : 0.f;
-    double p = 0.0;                    // (the padding columns take no part, whatever they hold)
-    if (4 * sub + 0 < a.Wb) p = fma(av[0], (double)b4.x, p);
-    if (4 * sub + 1 < a.Wb) p = fma(av[1], (double)b4.y, p);
-    if (4 * sub + 2 < a.Wb) p = fma(av[2], (double)b4.z, p);
-    if (4 * sub + 3 < a.Wb) p = fma(av[3], (double)b4.w, p);
-#pragma unroll
-    for (int m = LPE / 2; m >= 1; m >>= 1) p += __shfl_xor(p, m, 64);
-    if (live && sub == 0) {
-      const double r = (double)r32;
-      s[0] += 1.0; s[1] += r; s[2] = fma(r, r, s[2]); s[3] += p; s[4] = fma(p, p, s[4]); s[5] = fma(r, p, s[5]);
+      if (row_ok && lane < a.KPa / 4)
+        *reinterpret_cast<float4*>(&Fsh[wave * 64 + 4 * lane]) = *reinterpret_cast<const float4*>(a.A + (size_t)i * a.KPa + 4 * lane);
+      __syncthreads();
+      if (row_ok)
+        for (int k = 0; k < a.K; ++k) {
+          const double f = (double)Fsh[wave * 64 + k];
+          const float4 s4 = *reinterpret_cast<const float4*>(&Ssh[k * KP + 4 * sub]);
+          av[0] = fma(f, (double)s4.x, av[0]); av[1] = fma(f, (double)s4.y, av[1]);
+          av[2] = fma(f, (double)s4.z, av[2]); av[3] = fma(f, (double)s4.w, av[3]);
+        }
+    } else if (row_ok) {
+      const float4 a4 = *reinterpret_cast<const float4*>(a.A + (size_t)i * KP + 4 * sub);
+      av[0] = (double)a4.x; av[1] = (double)a4.y; av[2] = (double)a4.z; av[3] = (double)a4.w;
     }
-    e = en; live = ln; j = jn; r32 = rn;
-  }
 
-  // ---- wave, then block
+    // ---- the row's entries, EPS per step
+    const uint32_t beg = row_ok ? a.rowptr[i] : 0u, end = row_ok ? a.rowptr[i + 1] : 0u;
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    uint32_t e = beg + (uint32_t)grp;
+    bool live = e < end;
+    uint32_t j = live ? a.col[e] : 0u;
+    float r32 = live ? a.rval[e] : 0.f;
+    for (uint32_t base = beg; base < end; base += EPS) {
+      const float4 b4 = *reinterpret_cast<const float4*>(a.B + (size_t)j * KP + 4 * sub);
+      const uint32_t en = e + EPS;
+      const bool ln = en < end;
+      const uint32_t jn = ln ? a.col[en] : 0u;
+      const float rn = ln ? a.rval[en] : 0.f;
+      double p = 0.0;                    // (the padding columns take no part, whatever they hold)
+      if (4 * sub + 0 < a.Wb) p = fma(av[0], (double)b4.x, p);
+      if (4 * sub + 1 < a.Wb) p = fma(av[1], (double)b4.y, p);
+      if (4 * sub + 2 < a.Wb) p = fma(av[2], (double)b4.z, p);
+      if (4 * sub + 3 < a.Wb) p = fma(av[3], (double)b4.w, p);
 #pragma unroll
-  for (int m = 0; m < 6; ++m) s[m] = wave_sum(s[m]);
-  if (lane == 0)
-    for (int m = 0; m < 6; ++m) red[wave][m] = s[m];
-  __syncthreads();
-  if (threadIdx.x < 8) {
-    double v = 0.0;
-    if (threadIdx.x < 6)
-      for (int w = 0; w < kHeldoutRowsPerBlock; ++w) v += red[w][threadIdx.x];
-    a.part[(size_t)blockIdx.x * 8 + threadIdx.x] = v;
+      for (int m = LPE / 2; m >= 1; m >>= 1) p += __shfl_xor(p, m, 64);
+      if (live && sub == 0) {
+        const double r = (double)r32;
+        s[0] += 1.0; s[1] += r; s[2] = fma(r, r, s[2]); s[3] += p; s[4] = fma(p, p, s[4]); s[5] = fma(r, p, s[5]);
+      }
+      e = en; live = ln; j = jn; r32 = rn;
+    }
+
+    // ---- wave, then block
+#pragma unroll
+    for (int m = 0; m < 6; ++m) s[m] = wave_sum(s[m]);
+    if (lane == 0)
+      for (int m = 0; m < 6; ++m) red[wave][m] = s[m];
+    __syncthreads();
+    if (threadIdx.x < 8) {
+      double v = 0.0;
+      if (threadIdx.x < 6)
+        for (int w = 0; w < kHeldoutRowsPerBlock; ++w) v += red[w][threadIdx.x];
+      a.part[(size_t)blockIdx.x * 8 + threadIdx.x] = v;
+    }
   }
-}
-
-template <int KP, bool TRI>
-__global__ __launch_bounds__(256) void heldout_kernel(HeldoutArgs a) { heldout_body<KP, TRI>(a); }
-
-template <int KP, bool TRI>
-__global__ __launch_bounds__(256) void heldout_many(const HeldoutArgs* list, int) {
-  const HeldoutArgs a = load_pack(list, blockIdx.z);
-  if ((int)blockIdx.x >= heldout_blocks(a.I)) return;
-  heldout_body<KP, TRI>(a);
-}
+};
 
 // Column-major fp32 factors, ranks up to kHeldoutNpMaxRank: a lane per entry of the row.
 template <bool TRI>
-__device__ __forceinline__ void heldout_np_body(const HeldoutNpArgs& a) {
-  __shared__ double rowf[kHeldoutRowsPerBlock][kHeldoutNpMaxRank];       // the waves' factor rows: U_i, or F_i S
-  __shared__ double red[kHeldoutRowsPerBlock][6];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int i = blockIdx.x * kHeldoutRowsPerBlock + wave;
-  const bool row_ok = i < a.I;
-  const int W = TRI ? a.L : a.K;                 // columns of the row's factor row = rows of Xc
-  double* const mine = rowf[wave];
+struct HeldoutNp {
+  typedef HeldoutNpArgs Args;
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& a) { return heldout_blocks(a.I); }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) {
+    __shared__ double rowf[kHeldoutRowsPerBlock][kHeldoutNpMaxRank];       // the waves' factor rows: U_i, or F_i S
+    __shared__ double red[kHeldoutRowsPerBlock][6];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * kHeldoutRowsPerBlock + wave;
+    const bool row_ok = i < a.I;
+    const int W = TRI ? a.L : a.K;                 // columns of the row's factor row = rows of Xc
+    double* const mine = rowf[wave];
 
-  // ---- the row's factor row, fp64, lanes along its columns
-  if (row_ok) {
-    if (TRI) {
-      for (int l = lane; l < W; l += 64) {
-        double v = 0.0;
-        for (int k = 0; k < a.K; ++k) v = fma((double)a.Xr[(size_t)k * a.I + i], (double)a.S[(size_t)k * a.L + l], v);
-        mine[l] = v;
+    // ---- the row's factor row, fp64, lanes along its columns
+    if (row_ok) {
+      if (TRI) {
+        for (int l = lane; l < W; l += 64) {
+          double v = 0.0;
+          for (int k = 0; k < a.K; ++k) v = fma((double)a.Xr[(size_t)k * a.I + i], (double)a.S[(size_t)k * a.L + l], v);
+          mine[l] = v;
+        }
+      } else {
+        for (int k = lane; k < W; k += 64) mine[k] = (double)a.Xr[(size_t)k * a.I + i];
       }
-    } else {
-      for (int k = lane; k < W; k += 64) mine[k] = (double)a.Xr[(size_t)k * a.I + i];
     }
-  }
-  __syncthreads();
-
-  // ---- the row's entries, 64 per step
-  const uint32_t beg = row_ok ? a.rowptr[i] : 0u, end = row_ok ? a.rowptr[i + 1] : 0u;
-  double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  uint32_t e = beg + (uint32_t)lane;
-  bool live = e < end;
-  uint32_t j = live ? a.col[e] : 0u;
-  float r32 = live ? a.rval[e] : 0.f;
-  for (uint32_t base = beg; base < end; base += 64) {
-    const float* bcol = a.Xc + j;                // (a lane without an entry reads column 0: J >= 1)
-    const uint32_t en = e + 64;
-    const bool ln = en < end;
-    const uint32_t jn = ln ? a.col[en] : 0u;
-    const float rn = ln ? a.rval[en] : 0.f;
-    double p = 0.0;
-#pragma unroll 4
-    for (int k = 0; k < W; ++k) p = fma(mine[k], (double)bcol[(size_t)k * a.J], p);
-    if (live) {
-      const double r = (double)r32;
-      s[0] += 1.0; s[1] += r; s[2] = fma(r, r, s[2]); s[3] += p; s[4] = fma(p, p, s[4]); s[5] = fma(r, p, s[5]);
-    }
-    e = en; live = ln; j = jn; r32 = rn;
-  }
-
-  // ---- wave, then block
-#pragma unroll
-  for (int m = 0; m < 6; ++m) s[m] = wave_sum(s[m]);
-  if (lane == 0)
-    for (int m = 0; m < 6; ++m) red[wave][m] = s[m];
-  __syncthreads();
-  if (threadIdx.x < 8) {
-    double v = 0.0;
-    if (threadIdx.x < 6)
-      for (int w = 0; w < kHeldoutRowsPerBlock; ++w) v += red[w][threadIdx.x];
-    a.part[(size_t)blockIdx.x * 8 + threadIdx.x] = v;
-  }
-}
-
-template <bool TRI>
-__global__ __launch_bounds__(256) void heldout_np_kernel(HeldoutNpArgs a) { heldout_np_body<TRI>(a); }
-
-template <bool TRI>
-__global__ __launch_bounds__(256) void heldout_np_many(const HeldoutNpArgs* list, int) {
-  const HeldoutNpArgs a = load_pack(list, blockIdx.z);
-  if ((int)blockIdx.x >= heldout_blocks(a.I)) return;
-  heldout_np_body<TRI>(a);
-}
-
-// the blocks' partial sums in a fixed order, into the iteration's record
-__device__ __forceinline__ void heldout_fold_body(const double* part, int nblocks, double* rec) {
-  __shared__ double red[6][256];
-  const int tid = threadIdx.x;
-  double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int b = tid; b < nblocks; b += 256)
-    for (int m = 0; m < 6; ++m) s[m] += part[(size_t)b * 8 + m];
-  for (int m = 0; m < 6; ++m) red[m][tid] = s[m];
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (tid < w) for (int m = 0; m < 6; ++m) red[m][tid] += red[m][tid + w];
     __syncthreads();
+
+    // ---- the row's entries, 64 per step
+    const uint32_t beg = row_ok ? a.rowptr[i] : 0u, end = row_ok ? a.rowptr[i + 1] : 0u;
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    uint32_t e = beg + (uint32_t)lane;
+    bool live = e < end;
+    uint32_t j = live ? a.col[e] : 0u;
+    float r32 = live ? a.rval[e] : 0.f;
+    for (uint32_t base = beg; base < end; base += 64) {
+      const float* bcol = a.Xc + j;                // (a lane without an entry reads column 0: J >= 1)
+      const uint32_t en = e + 64;
+      const bool ln = en < end;
+      const uint32_t jn = ln ? a.col[en] : 0u;
+      const float rn = ln ? a.rval[en] : 0.f;
+      double p = 0.0;
+#pragma unroll 4
+      for (int k = 0; k < W; ++k) p = fma(mine[k], (double)bcol[(size_t)k * a.J], p);
+      if (live) {
+        const double r = (double)r32;
+        s[0] += 1.0; s[1] += r; s[2] = fma(r, r, s[2]); s[3] += p; s[4] = fma(p, p, s[4]); s[5] = fma(r, p, s[5]);
+      }
+      e = en; live = ln; j = jn; r32 = rn;
+    }
+
+    // ---- wave, then block
+#pragma unroll
+    for (int m = 0; m < 6; ++m) s[m] = wave_sum(s[m]);
+    if (lane == 0)
+      for (int m = 0; m < 6; ++m) red[wave][m] = s[m];
+    __syncthreads();
+    if (threadIdx.x < 8) {
+      double v = 0.0;
+      if (threadIdx.x < 6)
+        for (int w = 0; w < kHeldoutRowsPerBlock; ++w) v += red[w][threadIdx.x];
+      a.part[(size_t)blockIdx.x * 8 + threadIdx.x] = v;
+    }
   }
-  if (tid < 8) rec[tid] = tid < 6 ? red[tid][0] : 0.0;
-}
-__global__ __launch_bounds__(256) void heldout_fold_kernel(const double* part, int nblocks, double* rec) { heldout_fold_body(part, nblocks, rec); }
-// list form: rec = the run's FIRST record, the iteration's one is `it` records behind it (the argument list stays the same)
-struct HeldoutFoldPack { const double* part; double* rec; int nblocks, pad; };
-__global__ __launch_bounds__(256) void heldout_fold_many(const HeldoutFoldPack* list, int it) {
-  const HeldoutFoldPack p = load_pack(list, blockIdx.z);
-  heldout_fold_body(p.part, p.nblocks, p.rec + (size_t)it * 8);
-}
+};
+
+// the blocks' partial sums in a fixed order, into the iteration's record (rec: the run's FIRST record)
+struct HeldoutFold {
+  struct Args { const double* part; double* rec; int nblocks, pad; };
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args&) { return 1; }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int it) {
+    double* rec = a.rec + (size_t)it * 8;
+    __shared__ double red[6][256];
+    const int tid = threadIdx.x;
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = tid; b < a.nblocks; b += 256)
+      for (int m = 0; m < 6; ++m) s[m] += a.part[(size_t)b * 8 + m];
+    for (int m = 0; m < 6; ++m) red[m][tid] = s[m];
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+      if (tid < w) for (int m = 0; m < 6; ++m) red[m][tid] += red[m][tid + w];
+      __syncthreads();
+    }
+    if (tid < 8) rec[tid] = tid < 6 ? red[tid][0] : 0.0;
+  }
+};
 
 }  // namespace
 
 // the fold behind a main kernel of `nblocks` blocks -- launched, or recorded behind the main kernel's record (kernels.h: the
 // observed-entry layout's held-out kernel, kernel_obs_heldout.hip, ends in it as well)
 void launch_fold(const double* part, int nblocks, double* rec, hipStream_t st) {
-  if (g_recorder) {
-    HeldoutFoldPack p; memset(&p, 0, sizeof(p));
-    p.part = part; p.rec = rec; p.nblocks = nblocks;
-    record_launch((const void*)heldout_fold_many, dim3(1), dim3(256), 0, p);
-    return;
-  }
-  hipLaunchKernelGGL(heldout_fold_kernel, dim3(1), dim3(256), 0, st, part, nblocks, rec);
+  HeldoutFold::Args a; memset(&a, 0, sizeof(a));
+  a.part = part; a.rec = rec; a.nblocks = nblocks;
+  launch_forms<HeldoutFold>(a, st);
 }
 
 namespace {
@@ -248,30 +235,22 @@ __global__ __launch_bounds__(256) void heldout_values_kernel(const float* R, int
 // While a Recorder is installed (many.h): a.rec is the run's first record, and the pair is recorded at kHeldoutSite, behind every
 // site of the model's family.  (The caller has zeroed the pack's padding: a recorded list compares argument bytes.)
 void launch_heldout(const HeldoutArgs& a, hipStream_t st) {
-  const dim3 grid(heldout_blocks(a.I)), block(256);
-  if (g_recorder) {
-    const void* fn = a.S ? (a.KPb == 32 ? (const void*)heldout_many<32, true> : (const void*)heldout_many<64, true>)
-                         : (a.KPb == 32 ? (const void*)heldout_many<32, false> : (const void*)heldout_many<64, false>);
-    site_at(kHeldoutSite);
-    record_launch(fn, grid, block, 0, a, true);
-  } else if (a.S) {
-    if (a.KPb == 32) hipLaunchKernelGGL((heldout_kernel<32, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((heldout_kernel<64, true>), grid, block, 0, st, a);
+  site_at(kHeldoutSite);
+  if (a.S) {
+    if (a.KPb == 32) launch_forms<Heldout<32, true>>(a, st);
+    else launch_forms<Heldout<64, true>>(a, st);
   } else {
-    if (a.KPb == 32) hipLaunchKernelGGL((heldout_kernel<32, false>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((heldout_kernel<64, false>), grid, block, 0, st, a);
+    if (a.KPb == 32) launch_forms<Heldout<32, false>>(a, st);
+    else launch_forms<Heldout<64, false>>(a, st);
   }
-  launch_fold(a.part, (int)grid.x, a.rec, st);
+  launch_fold(a.part, heldout_blocks(a.I), a.rec, st);
 }
 
 void launch_heldout_np(const HeldoutNpArgs& a, hipStream_t st) {
-  const dim3 grid(heldout_blocks(a.I)), block(256);
-  if (g_recorder) {
-    site_at(kHeldoutSite);
-    record_launch(a.S ? (const void*)heldout_np_many<true> : (const void*)heldout_np_many<false>, grid, block, 0, a, true);
-  } else if (a.S) hipLaunchKernelGGL(heldout_np_kernel<true>, grid, block, 0, st, a);
-  else hipLaunchKernelGGL(heldout_np_kernel<false>, grid, block, 0, st, a);
-  launch_fold(a.part, (int)grid.x, a.rec, st);
+  site_at(kHeldoutSite);
+  if (a.S) launch_forms<HeldoutNp<true>>(a, st);
+  else launch_forms<HeldoutNp<false>>(a, st);
+  launch_fold(a.part, heldout_blocks(a.I), a.rec, st);
 }
 
 void launch_heldout_values(const float* R, int I, int J, const uint32_t* rowptr, const uint32_t* col, float* rval, hipStream_t st) {

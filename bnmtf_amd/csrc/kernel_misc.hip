@@ -115,75 +115,74 @@ __global__ __launch_bounds__(kFinishThreads) void finish_kernel(FinishArgs a) {
 }
 // VB end of iteration (bnmf_vb_optimised.py:181-187, 213-215): exp_square_diff from Gram identities,
 // exptau = alpha_s / beta_s, training-mask metrics, and the O((I+J)K) sums elbo() needs.
-__device__ __forceinline__ void vb_finish_body(const VbFinishArgs& a) {
-  __shared__ double red[16][16];
-  const int KP = a.KP, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // 16 sums: <Cr, Cc>, six columns of the rows-sweep pieces, six of the cols-sweep pieces, and the three K-term sums (colsum .
-  // colsum, colsum2 . colsum2, diag(Cr) . diag(Cc)).  Round 5: a sum per WAVE -- waves 0-3 a quarter of <Cr, Cc> each (and, waves
-  // 1-3, one K-term sum), waves 4-15 one column of the pieces -- so a wave reduces one or two values over its lanes, not sixteen
-  // (16 x 6 fp64 shuffles per wave were most of this kernel's 16 us).  red[w][0 / 1] = the wave's sums.
-  double s0 = 0.0, s1 = 0.0;
-  if (wave < 4) {
-    const int q4 = KP * KP / 4;
-    double p[16];
+// (rec = the run's FIRST record, the iteration's one is `it` records behind it: a recorded argument list stays the same)
+struct VbFinish {
+  typedef VbFinishArgs Args;
+  static constexpr int kThreads = 1024;
+  static __host__ __device__ int blocks(const Args&) { return 1; }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& args, int, int it) {
+    VbFinishArgs a = args;
+    a.rec += (size_t)it * 16;
+    __shared__ double red[16][16];
+    const int KP = a.KP, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // 16 sums: <Cr, Cc>, six columns of the rows-sweep pieces, six of the cols-sweep pieces, and the three K-term sums (colsum .
+    // colsum, colsum2 . colsum2, diag(Cr) . diag(Cc)).  Round 5: a sum per WAVE -- waves 0-3 a quarter of <Cr, Cc> each (and, waves
+    // 1-3, one K-term sum), waves 4-15 one column of the pieces -- so a wave reduces one or two values over its lanes, not sixteen
+    // (16 x 6 fp64 shuffles per wave were most of this kernel's 16 us).  red[w][0 / 1] = the wave's sums.
+    double s0 = 0.0, s1 = 0.0;
+    if (wave < 4) {
+      const int q4 = KP * KP / 4;
+      double p[16];
 #pragma unroll
-    for (int u = 0; u < 16; ++u) { const int t = wave * q4 + lane + 64 * u; p[u] = 64 * u < q4 ? a.Cr64[t] * a.Cc64[t] : 0.0; }
+      for (int u = 0; u < 16; ++u) { const int t = wave * q4 + lane + 64 * u; p[u] = 64 * u < q4 ? a.Cr64[t] * a.Cc64[t] : 0.0; }
 #pragma unroll
-    for (int u = 0; u < 16; ++u) s0 += p[u];
-    if (wave == 0 && a.extra) for (int b = lane; b < a.n_extra; b += 64) s1 += a.extra[b];
-    if (wave >= 1 && lane < KP)
-      s1 = wave == 1 ? a.sr[lane] * a.sc[lane] : wave == 2 ? a.s2r[lane] * a.s2c[lane] : a.Cr64[lane * KP + lane] * a.Cc64[lane * KP + lane];
-  } else {
-    const int c = wave - 4, col = c % 6;
-    const double* src = c < 6 ? a.stats_r : a.stats_c;
-    const int n = c < 6 ? a.nr : a.nc;
-    for (int b = lane; b < n; b += 64) s0 += src[(size_t)b * 8 + col];
-    // (round 6: the on-chip cols sweep's per-block sums -- sum P.X', sum_miss q, sum_miss q^2 -- are folded here by waves 4-6;
-    // they used to be a launch of their own behind a memset of acc: ~10 us of an iteration that is 125 us for a GDSC-shaped model)
-    if (a.sweep_stats && c < 3)
-      for (int b = lane; b < a.n_sweep_stats; b += 64) s1 += a.sweep_stats[(size_t)b * 4 + c];
+      for (int u = 0; u < 16; ++u) s0 += p[u];
+      if (wave == 0 && a.extra) for (int b = lane; b < a.n_extra; b += 64) s1 += a.extra[b];
+      if (wave >= 1 && lane < KP)
+        s1 = wave == 1 ? a.sr[lane] * a.sc[lane] : wave == 2 ? a.s2r[lane] * a.s2c[lane] : a.Cr64[lane * KP + lane] * a.Cc64[lane * KP + lane];
+    } else {
+      const int c = wave - 4, col = c % 6;
+      const double* src = c < 6 ? a.stats_r : a.stats_c;
+      const int n = c < 6 ? a.nr : a.nc;
+      for (int b = lane; b < n; b += 64) s0 += src[(size_t)b * 8 + col];
+      // (round 6: the on-chip cols sweep's per-block sums -- sum P.X', sum_miss q, sum_miss q^2 -- are folded here by waves 4-6;
+      // they used to be a launch of their own behind a memset of acc: ~10 us of an iteration that is 125 us for a GDSC-shaped model)
+      if (a.sweep_stats && c < 3)
+        for (int b = lane; b < a.n_sweep_stats; b += 64) s1 += a.sweep_stats[(size_t)b * 4 + c];
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { s0 += __shfl_xor(s0, m, 64); s1 += __shfl_xor(s1, m, 64); }
+    if (lane == 0) { red[wave][0] = s0; red[wave][1] = s1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double tot[16];
+      tot[0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+      for (int c = 0; c < 12; ++c) tot[1 + c] = red[4 + c][0];
+      tot[13] = red[1][1]; tot[14] = red[2][1]; tot[15] = red[3][1];
+      const double dot = tot[0];
+      const double* su = &tot[1];
+      const double* sv = &tot[7];
+      const double sp1 = tot[13], s22 = tot[14], sdd = tot[15];
+      const double acc0 = a.acc[0] + (a.sweep_stats ? red[4][1] : 0.0), acc1 = a.acc[1] + (a.sweep_stats ? red[5][1] : 0.0), acc2 = a.acc[2] + (a.sweep_stats ? red[6][1] : 0.0);
+      const double srp = acc0, sp = sp1 - acc1, spp = dot - acc2;
+      const double n = a.n_obs;
+      const double sse = a.sumR2 - 2.0 * srp + spp;
+      const double esd = sse + (s22 - sv[4]) - (sdd - sv[5]) + red[0][1];
+      const double alpha_s = a.alpha + 0.5 * n, beta_s = a.beta + 0.5 * esd;
+      const double exptau = alpha_s / beta_s;
+      *a.tau_d = exptau; *a.tau_f = (float)exptau;
+      const double ss_tot = a.sumR2 - a.sumR * a.sumR / n;
+      const double cov = srp - a.sumR * sp / n, vp = spp - sp * sp / n;
+      a.rec[0] = exptau; a.rec[1] = sse / n;
+      a.rec[2] = ss_tot != 0.0 ? 1.0 - sse / ss_tot : __longlong_as_double(0x7ff0000000000000LL);
+      a.rec[3] = cov / (sqrt(ss_tot) * sqrt(vp));
+      a.rec[4] = esd; a.rec[5] = beta_s;
+      for (int c = 0; c < 4; ++c) { a.rec[6 + c] = su[c]; a.rec[10 + c] = sv[c]; }
+    }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) { s0 += __shfl_xor(s0, m, 64); s1 += __shfl_xor(s1, m, 64); }
-  if (lane == 0) { red[wave][0] = s0; red[wave][1] = s1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tot[16];
-    tot[0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-    for (int c = 0; c < 12; ++c) tot[1 + c] = red[4 + c][0];
-    tot[13] = red[1][1]; tot[14] = red[2][1]; tot[15] = red[3][1];
-    const double dot = tot[0];
-    const double* su = &tot[1];
-    const double* sv = &tot[7];
-    const double sp1 = tot[13], s22 = tot[14], sdd = tot[15];
-    const double acc0 = a.acc[0] + (a.sweep_stats ? red[4][1] : 0.0), acc1 = a.acc[1] + (a.sweep_stats ? red[5][1] : 0.0), acc2 = a.acc[2] + (a.sweep_stats ? red[6][1] : 0.0);
-    const double srp = acc0, sp = sp1 - acc1, spp = dot - acc2;
-    const double n = a.n_obs;
-    const double sse = a.sumR2 - 2.0 * srp + spp;
-    const double esd = sse + (s22 - sv[4]) - (sdd - sv[5]) + red[0][1];
-    const double alpha_s = a.alpha + 0.5 * n, beta_s = a.beta + 0.5 * esd;
-    const double exptau = alpha_s / beta_s;
-    *a.tau_d = exptau; *a.tau_f = (float)exptau;
-    const double ss_tot = a.sumR2 - a.sumR * a.sumR / n;
-    const double cov = srp - a.sumR * sp / n, vp = spp - sp * sp / n;
-    a.rec[0] = exptau; a.rec[1] = sse / n;
-    a.rec[2] = ss_tot != 0.0 ? 1.0 - sse / ss_tot : __longlong_as_double(0x7ff0000000000000LL);
-    a.rec[3] = cov / (sqrt(ss_tot) * sqrt(vp));
-    a.rec[4] = esd; a.rec[5] = beta_s;
-    for (int c = 0; c < 4; ++c) { a.rec[6 + c] = su[c]; a.rec[10 + c] = sv[c]; }
-  }
-}
-__global__ __launch_bounds__(1024) void vb_finish_kernel(VbFinishArgs a) { vb_finish_body(a); }
-// list form (many.h): blockIdx.z = model; rec = the run's first record, the iteration's one is `it` records behind it
-__global__ __launch_bounds__(1024) void vb_finish_many(const VbFinishArgs* list, int it) {
-  VbFinishArgs a = load_pack(list, blockIdx.z);
-  a.rec += (size_t)it * 16;
-  vb_finish_body(a);
-}
-void launch_vb_finish(const VbFinishArgs& a, hipStream_t st) {
-  if (record_launch((const void*)vb_finish_many, dim3(1), dim3(1024), 0, a)) return;     // (recording: the caller passes the run's FIRST record)
-  hipLaunchKernelGGL(vb_finish_kernel, dim3(1), dim3(1024), 0, st, a);
-}
+};
+void launch_vb_finish(const VbFinishArgs& a, hipStream_t st) { launch_forms<VbFinish>(a, st); }
 
 void launch_finish(const FinishArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(kFinishThreads), 0, st, a);

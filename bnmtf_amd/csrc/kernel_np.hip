@@ -1,6 +1,6 @@
 // Non-probabilistic NMF / NMTF (nmf_np.py, Lee-Seung; nmtf_np.py, Yoo-Choi): multiplicative updates.
 //
-// The half sweep (np_sweep_kernel) is the hot path: U_ik *= (sum_{j in Omega_i} V_jk R_ij / P_ij) / (sum_{j in Omega_i} V_jk),
+// The half sweep (NpSweep) is the hot path: U_ik *= (sum_{j in Omega_i} V_jk R_ij / P_ij) / (sum_{j in Omega_i} V_jk),
 // column after column, with P = U V^T moved by every column's change.  Given V the rows of U are independent, so a block owns
 // RB rows: their data and their P live in registers (thread t holds the inner indices t + T e, e < E, of every row), the
 // block's U rows in LDS.  P is rebuilt from U and V at the start of every half sweep (no P in HBM, no drift carried from one half
@@ -76,102 +76,99 @@ __device__ void np_block_stats(double* s, double* out) {
   }
 }
 
-// The half sweep of the RB rows from blockIdx.x * RB (np_sweep_kernel, and np_sweep_many for a model of a list).
+__host__ __device__ inline int np_row_blocks(int n, int RB) { return (n + RB - 1) / RB; }
+
+// The half sweep of the RB rows from blockIdx.x * RB (both forms: many.h).
 template <int E, int RB>
-__device__ __forceinline__ void np_sweep_body(const NpSweepArgs& a) {
-  extern __shared__ float xs[];                               // [RB][K] the block's rows of X
-  __shared__ float red[kNpMaxWaves][2 * RB];
-  __shared__ float delta[RB];
-  const int T = blockDim.x, t = threadIdx.x, lane = t & 63, w = t >> 6, nw = T >> 6;
-  const int u0 = blockIdx.x * RB, K = a.K, m = a.m;
-  float R[RB][E], P[RB][E], y[E];
-#pragma unroll
-  for (int r = 0; r < RB; ++r)
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int j = t + T * e;
-      R[r][e] = (u0 + r < a.n && j < m) ? a.Rn[(size_t)(u0 + r) * m + j] : __builtin_nanf("");
-      P[r][e] = 0.f;
-    }
-  for (int q = t; q < RB * K; q += T) {
-    const int r = q / K, k = q - r * K;
-    xs[q] = u0 + r < a.n ? a.Xt[(size_t)k * a.n + u0 + r] : 0.f;
-  }
-  __syncthreads();
-  // P of the block's rows from X and Y
-  for (int k = 0; k < K; ++k) {
-#pragma unroll
-    for (int e = 0; e < E; ++e) { const int j = t + T * e; y[e] = j < m ? a.Yt[(size_t)k * m + j] : 0.f; }
-#pragma unroll
-    for (int r = 0; r < RB; ++r) {
-      const float x = xs[r * K + k];
-#pragma unroll
-      for (int e = 0; e < E; ++e) P[r][e] = fmaf(x, y[e], P[r][e]);
-    }
-  }
-  // the columns k0 .. k1-1, in order
-  for (int k = a.k0; k < a.k1; ++k) {
-#pragma unroll
-    for (int e = 0; e < E; ++e) { const int j = t + T * e; y[e] = j < m ? a.Yt[(size_t)k * m + j] : 0.f; }
-#pragma unroll
-    for (int r = 0; r < RB; ++r) {
-      float num = 0.f, den = 0.f;
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const bool obs = R[r][e] == R[r][e];
-        const float q = obs ? R[r][e] * __builtin_amdgcn_rcpf(P[r][e]) : 0.f;
-        num = fmaf(y[e], q, num);
-        den += obs ? y[e] : 0.f;
-      }
-      num = wave_sum(num); den = wave_sum(den);
-      if (lane == 0) { red[w][2 * r] = num; red[w][2 * r + 1] = den; }
-    }
-    __syncthreads();
-    if (t < RB) {
-      float d = 0.f;
-      if (u0 + t < a.n) {
-        double nu = 0.0, de = 0.0;
-        for (int q = 0; q < nw; ++q) { nu += (double)red[q][2 * t]; de += (double)red[q][2 * t + 1]; }
-        const float x = xs[t * K + k];
-        const float nx = (float)((double)x * nu / de);
-        d = nx - x;
-        xs[t * K + k] = nx;
-      }
-      delta[t] = d;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RB; ++r) {
-      const float d = delta[r];
-#pragma unroll
-      for (int e = 0; e < E; ++e) P[r][e] = fmaf(d, y[e], P[r][e]);
-    }
-  }
-  for (int q = t; q < RB * K; q += T) {
-    const int r = q / K, k = q - r * K;
-    if (u0 + r < a.n && k >= a.k0 && k < a.k1) a.Xt[(size_t)k * a.n + u0 + r] = xs[q];
-  }
-  if (a.stats) {                                              // the iteration's metrics from the final P
-    double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+struct NpSweep {
+  typedef NpSweepArgs Args;
+  static constexpr int kThreads = 1024;
+  static __host__ __device__ int blocks(const Args& a) { return np_row_blocks(a.n, RB); }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) {
+    extern __shared__ float xs[];                               // [RB][K] the block's rows of X
+    __shared__ float red[kNpMaxWaves][2 * RB];
+    __shared__ float delta[RB];
+    const int T = blockDim.x, t = threadIdx.x, lane = t & 63, w = t >> 6, nw = T >> 6;
+    const int u0 = blockIdx.x * RB, K = a.K, m = a.m;
+    float R[RB][E], P[RB][E], y[E];
 #pragma unroll
     for (int r = 0; r < RB; ++r)
 #pragma unroll
-      for (int e = 0; e < E; ++e)
-        if (R[r][e] == R[r][e]) np_entry_stats(s, R[r][e], P[r][e]);
-    np_block_stats(s, a.stats + (size_t)blockIdx.x * 8);
+      for (int e = 0; e < E; ++e) {
+        const int j = t + T * e;
+        R[r][e] = (u0 + r < a.n && j < m) ? a.Rn[(size_t)(u0 + r) * m + j] : __builtin_nanf("");
+        P[r][e] = 0.f;
+      }
+    for (int q = t; q < RB * K; q += T) {
+      const int r = q / K, k = q - r * K;
+      xs[q] = u0 + r < a.n ? a.Xt[(size_t)k * a.n + u0 + r] : 0.f;
+    }
+    __syncthreads();
+    // P of the block's rows from X and Y
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+      for (int e = 0; e < E; ++e) { const int j = t + T * e; y[e] = j < m ? a.Yt[(size_t)k * m + j] : 0.f; }
+#pragma unroll
+      for (int r = 0; r < RB; ++r) {
+        const float x = xs[r * K + k];
+#pragma unroll
+        for (int e = 0; e < E; ++e) P[r][e] = fmaf(x, y[e], P[r][e]);
+      }
+    }
+    // the columns k0 .. k1-1, in order
+    for (int k = a.k0; k < a.k1; ++k) {
+#pragma unroll
+      for (int e = 0; e < E; ++e) { const int j = t + T * e; y[e] = j < m ? a.Yt[(size_t)k * m + j] : 0.f; }
+#pragma unroll
+      for (int r = 0; r < RB; ++r) {
+        float num = 0.f, den = 0.f;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          const bool obs = R[r][e] == R[r][e];
+          const float q = obs ? R[r][e] * __builtin_amdgcn_rcpf(P[r][e]) : 0.f;
+          num = fmaf(y[e], q, num);
+          den += obs ? y[e] : 0.f;
+        }
+        num = wave_sum(num); den = wave_sum(den);
+        if (lane == 0) { red[w][2 * r] = num; red[w][2 * r + 1] = den; }
+      }
+      __syncthreads();
+      if (t < RB) {
+        float d = 0.f;
+        if (u0 + t < a.n) {
+          double nu = 0.0, de = 0.0;
+          for (int q = 0; q < nw; ++q) { nu += (double)red[q][2 * t]; de += (double)red[q][2 * t + 1]; }
+          const float x = xs[t * K + k];
+          const float nx = (float)((double)x * nu / de);
+          d = nx - x;
+          xs[t * K + k] = nx;
+        }
+        delta[t] = d;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < RB; ++r) {
+        const float d = delta[r];
+#pragma unroll
+        for (int e = 0; e < E; ++e) P[r][e] = fmaf(d, y[e], P[r][e]);
+      }
+    }
+    for (int q = t; q < RB * K; q += T) {
+      const int r = q / K, k = q - r * K;
+      if (u0 + r < a.n && k >= a.k0 && k < a.k1) a.Xt[(size_t)k * a.n + u0 + r] = xs[q];
+    }
+    if (a.stats) {                                              // the iteration's metrics from the final P
+      double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+      for (int r = 0; r < RB; ++r)
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+          if (R[r][e] == R[r][e]) np_entry_stats(s, R[r][e], P[r][e]);
+      np_block_stats(s, a.stats + (size_t)blockIdx.x * 8);
+    }
   }
-}
-
-template <int E, int RB>
-__global__ __launch_bounds__(1024) void np_sweep_kernel(NpSweepArgs a) { np_sweep_body<E, RB>(a); }
-
-// list form (many.h): blockIdx.z = model; grid.x is the largest block count of the launch, a model's surplus blocks leave
-template <int E, int RB>
-__global__ __launch_bounds__(1024) void np_sweep_many(const NpSweepArgs* list, int) {
-  const NpSweepArgs a = load_pack(list, blockIdx.z);
-  if ((int)blockIdx.x * RB >= a.n) return;
-  np_sweep_body<E, RB>(a);
-}
+};
 
 // Configuration of a half sweep over n units of inner extent m: E entries per thread and row, T threads, RB rows per block
 // (E RB = 32 values of R and of P per thread; 16 for the longest rows, whose 1 024-thread blocks leave 128 registers a lane).
@@ -186,7 +183,7 @@ static void np_sweep_shape(int m, int* E, int* T, int* RB) {
 int np_sweep_blocks(int n, int m) {
   int E, T, RB;
   np_sweep_shape(m, &E, &T, &RB);
-  return (n + RB - 1) / RB;
+  return np_row_blocks(n, RB);
 }
 
 bool np_sweep_supported(int m, int K) {
@@ -198,19 +195,12 @@ bool np_sweep_supported(int m, int K) {
 void launch_np_sweep(const NpSweepArgs& a, hipStream_t st) {
   int E, T, RB;
   np_sweep_shape(a.m, &E, &T, &RB);
-  const int nb = (a.n + RB - 1) / RB;
   const size_t lds = (size_t)RB * a.K * sizeof(float);
-  if (g_recorder) {
-    const void* fn = E == 2 ? (const void*)np_sweep_many<2, 16> : E == 4 ? (const void*)np_sweep_many<4, 8>
-                   : E == 8 ? (const void*)np_sweep_many<8, 4> : (const void*)np_sweep_many<16, 1>;
-    record_launch(fn, dim3(nb), dim3(T), lds, a, true);
-    return;
-  }
   switch (E) {
-    case 2: np_sweep_kernel<2, 16><<<nb, T, lds, st>>>(a); break;
-    case 4: np_sweep_kernel<4, 8><<<nb, T, lds, st>>>(a); break;
-    case 8: np_sweep_kernel<8, 4><<<nb, T, lds, st>>>(a); break;
-    default: np_sweep_kernel<16, 1><<<nb, T, lds, st>>>(a); break;
+    case 2: launch_forms<NpSweep<2, 16>>(a, st, T, lds); break;
+    case 4: launch_forms<NpSweep<4, 8>>(a, st, T, lds); break;
+    case 8: launch_forms<NpSweep<8, 4>>(a, st, T, lds); break;
+    default: launch_forms<NpSweep<16, 1>>(a, st, T, lds); break;
   }
 }
 
@@ -235,24 +225,19 @@ __device__ __forceinline__ void np_stats_finish_body(const double* __restrict__ 
     __syncthreads();
   }
 }
-__global__ __launch_bounds__(256) void np_stats_finish_kernel(const double* __restrict__ part, int nb, double* __restrict__ out) {
-  np_stats_finish_body(part, nb, out);
-}
-// list form: out = the run's FIRST record, the iteration's one is `it` records behind it (the argument list stays the same)
-struct NpStatsFinishPack { const double* part; double* out; int nb, pad; };
-__global__ __launch_bounds__(256) void np_stats_finish_many(const NpStatsFinishPack* list, int it) {
-  const NpStatsFinishPack p = load_pack(list, blockIdx.z);
-  np_stats_finish_body(p.part, p.nb, p.out + (size_t)it * 8);
-}
+// (out = the run's FIRST record, the iteration's one is `it` records behind it: a recorded argument list stays the same)
+struct NpStatsFinish {
+  struct Args { const double* part; double* out; int nb, pad; };
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args&) { return 1; }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int it) { np_stats_finish_body(a.part, a.nb, a.out + (size_t)it * 8); }
+};
 
 void launch_np_stats_finish(const double* part, int nb, double* out, hipStream_t st) {
-  if (g_recorder) {                                           // (recording: the caller passes the run's first record)
-    NpStatsFinishPack p; memset(&p, 0, sizeof(p));
-    p.part = part; p.out = out; p.nb = nb;
-    record_launch((const void*)np_stats_finish_many, dim3(1), dim3(256), 0, p);
-    return;
-  }
-  np_stats_finish_kernel<<<1, 256, 0, st>>>(part, nb, out);
+  NpStatsFinish::Args a; memset(&a, 0, sizeof(a));
+  a.part = part; a.out = out; a.nb = nb;
+  launch_forms<NpStatsFinish>(a, st);
 }
 
 // out[c][x] = sum_a S[c sc + a sa] in[a][x]  (c < C, a < A, x < n): G S^T as [K][J] (sc = L, sa = 1) or (F S)^T as [L][I]
@@ -266,25 +251,18 @@ __device__ __forceinline__ void np_small_product_body(const float* __restrict__ 
   for (int q = 0; q < A; ++q) s = fmaf(S[c * sc + q * sa], in[(size_t)q * n + x], s);
   out[idx] = s;
 }
-__global__ __launch_bounds__(256) void np_small_product_kernel(const float* __restrict__ S, int sc, int sa, const float* __restrict__ in,
-                                                               int A, int C, int n, float* __restrict__ out) {
-  np_small_product_body(S, sc, sa, in, A, C, n, out);
-}
-struct NpProductPack { const float* S; const float* in; float* out; int sc, sa, A, C, n, pad; };
-__global__ __launch_bounds__(256) void np_small_product_many(const NpProductPack* list, int) {      // (surplus blocks: idx >= C n)
-  const NpProductPack p = load_pack(list, blockIdx.z);
-  np_small_product_body(p.S, p.sc, p.sa, p.in, p.A, p.C, p.n, p.out);
-}
+struct NpSmallProduct {
+  struct Args { const float* S; const float* in; float* out; int sc, sa, A, C, n, pad; };
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& a) { return (int)(((size_t)a.C * a.n + 255) / 256); }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) { np_small_product_body(a.S, a.sc, a.sa, a.in, a.A, a.C, a.n, a.out); }
+};
 
 void launch_np_small_product(const float* S, int sc, int sa, const float* in, int A, int C, int n, float* out, hipStream_t st) {
-  const size_t tot = (size_t)C * n;
-  if (g_recorder) {
-    NpProductPack p; memset(&p, 0, sizeof(p));
-    p.S = S; p.in = in; p.out = out; p.sc = sc; p.sa = sa; p.A = A; p.C = C; p.n = n;
-    record_launch((const void*)np_small_product_many, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, p, true);
-    return;
-  }
-  np_small_product_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(S, sc, sa, in, A, C, n, out);
+  NpSmallProduct::Args a; memset(&a, 0, sizeof(a));
+  a.S = S; a.in = in; a.out = out; a.sc = sc; a.sa = sa; a.A = A; a.C = C; a.n = n;
+  launch_forms<NpSmallProduct>(a, st);
 }
 
 // P[i][j] = sum_k Ut[k][i] Yt[k][j] on the observed entries (NMTF's S step keeps P in memory).
@@ -298,111 +276,97 @@ __device__ __forceinline__ void np_build_p_body(const float* __restrict__ Rn, co
   for (int k = 0; k < K; ++k) s = fmaf(Ut[(size_t)k * I + i], Yt[(size_t)k * J + j], s);
   P[o] = s;
 }
-__global__ __launch_bounds__(256) void np_build_p_kernel(const float* __restrict__ Rn, const float* __restrict__ Ut, const float* __restrict__ Yt,
-                                                         int I, int J, int K, float* __restrict__ P) {
-  np_build_p_body(Rn, Ut, Yt, I, J, K, P, blockIdx.y, blockIdx.x * 256 + threadIdx.x);
-}
-// list form: a one-dimensional grid of I row groups of (J + 255) / 256 blocks each (the models of a launch differ in I and J)
-struct NpBuildPPack { const float* Rn; const float* Ut; const float* Yt; float* P; int I, J, K, pad; };
-__global__ __launch_bounds__(256) void np_build_p_many(const NpBuildPPack* list, int) {
-  const NpBuildPPack p = load_pack(list, blockIdx.z);
-  const int bj = (p.J + 255) / 256;
-  if ((int)blockIdx.x >= p.I * bj) return;
-  const int i = (int)blockIdx.x / bj, jb = (int)blockIdx.x - i * bj;
-  np_build_p_body(p.Rn, p.Ut, p.Yt, p.I, p.J, p.K, p.P, i, jb * 256 + threadIdx.x);
-}
+// A one-dimensional grid of I row groups of (J + 255) / 256 blocks each (the models of a launch differ in I and J).
+struct NpBuildP {
+  struct Args { const float* Rn; const float* Ut; const float* Yt; float* P; int I, J, K, pad; };
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int row_blocks(const Args& a) { return (a.J + 255) / 256; }
+  static __host__ __device__ int blocks(const Args& a) { return a.I * row_blocks(a); }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) {
+    const int bj = row_blocks(a), i = (int)blockIdx.x / bj, jb = (int)blockIdx.x - i * bj;
+    np_build_p_body(a.Rn, a.Ut, a.Yt, a.I, a.J, a.K, a.P, i, jb * 256 + threadIdx.x);
+  }
+};
 
 void launch_np_build_p(const float* Rn, const float* Ut, const float* Yt, int I, int J, int K, float* P, hipStream_t st) {
-  if (g_recorder) {
-    NpBuildPPack p; memset(&p, 0, sizeof(p));
-    p.Rn = Rn; p.Ut = Ut; p.Yt = Yt; p.P = P; p.I = I; p.J = J; p.K = K;
-    record_launch((const void*)np_build_p_many, dim3((unsigned)(I * ((J + 255) / 256))), dim3(256), 0, p, true);
-    return;
-  }
-  dim3 g((J + 255) / 256, I);
-  np_build_p_kernel<<<g, 256, 0, st>>>(Rn, Ut, Yt, I, J, K, P);
+  NpBuildP::Args a; memset(&a, 0, sizeof(a));
+  a.Rn = Rn; a.Ut = Ut; a.Yt = Yt; a.P = P; a.I = I; a.J = J; a.K = K;
+  launch_forms<NpBuildP>(a, st);
 }
 
 // One pass of NMTF's S step (nmtf_np.py:169-174).  A pass first finishes entry `prev` (if >= 0) -- every block sums the previous
 // pass's block partials in the same order, so all agree on its new value -- and moves P by dS F[:, k'] G[:, l']^T, then
 // accumulates entry `cur`'s (if >= 0) numerator sum F_ik G_jl R_ij / P_ij and denominator sum F_ik G_jl over the observed entries.
 // S_in holds the values at the start of the step (read only); S_out receives each entry as it is finished.
-// (nb: the pass's block count -- the stride of the rows and the number of partials -- gridDim.x of the single-model launch)
-__device__ __forceinline__ void np_s_pass_body(const NpSPassArgs& a, int nb) {
-  __shared__ double red[256][2];
-  __shared__ float s_delta;
-  const int t = threadIdx.x;
-  const int I = a.I, J = a.J;
-  const int kp = a.prev >= 0 ? a.prev / a.L : 0, lp = a.prev >= 0 ? a.prev % a.L : 0;
-  if (a.prev >= 0) {
-    double nu = 0.0, de = 0.0;
-    for (int b = t; b < nb; b += 256) { nu += a.part_prev[(size_t)b * 2]; de += a.part_prev[(size_t)b * 2 + 1]; }
+// (nb: the pass's block count np_s_blocks(I) -- the stride of the rows and the number of partials)
+struct NpSPass {
+  typedef NpSPassArgs Args;
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& a) { return np_s_blocks(a.I); }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int nb, int) {
+    __shared__ double red[256][2];
+    __shared__ float s_delta;
+    const int t = threadIdx.x;
+    const int I = a.I, J = a.J;
+    const int kp = a.prev >= 0 ? a.prev / a.L : 0, lp = a.prev >= 0 ? a.prev % a.L : 0;
+    if (a.prev >= 0) {
+      double nu = 0.0, de = 0.0;
+      for (int b = t; b < nb; b += 256) { nu += a.part_prev[(size_t)b * 2]; de += a.part_prev[(size_t)b * 2 + 1]; }
+      red[t][0] = nu; red[t][1] = de;
+      __syncthreads();
+      for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) { red[t][0] += red[t + h][0]; red[t][1] += red[t + h][1]; }
+        __syncthreads();
+      }
+      if (t == 0) {
+        const float s0 = a.S_in[a.prev];
+        const float s1 = (float)((double)s0 * red[0][0] / red[0][1]);
+        s_delta = s1 - s0;
+        if (blockIdx.x == 0) a.S_out[a.prev] = s1;
+      }
+      __syncthreads();
+    }
+    const float d = a.prev >= 0 ? s_delta : 0.f;
+    if (a.cur < 0) {                                            // only the change of entry prev
+      for (int i = blockIdx.x; i < I; i += nb) {
+        const float fp = d * a.Ft[(size_t)kp * I + i];
+        for (int j = t; j < J; j += 256) {
+          const size_t o = (size_t)i * J + j;
+          const float r = a.Rn[o];
+          if (r == r) a.P[o] = fmaf(fp, a.Gt[(size_t)lp * J + j], a.P[o]);
+        }
+      }
+      return;
+    }
+    const int k = a.cur / a.L, l = a.cur % a.L;
+    float nu = 0.f, de = 0.f;
+    for (int i = blockIdx.x; i < I; i += nb) {
+      const float fp = d * a.Ft[(size_t)kp * I + i], fk = a.Ft[(size_t)k * I + i];
+      for (int j = t; j < J; j += 256) {
+        const size_t o = (size_t)i * J + j;
+        const float r = a.Rn[o];
+        if (!(r == r)) continue;
+        float p = a.P[o];
+        if (a.prev >= 0) { p = fmaf(fp, a.Gt[(size_t)lp * J + j], p); a.P[o] = p; }
+        const float wgt = fk * a.Gt[(size_t)l * J + j];
+        nu = fmaf(wgt, r * __builtin_amdgcn_rcpf(p), nu);
+        de += wgt;
+      }
+    }
+    __syncthreads();                                            // (red is reused)
     red[t][0] = nu; red[t][1] = de;
     __syncthreads();
     for (int h = 128; h > 0; h >>= 1) {
       if (t < h) { red[t][0] += red[t + h][0]; red[t][1] += red[t + h][1]; }
       __syncthreads();
     }
-    if (t == 0) {
-      const float s0 = a.S_in[a.prev];
-      const float s1 = (float)((double)s0 * red[0][0] / red[0][1]);
-      s_delta = s1 - s0;
-      if (blockIdx.x == 0) a.S_out[a.prev] = s1;
-    }
-    __syncthreads();
+    if (t == 0) { a.part_cur[(size_t)blockIdx.x * 2] = red[0][0]; a.part_cur[(size_t)blockIdx.x * 2 + 1] = red[0][1]; }
   }
-  const float d = a.prev >= 0 ? s_delta : 0.f;
-  if (a.cur < 0) {                                            // only the change of entry prev
-    for (int i = blockIdx.x; i < I; i += nb) {
-      const float fp = d * a.Ft[(size_t)kp * I + i];
-      for (int j = t; j < J; j += 256) {
-        const size_t o = (size_t)i * J + j;
-        const float r = a.Rn[o];
-        if (r == r) a.P[o] = fmaf(fp, a.Gt[(size_t)lp * J + j], a.P[o]);
-      }
-    }
-    return;
-  }
-  const int k = a.cur / a.L, l = a.cur % a.L;
-  float nu = 0.f, de = 0.f;
-  for (int i = blockIdx.x; i < I; i += nb) {
-    const float fp = d * a.Ft[(size_t)kp * I + i], fk = a.Ft[(size_t)k * I + i];
-    for (int j = t; j < J; j += 256) {
-      const size_t o = (size_t)i * J + j;
-      const float r = a.Rn[o];
-      if (!(r == r)) continue;
-      float p = a.P[o];
-      if (a.prev >= 0) { p = fmaf(fp, a.Gt[(size_t)lp * J + j], p); a.P[o] = p; }
-      const float wgt = fk * a.Gt[(size_t)l * J + j];
-      nu = fmaf(wgt, r * __builtin_amdgcn_rcpf(p), nu);
-      de += wgt;
-    }
-  }
-  __syncthreads();                                            // (red is reused)
-  red[t][0] = nu; red[t][1] = de;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (t < h) { red[t][0] += red[t + h][0]; red[t][1] += red[t + h][1]; }
-    __syncthreads();
-  }
-  if (t == 0) { a.part_cur[(size_t)blockIdx.x * 2] = red[0][0]; a.part_cur[(size_t)blockIdx.x * 2 + 1] = red[0][1]; }
-}
+};
 
-int np_s_blocks(int I) { return I < 1024 ? I : 1024; }
-
-__global__ __launch_bounds__(256) void np_s_pass_kernel(NpSPassArgs a) { np_s_pass_body(a, gridDim.x); }
-// list form: the model's own block count np_s_blocks(I), its surplus blocks leave
-__global__ __launch_bounds__(256) void np_s_pass_many(const NpSPassArgs* list, int) {
-  const NpSPassArgs a = load_pack(list, blockIdx.z);
-  const int nb = a.I < 1024 ? a.I : 1024;                     // np_s_blocks(I)
-  if ((int)blockIdx.x >= nb) return;
-  np_s_pass_body(a, nb);
-}
-
-void launch_np_s_pass(const NpSPassArgs& a, hipStream_t st) {
-  if (record_launch((const void*)np_s_pass_many, dim3(np_s_blocks(a.I)), dim3(256), 0, a, true)) return;
-  np_s_pass_kernel<<<np_s_blocks(a.I), 256, 0, st>>>(a);
-}
+void launch_np_s_pass(const NpSPassArgs& a, hipStream_t st) { launch_forms<NpSPass>(a, st); }
 
 // dst[0 .. n) = src[0 .. n): the list form of the S step's device-to-device copy (a copy cannot be recorded)
 struct NpCopyPack { const float* src; float* dst; int n, pad; };

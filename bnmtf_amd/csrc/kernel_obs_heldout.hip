@@ -4,8 +4,8 @@
 // iteration's finish kernel on the handle's stream.
 //
 // Operands: the two-factor handle's row-major fp32 factors, rows.X [I][stride] and cols.X [J][stride], stride = K rounded up to 4,
-// K <= kObsMaxRank (for the variational model: the expectations).  Neither kernel of kernel_heldout.hip reads them: heldout_kernel
-// is tied to a row stride of 32 or 64, heldout_np_kernel to column-major factors.
+// K <= kObsMaxRank (for the variational model: the expectations).  Neither kernel of kernel_heldout.hip reads them: Heldout
+// is tied to a row stride of 32 or 64, HeldoutNp to column-major factors.
 //
 // Layout, as heldout_np_body's.  A wave owns one row i (kObsHeldoutRows consecutive rows per block, heldout_blocks(I) blocks: no
 // grid stride).  The row's factor row is staged once in LDS as doubles ([4][256], 8 KiB) and read by broadcast: every lane of a
@@ -16,7 +16,7 @@
 // index and value of the lane's next entry are fetched before the current entry's arithmetic.
 //
 // Order of the sums (fixed: two runs give the same bits, no floating-point atomics): a lane's entries in list order; a butterfly
-// over the wave; the block's waves in wave order; heldout_fold_kernel (launch_fold) over the blocks' partials.
+// over the wave; the block's waves in wave order; HeldoutFold (launch_fold) over the blocks' partials.
 #include "obs_common.h"
 
 namespace bnmtf {

@@ -8,7 +8,7 @@
 //   Phase 1  P = x . Xo_j for every entry, from whole rows of the other factor (row major [m][KP], float4 loads): no P is carried
 //            between half sweeps.
 //   Phase 2  per column: gather v = XoT[k][j], per-lane fp32 partials of sum v (r rcp(p)) and sum v in entry order -- the quotient
-//            as np_sweep_kernel takes it, r times the hardware reciprocal of p --, a butterfly over the wave (every lane ends with
+//            as NpSweep takes it, r times the hardware reciprocal of p --, a butterfly over the wave (every lane ends with
 //            the same bits), x_k' = (float)((double)x_k num / den) in every lane alike, then p += (x_k' - x_k) v.
 // Every per-entry loop is written once, on the unit's two forms (obs_common.h, "the contract"), with P in the place of the
 // residual: the register form keeps p, r, j and v, and a slot without an entry holds r = 0 and p = 1 -- it adds +0 to both sums;
@@ -19,7 +19,7 @@
 // t + 256, ..., then a tree -- into the iteration's record.  No floating-point atomics anywhere.
 //
 // onp_eff_kernel: NMTF's effective factors G S^T and F S, fp32, any K, L <= 256, in both forms.
-// onp_s_pass_kernel: one pass of NMTF's S step (np_s_pass_kernel's scheme on the row list): a wave owns a row, the lanes run along
+// onp_s_pass_kernel: one pass of NMTF's S step (NpSPass's scheme on the row list): a wave owns a row, the lanes run along
 // its entries; P per entry in escratch in row-list order; a pass sums the previous pass's block partials -- every block in the same
 // order, block 0 stores S --, moves P by that entry's change and sums the next entry's numerator and denominator.
 // onp_metric_kernel: the eight sums over an arbitrary entry list, P in fp64 from the fp32 factors ((F_i S) . G_j with F_i S in fp64).

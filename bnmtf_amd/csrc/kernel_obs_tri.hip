@@ -21,7 +21,7 @@
 // fmaf, and the halves are added by one exchange.  An entry past the column's end contributes F = 0, R = 0 (+0 into sums that
 // are never -0).  Nothing is atomic, nothing depends on the launch: two runs give the same bits.  The F rows come straight from
 // global memory, one float per lane (a 128-byte row per half and load), no LDS.  The loop is software-pipelined as
-// scol_gram_kernel's is: a trip's rows are loaded while the trip before it multiplies, its indices a trip earlier still (without
+// SColGram's is: a trip's rows are loaded while the trip before it multiplies, its indices a trip earlier still (without
 // that a 4096-column launch at 411 entries per column took 97 us: 26 dependent index -> row -> MFMA round trips per wave).
 #include "obs_common.h"
 

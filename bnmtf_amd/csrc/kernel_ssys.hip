@@ -10,9 +10,9 @@
 //                                         = (F^T F)[k][k'] - sum_{i in miss(j)} F_ik F_ik'   (a K x K matrix per column).
 // W_j and G_j G_j^T are symmetric: with their upper triangles packed (p = (k <= k'), r = (l <= l'); tri_index, kernels.h)
 // the whole system is one plain GEMM, A[p][r] = sum_j Wc[j][p] Gc[j][r], written to its four symmetric places.
-// So an iteration costs one masked Gram per column (scol_gram_kernel: f32 MFMA over the ~10 % missing entries), the
-// packed second moments of G's rows (gamma_pack_kernel), one K(K+1)/2 x J x L(L+1)/2 GEMM (ssys_gemm_kernel: f32 MFMA,
-// partial slabs over column ranges, summed in a fixed order by ssys_reduce_kernel), and then the
+// So an iteration costs one masked Gram per column (SColGram: f32 MFMA over the ~10 % missing entries), the
+// packed second moments of G's rows (GammaPack), one K(K+1)/2 x J x L(L+1)/2 GEMM (ssys_gemm_kernel: f32 MFMA,
+// partial slabs over column ranges, summed in a fixed order by SSysReduce), and then the
 // K.L sequential conditionals touch nothing but A: ssys_chain_kernel keeps the residual r = b - A S on chip and walks the
 // entries row by row (a row of S = the lanes of one wave, the running correction of a lane grows by one FMA per step).
 // The variational version (second moments) is the same system with E[F_ik F_ik'] = F_ik F_ik' + [k = k'] varF_ik and
@@ -38,7 +38,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // their 64, the texture path takes ~9 cycles per wave-level load): per step one shift-add (row offset), one row load.
 // Everything else sits in buffer descriptors, scalar offsets and immediates.  Rows are loaded a batch (8 steps) ahead,
 // indices two.
-// (the three-term bf16 split of the round-6 matrix-core kernels below: ssys_gemm_bf16_kernel's comment)
+// (the three-term bf16 split of the round-6 matrix-core kernels below: SSysGemmBf16's comment)
 namespace {
 typedef __bf16 g_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 g_bf16x2 __attribute__((ext_vector_type(2)));
@@ -63,6 +63,8 @@ __device__ __forceinline__ void g_split3(const float (&v)[8], g_u32x4& hi, g_u32
   }
 }
 }  // namespace
+__host__ __device__ inline int scol_gram_col_blocks(int n) { return (n + 3) / 4; }       // a wave per column
+__host__ __device__ inline int gamma_pack_blocks(int n) { return (n + 7) / 8; }
 __device__ __forceinline__ void gamma_pack_body(const GammaPackArgs& a, int block);
 // (blocks behind the column Grams' pack the second moments of G's rows -- gamma_pack_body, below: the two do not depend on each
 // other, and one launch less is ~5 us of the S step)
@@ -70,11 +72,11 @@ __device__ __forceinline__ void ssys_b_body(const SSysBArgs& a, int block);
 // BF = 1 (round 6): the outer products on the bf16 matrix cores, fp32-exact -- a half's eight rows of a 16-slot step ARE the A (and
 // B) operand of v_mfma_f32_32x32x16_bf16 (lane (c, g) holds k = 8 g .. 8 g + 7), so the loads stay as they are and a step is one
 // three-term split of eight registers (g_split3) and six products (6 x 32 cycles) instead of eight f32 products (8 x 64).
-// (LIST: the list form's own instantiation -- a body shared by two kernels is inlined differently into each)
-template <int VB, int BF, int LIST>
+// (FORM: many.h -- each form its own instantiation)
+template <int VB, int BF, int FORM>
 __device__ __forceinline__ void scol_gram_body(SColGramArgs a, GammaPackArgs gp, SSysBArgs sb, unsigned block) {
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  const int gram_blocks = (a.n + 3) / 4, pack_blocks = (gp.n + 7) / 8;
+  const int gram_blocks = scol_gram_col_blocks(a.n), pack_blocks = gamma_pack_blocks(gp.n);
   // (... and behind those, the blocks of b = sum_j Pv_j (x) G_j: a third independent piece of the S system's build in this launch)
   if ((int)block >= gram_blocks + pack_blocks) { ssys_b_body(sb, (int)block - gram_blocks - pack_blocks); return; }
   if ((int)block >= gram_blocks) { gamma_pack_body(gp, (int)block - gram_blocks); return; }
@@ -144,7 +146,7 @@ __device__ __forceinline__ void scol_gram_body(SColGramArgs a, GammaPackArgs gp,
 #pragma unroll
   for (int t = 0; t < 16; ++t) acc[t] += acc2[t];
   dv += __shfl_xor(dv, 32, 64);
-  if (VB && a.var_obs_out && half == 0)      // sum_{i in Omega_j} varF_ik = total - missing: what the G sweep's covariance term reads (masked_colsum_kernel's output)
+  if (VB && a.var_obs_out && half == 0)      // sum_{i in Omega_j} varF_ik = total - missing: what the G sweep's covariance term reads (MaskedColsum's output)
     a.var_obs_out[(size_t)u * 32 + c] = c < a.K ? (float)(a.cf_diag_extra[c] - a.Cf64[(size_t)c * 32 + c]) - dv : 0.f;
   float* w = a.Wc + (size_t)u * tri_padded(a.K);
 #pragma unroll
@@ -161,42 +163,36 @@ __device__ __forceinline__ void scol_gram_body(SColGramArgs a, GammaPackArgs gp,
     if (row <= c && c < a.K) w[tri_pos(tri_index(row, c, a.K))] = cf - m;    // the upper triangle, packed: what the S-system GEMM reads
   }
 }
-template <int VB, int BF = 0>
-__global__ __launch_bounds__(256) void scol_gram_kernel(SColGramArgs a, GammaPackArgs gp, SSysBArgs sb) { scol_gram_body<VB, BF, 0>(a, gp, sb, blockIdx.x); }
-// list form (many.h): blockIdx.z = model; a model with fewer blocks than the launch leaves
-struct SColGramPack { SColGramArgs a; GammaPackArgs gp; SSysBArgs sb; };
-__host__ __device__ inline int scol_gram_blocks(const SColGramArgs& a, const GammaPackArgs& gp, const SSysBArgs* sb) {
-  return (a.n + 3) / 4 + (gp.n + 7) / 8 + (sb ? ((sb->n + 63) / 64 > 0 ? (sb->n + 63) / 64 : 1) : 0);      // (ssys_b_blocks)
-}
+// The bf16 form, in both forms.  gp.n == 0: no packing rides along; sb.b == nullptr: nor the blocks of b.
+struct SColGramForms {      // what the instances share
+  struct Args { SColGramArgs a; GammaPackArgs gp; SSysBArgs sb; };
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& p) { return scol_gram_col_blocks(p.a.n) + gamma_pack_blocks(p.gp.n) + (p.sb.b ? ssys_b_blocks(p.sb.n) : 0); }
+};
 template <int VB>
-__global__ __launch_bounds__(256) void scol_gram_many(const SColGramPack* list, int) {
-  const SColGramPack p = load_pack(list, blockIdx.z);
-  if ((int)blockIdx.x >= scol_gram_blocks(p.a, p.gp, p.sb.b ? &p.sb : nullptr)) return;
-  scol_gram_body<VB, 1, 1>(p.a, p.gp, p.sb, blockIdx.x);
-}
+struct SColGram : SColGramForms {
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& p, int, int) { scol_gram_body<VB, 1, FORM>(p.a, p.gp, p.sb, blockIdx.x); }
+};
 // BNMTF_SCOL_GRAM=f32: the f32 matrix-core form (A/B switch; no list form)
+template <int VB>
+__global__ __launch_bounds__(256) void scol_gram_f32_kernel(SColGramForms::Args p) { scol_gram_body<VB, 0, 0>(p.a, p.gp, p.sb, blockIdx.x); }
 static bool scol_gram_f32() { static const bool f32 = [] { const char* e = getenv("BNMTF_SCOL_GRAM"); return e && !strcmp(e, "f32"); }(); return f32; }
 // gp: the packing of G's second moments rides along (gp.n == 0: none); sb (may be null): and the blocks of b
 void launch_scol_gram(const SColGramArgs& a, const GammaPackArgs& gp, hipStream_t st, const SSysBArgs* sb) {
   if (a.n <= 0) return;
-  SSysBArgs b0 = {};
-  const int blocks = scol_gram_blocks(a, gp, sb);
-  const bool f32 = scol_gram_f32();
-  if (g_recorder) {
-    if (f32) { record_missing("scol_gram (BNMTF_SCOL_GRAM=f32)"); return; }
-    SColGramPack p; memset(&p, 0, sizeof(p));
-    p.a = a; p.gp = gp;
-    if (sb) p.sb = *sb;
-    record_launch(a.varF ? (const void*)scol_gram_many<1> : (const void*)scol_gram_many<0>, dim3(blocks), dim3(256), 0, p, true);
+  SColGramForms::Args p; memset(&p, 0, sizeof(p));
+  p.a = a; p.gp = gp;
+  if (sb) p.sb = *sb;
+  if (!scol_gram_f32()) {
+    if (a.varF) launch_forms<SColGram<1>>(p, st);
+    else        launch_forms<SColGram<0>>(p, st);
     return;
   }
-  if (f32) {
-    if (a.varF) hipLaunchKernelGGL((scol_gram_kernel<1, 0>), dim3(blocks), dim3(256), 0, st, a, gp, sb ? *sb : b0);
-    else        hipLaunchKernelGGL((scol_gram_kernel<0, 0>), dim3(blocks), dim3(256), 0, st, a, gp, sb ? *sb : b0);
-  } else {
-    if (a.varF) hipLaunchKernelGGL((scol_gram_kernel<1, 1>), dim3(blocks), dim3(256), 0, st, a, gp, sb ? *sb : b0);
-    else        hipLaunchKernelGGL((scol_gram_kernel<0, 1>), dim3(blocks), dim3(256), 0, st, a, gp, sb ? *sb : b0);
-  }
+  if (record_missing("scol_gram (BNMTF_SCOL_GRAM=f32)")) return;
+  const dim3 grid(SColGramForms::blocks(p));
+  if (a.varF) scol_gram_f32_kernel<1><<<grid, 256, 0, st>>>(p);
+  else        scol_gram_f32_kernel<0><<<grid, 256, 0, st>>>(p);
 }
 
 // Gc[j][r(l, l')] = G_jl G_jl' (l <= l'), the packed second-moment matrix of column j's row of G.  Block = 8 columns (512 blocks at 4096 columns: two per CU hide each other's load -> store latency).
@@ -219,16 +215,16 @@ __device__ __forceinline__ void gamma_pack_body(const GammaPackArgs& a, int bloc
       if (j0 + t < a.n) a.Gc[(size_t)(j0 + t) * PLp + pos] = fmaf(g[t][l], g[t][lp], l == lp ? v[t][l] : 0.f);
   }
 }
-__global__ __launch_bounds__(256) void gamma_pack_kernel(GammaPackArgs a) { gamma_pack_body(a, (int)blockIdx.x); }
-__global__ __launch_bounds__(256) void gamma_pack_many(const GammaPackArgs* list, int) {
-  const GammaPackArgs a = load_pack(list, blockIdx.z);
-  if ((int)blockIdx.x >= (a.n + 7) / 8) return;
-  gamma_pack_body(a, (int)blockIdx.x);
-}
+struct GammaPack {
+  typedef GammaPackArgs Args;
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& a) { return gamma_pack_blocks(a.n); }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) { gamma_pack_body(a, (int)blockIdx.x); }
+};
 void launch_gamma_pack(const GammaPackArgs& a, hipStream_t st) {
   if (a.n <= 0) return;
-  if (record_launch((const void*)gamma_pack_many, dim3((a.n + 7) / 8), dim3(256), 0, a, true)) return;
-  hipLaunchKernelGGL(gamma_pack_kernel, dim3((a.n + 7) / 8), dim3(256), 0, st, a);
+  launch_forms<GammaPack>(a, st);
 }
 
 // A on the packed pairs: slab[s][p][r] = sum_{j in range s} Wc[j][p] Gc[j][r], p = (k <= k'), r = (l <= l') -- with both
@@ -306,98 +302,96 @@ __global__ __launch_bounds__(256) void ssys_gemm_kernel(SSysGemmArgs a) {
 // of BOTH interleaved tiles) -- splits its four fragments (a0, a1, b0, b1) and issues the 24 products; the next step's rows are
 // on their way in a second register set meanwhile.  Ranges are cut at multiples of 16 columns; past a range's end the zero rows
 // behind the arrays are read.  Same tiles, same slab layout, same epilogue as ssys_gemm_kernel.
-template <int LIST>
-__device__ __forceinline__ void ssys_gemm_bf16_body(const SSysGemmArgs& a, unsigned block) {
-  const int lane = threadIdx.x & 63, half = lane >> 5, c = lane & 31;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int PKp = tri_padded(a.K), PLp = tri_padded(a.L), TR = PLp / 64;
-  const int wt = block * 4 + wave, sp = blockIdx.y;
-  if (wt >= (PKp / 64) * TR) return;
-  const int tp = wt / TR, tr = wt % TR;
-  const int per = ssys_gemm_range(a.n, a.nsplit);
-  const int jbeg = sp * per, jend = min(a.n, jbeg + per);
-  const int offA = 4 * (tp * 64 + 2 * c), offB = 4 * (tr * 64 + 2 * c);
-  const __amdgpu_buffer_rsrc_t rsA = panel_rsrc(a.Wc, (size_t)(a.n + 2) * PKp * 4), rsB = panel_rsrc(a.Gc, (size_t)(a.n + 2) * PLp * 4);
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int t = 0; t < 16; ++t) acc[x][y][t] = 0.f;
-  struct Raw { float a0[8], a1[8], b0[8], b1[8]; };
-  auto fetch = [&](int j0, Raw& r) {
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const int jj = j0 + 8 * half + t;
-      const int j = jj < jend ? jj : a.n;                            // (rows n, n + 1 are zero)
-      const f32x2 av = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsA, offA + j * PKp * 4, 0, 0));
-      const f32x2 bv = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsB, offB + j * PLp * 4, 0, 0));
-      r.a0[t] = av.x; r.a1[t] = av.y; r.b0[t] = bv.x; r.b1[t] = bv.y;
-    }
-  };
-  auto products = [&](const Raw& r) {
-    g_u32x4 ah[2], am[2], al[2], bh[2], bm[2], bl[2];
-    g_split3(r.a0, ah[0], am[0], al[0]); g_split3(r.a1, ah[1], am[1], al[1]);
-    g_split3(r.b0, bh[0], bm[0], bl[0]); g_split3(r.b1, bh[1], bm[1], bl[1]);
+// (grid.y: the column ranges, every model's own; a wave past the model's tiles leaves)
+struct SSysGemmBf16 {
+  typedef SSysGemmArgs Args;
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& a) { return (ssys_gemm_wave_tiles(a.K, a.L) + 3) / 4; }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) {
+    const unsigned block = blockIdx.x;
+    const int lane = threadIdx.x & 63, half = lane >> 5, c = lane & 31;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int PKp = tri_padded(a.K), PLp = tri_padded(a.L), TR = PLp / 64;
+    const int wt = block * 4 + wave, sp = blockIdx.y;
+    if (wt >= (PKp / 64) * TR) return;
+    const int tp = wt / TR, tr = wt % TR;
+    const int per = ssys_gemm_range(a.n, a.nsplit);
+    const int jbeg = sp * per, jend = min(a.n, jbeg + per);
+    const int offA = 4 * (tp * 64 + 2 * c), offB = 4 * (tr * 64 + 2 * c);
+    const __amdgpu_buffer_rsrc_t rsA = panel_rsrc(a.Wc, (size_t)(a.n + 2) * PKp * 4), rsB = panel_rsrc(a.Gc, (size_t)(a.n + 2) * PLp * 4);
+    f32x16 acc[2][2];
 #pragma unroll
     for (int x = 0; x < 2; ++x)
 #pragma unroll
-      for (int y = 0; y < 2; ++y) {
-        f32x16 d = acc[x][y];
-        d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g_bf16x8, al[x]), __builtin_bit_cast(g_bf16x8, bh[y]), d, 0, 0, 0);     // small terms first
-        d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g_bf16x8, ah[x]), __builtin_bit_cast(g_bf16x8, bl[y]), d, 0, 0, 0);
-        d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g_bf16x8, am[x]), __builtin_bit_cast(g_bf16x8, bm[y]), d, 0, 0, 0);
-        d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g_bf16x8, am[x]), __builtin_bit_cast(g_bf16x8, bh[y]), d, 0, 0, 0);
-        d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g_bf16x8, ah[x]), __builtin_bit_cast(g_bf16x8, bm[y]), d, 0, 0, 0);
-        d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g_bf16x8, ah[x]), __builtin_bit_cast(g_bf16x8, bh[y]), d, 0, 0, 0);
-        acc[x][y] = d;
+      for (int y = 0; y < 2; ++y)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) acc[x][y][t] = 0.f;
+    struct Raw { float a0[8], a1[8], b0[8], b1[8]; };
+    auto fetch = [&](int j0, Raw& r) {
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        const int jj = j0 + 8 * half + t;
+        const int j = jj < jend ? jj : a.n;                            // (rows n, n + 1 are zero)
+        const f32x2 av = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsA, offA + j * PKp * 4, 0, 0));
+        const f32x2 bv = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsB, offB + j * PLp * 4, 0, 0));
+        r.a0[t] = av.x; r.a1[t] = av.y; r.b0[t] = bv.x; r.b1[t] = bv.y;
       }
-  };
-  Raw r0, r1;
-  fetch(jbeg, r0);
-  for (int j0 = jbeg; j0 < jend; j0 += 32) {                        // two steps per trip: the register sets alternate without copies
-    fetch(j0 + 16, r1);                                             // (a step past the range multiplies zeros: no branch around the products)
-    __builtin_amdgcn_sched_barrier(0);
-    products(r0);
-    __builtin_amdgcn_sched_barrier(0);
-    fetch(j0 + 32, r0);
-    __builtin_amdgcn_sched_barrier(0);
-    products(r1);
-    __builtin_amdgcn_sched_barrier(0);
+    };
+    auto products = [&](const Raw& r) {
+      g_u32x4 ah[2], am[2], al[2], bh[2], bm[2], bl[2];
+      g_split3(r.a0, ah[0], am[0], al[0]); g_split3(r.a1, ah[1], am[1], al[1]);
+      g_split3(r.b0, bh[0], bm[0], bl[0]); g_split3(r.b1, bh[1], bm[1], bl[1]);
+#pragma unroll
+      for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) {
+          f32x16 d = acc[x][y];
+          d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g_bf16x8, al[x]), __builtin_bit_cast(g_bf16x8, bh[y]), d, 0, 0, 0);     // small terms first
+          d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g_bf16x8, ah[x]), __builtin_bit_cast(g_bf16x8, bl[y]), d, 0, 0, 0);
+          d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g_bf16x8, am[x]), __builtin_bit_cast(g_bf16x8, bm[y]), d, 0, 0, 0);
+          d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g_bf16x8, am[x]), __builtin_bit_cast(g_bf16x8, bh[y]), d, 0, 0, 0);
+          d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g_bf16x8, ah[x]), __builtin_bit_cast(g_bf16x8, bm[y]), d, 0, 0, 0);
+          d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g_bf16x8, ah[x]), __builtin_bit_cast(g_bf16x8, bh[y]), d, 0, 0, 0);
+          acc[x][y] = d;
+        }
+    };
+    Raw r0, r1;
+    fetch(jbeg, r0);
+    for (int j0 = jbeg; j0 < jend; j0 += 32) {                        // two steps per trip: the register sets alternate without copies
+      fetch(j0 + 16, r1);                                             // (a step past the range multiplies zeros: no branch around the products)
+      __builtin_amdgcn_sched_barrier(0);
+      products(r0);
+      __builtin_amdgcn_sched_barrier(0);
+      fetch(j0 + 32, r0);
+      __builtin_amdgcn_sched_barrier(0);
+      products(r1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    float* slab = a.slabs + (size_t)sp * PKp * PLp;
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int y = 0; y < 2; ++y)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+          const int row = tp * 64 + 32 * x + (t & 3) + 8 * (t >> 2) + 4 * half;
+          slab[(size_t)row * PLp + tr * 64 + 32 * y + c] = acc[x][y][t];
+        }
   }
-  float* slab = a.slabs + (size_t)sp * PKp * PLp;
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        const int row = tp * 64 + 32 * x + (t & 3) + 8 * (t >> 2) + 4 * half;
-        slab[(size_t)row * PLp + tr * 64 + 32 * y + c] = acc[x][y][t];
-      }
-}
-__global__ __launch_bounds__(256) void ssys_gemm_bf16_kernel(SSysGemmArgs a) { ssys_gemm_bf16_body<0>(a, blockIdx.x); }
-// list form: the launch's grid.y (the column ranges) is every model's own; a block past a model's tiles leaves in the body
-__global__ __launch_bounds__(256) void ssys_gemm_bf16_many(const SSysGemmArgs* list, int) { ssys_gemm_bf16_body<1>(load_pack(list, blockIdx.z), blockIdx.x); }
+};
 static bool ssys_gemm_f32() { const char* e = getenv("BNMTF_SSYS_GEMM"); return e && !strcmp(e, "f32"); }
 bool ssys_ab_switch_set() { return scol_gram_f32() || ssys_gemm_f32(); }
 void launch_ssys_gemm(const SSysGemmArgs& a, hipStream_t st) {
-  const dim3 grid((ssys_gemm_wave_tiles(a.K, a.L) + 3) / 4, a.nsplit);
-  const bool f32 = ssys_gemm_f32();                 // A/B switch: "f32" = the f32-MFMA form of rounds 2-5 (no list form)
-  if (g_recorder) {
-    if (f32) record_missing("ssys_gemm (BNMTF_SSYS_GEMM=f32)");
-    else record_launch((const void*)ssys_gemm_bf16_many, grid, dim3(256), 0, a, true);
-    return;
-  }
-  if (f32) hipLaunchKernelGGL(ssys_gemm_kernel, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(ssys_gemm_bf16_kernel, grid, dim3(256), 0, st, a);
+  if (!ssys_gemm_f32()) { launch_forms<SSysGemmBf16>(a, st, 256, 0, a.nsplit); return; }
+  // A/B switch: "f32" = the f32-MFMA form of rounds 2-5 (no list form)
+  if (record_missing("ssys_gemm (BNMTF_SSYS_GEMM=f32)")) return;
+  hipLaunchKernelGGL(ssys_gemm_kernel, dim3(SSysGemmBf16::blocks(a), a.nsplit), dim3(256), 0, st, a);
 }
 
 // A[(k,l)][(k',l')] = sum of the column-range slabs (in range order) at (p(k,k'), r(l,l')).  One block per packed pair p:
 // its row of the slabs is summed 16 bytes per thread, the two halves of the ranges by two threads (combined in a fixed
 // order), goes through LDS and comes out as the full L x L blocks (k,k') and (k',k), rows contiguous.
-template <int LIST>
 __device__ __forceinline__ void ssys_reduce_body(const float* slabs, int nsplit, int K, int L, float* A, unsigned block) {
   __shared__ __align__(16) float v[2][640];
   int k, kp; tri_unindex(block, K, &k, &kp);
@@ -419,29 +413,23 @@ __device__ __forceinline__ void ssys_reduce_body(const float* slabs, int nsplit,
     if (k != kp) A[(size_t)(kp * L + l) * n2 + k * L + lp] = x;
   }
 }
-__global__ __launch_bounds__(320) void ssys_reduce_kernel(const float* slabs, int nsplit, int K, int L, float* A) {
-  ssys_reduce_body<0>(slabs, nsplit, K, L, A, blockIdx.x);
-}
-struct SSysReducePack { const float* slabs; float* A; int nsplit, K, L, pad_; };
-__global__ __launch_bounds__(320) void ssys_reduce_many(const SSysReducePack* list, int) {
-  const SSysReducePack p = load_pack(list, blockIdx.z);
-  if ((int)blockIdx.x >= tri_count(p.K)) return;
-  ssys_reduce_body<1>(p.slabs, p.nsplit, p.K, p.L, p.A, blockIdx.x);
-}
+struct SSysReduce {
+  struct Args { const float* slabs; float* A; int nsplit, K, L, pad; };
+  static constexpr int kThreads = 320;
+  static __host__ __device__ int blocks(const Args& a) { return tri_count(a.K); }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) { ssys_reduce_body(a.slabs, a.nsplit, a.K, a.L, a.A, blockIdx.x); }
+};
 void launch_ssys_reduce(const float* slabs, int nsplit, int K, int L, float* A, hipStream_t st) {
-  if (g_recorder) {
-    SSysReducePack p; memset(&p, 0, sizeof(p));
-    p.slabs = slabs; p.A = A; p.nsplit = nsplit; p.K = K; p.L = L;
-    record_launch((const void*)ssys_reduce_many, dim3(tri_count(K)), dim3(320), 0, p, true);
-    return;
-  }
-  hipLaunchKernelGGL(ssys_reduce_kernel, dim3(tri_count(K)), dim3(320), 0, st, slabs, nsplit, K, L, A);
+  SSysReduce::Args a; memset(&a, 0, sizeof(a));
+  a.slabs = slabs; a.A = A; a.nsplit = nsplit; a.K = K; a.L = L;
+  launch_forms<SSysReduce>(a, st);
 }
 
 // b[k][l] = sum_j Pv_jk G_jl over the local columns (Pv = the contraction's partial slabs, summed in slab order).
 // Block = 64 columns: Pv and G tiles through LDS, thread (k, l) sums its 64 products; the per-block partials are summed
-// in block order by ssys_reduce_kernel.
-// (a body for blocks of 256 threads -- it rides in scol_gram_kernel's launch --: thread t takes the entries k = t / 32 + 8 i, l = t % 32)
+// in block order by SSysReduce.
+// (a body for blocks of 256 threads -- it rides in SColGram's launch --: thread t takes the entries k = t / 32 + 8 i, l = t % 32)
 __device__ __forceinline__ void ssys_b_body(const SSysBArgs& a, int block) {
   __shared__ float pv[64][33], g[64][33];
   const int j0 = block * 64;
@@ -473,16 +461,14 @@ __device__ __forceinline__ void ssys_b_body(const SSysBArgs& a, int block) {
   for (int i = 0; i < 4; ++i)
     if (k0 + 8 * i < a.K && l < a.L) a.b[(size_t)block * a.K * a.L + (k0 + 8 * i) * a.L + l] = s[i];
 }
-__global__ __launch_bounds__(256) void ssys_b_kernel(SSysBArgs a) { ssys_b_body(a, (int)blockIdx.x); }
-__global__ __launch_bounds__(256) void ssys_b_many(const SSysBArgs* list, int) {
-  const SSysBArgs a = load_pack(list, blockIdx.z);
-  if ((int)blockIdx.x >= ((a.n + 63) / 64 > 0 ? (a.n + 63) / 64 : 1)) return;     // (ssys_b_blocks)
-  ssys_b_body(a, (int)blockIdx.x);
-}
-void launch_ssys_b(const SSysBArgs& a, hipStream_t st) {
-  if (record_launch((const void*)ssys_b_many, dim3(ssys_b_blocks(a.n)), dim3(256), 0, a, true)) return;
-  hipLaunchKernelGGL(ssys_b_kernel, dim3(ssys_b_blocks(a.n)), dim3(256), 0, st, a);
-}
+struct SSysB {
+  typedef SSysBArgs Args;
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& a) { return ssys_b_blocks(a.n); }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) { ssys_b_body(a, (int)blockIdx.x); }
+};
+void launch_ssys_b(const SSysBArgs& a, hipStream_t st) { launch_forms<SSysB>(a, st); }
 
 // out = sum of the per-block partial vectors, in block order
 __global__ void ssys_sum_parts_kernel(const float* slabs, int nsplit, size_t n, float* A) {
@@ -541,14 +527,14 @@ __device__ __forceinline__ void ssys_tinv_body(const float* A, int K, int L, int
 // not on A) -- a Philox call each, hidden behind the dot product instead of standing at the head of the one-block chain kernel.
 // (bparts != nullptr: b is still in its nparts per-block parts -- summed here, in part order, as ssys_sum_parts_kernel would, and
 // written to b as well.)  K blocks behind the rows' make the chain's Ti (tinv != nullptr).
-template <int LIST>
+__host__ __device__ inline int ssys_residual_row_blocks(int n2) { return (n2 + 3) / 4; }      // a wave per row
 __device__ __forceinline__ void ssys_residual_body(const float* A, float* b, const float* bparts, int nparts, const float* S, int n2, float* r,
                                                    float4* cands, uint32_t it, uint32_t key0, uint32_t key1, float* tinv, int K, int L, const float* tau,
                                                    float4* own8, float4* recT, float* Tn, int block) {
 #pragma clang fp contract(off)
   // the grid: K blocks for Ti (tinv != nullptr; FIRST: one wave of ~750 dependent fp64 instructions each, the longest blocks of
   // the launch), the rows' blocks, the warm-up blocks
-  const int rblocks = (n2 + 3) / 4, kt = tinv ? K : 0;
+  const int rblocks = ssys_residual_row_blocks(n2), kt = tinv ? K : 0;
   if (block < kt) { ssys_tinv_body(A, K, L, block, *tau, tinv); return; }
   if (block >= rblocks + kt) {
     // Warm-up for the chain kernel that follows: it is ONE block, which the dispatcher puts on XCD 0 (block i of a grid goes to
@@ -633,29 +619,34 @@ __device__ __forceinline__ void ssys_residual_body(const float* A, float* b, con
     r[row] = (float)((double)bv - s);
   }
 }
-__global__ __launch_bounds__(256) void ssys_residual_kernel(const float* A, float* b, const float* bparts, int nparts, const float* S, int n2, float* r,
-                                                            float4* cands, uint32_t it, uint32_t key0, uint32_t key1, float* tinv, int K, int L, const float* tau,
-                                                            float4* own8, float4* recT, float* Tn) {
-  ssys_residual_body<0>(A, b, bparts, nparts, S, n2, r, cands, it, key0, key1, tinv, K, L, tau, own8, recT, Tn, (int)blockIdx.x);
-}
-// list form of the variational system's residual (no candidates, no Ti, no warm-up blocks: (n2 + 3) / 4 blocks of rows)
-struct SSysResidualPack { const float* A; float* b; const float* bparts; const float* S; float* r; int nparts, n2; };
-__global__ __launch_bounds__(256) void ssys_residual_many(const SSysResidualPack* list, int) {
-  const SSysResidualPack p = load_pack(list, blockIdx.z);
-  if ((int)blockIdx.x >= (p.n2 + 3) / 4) return;
-  ssys_residual_body<1>(p.A, p.b, p.bparts, p.nparts, p.S, p.n2, p.r, nullptr, 0, 0, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, (int)blockIdx.x);
-}
+struct SSysResidual {
+  struct Args {
+    const float* A; float* b; const float* bparts; const float* S; float* r; const float* tau;
+    float4* cands; float* tinv; float4* own8; float4* recT; float* Tn;      // the sampler's (all null in a recorded launch)
+    int nparts, n2, K, L;
+    uint32_t it, key0, key1, pad;
+  };
+  static constexpr int kThreads = 256;
+  // the rows' blocks; with tinv K blocks ahead of them, and for the sampler's large systems the warm-up blocks behind, from a multiple of 8
+  static __host__ __device__ int blocks(const Args& a) {
+    const int rows = ssys_residual_row_blocks(a.n2), kt = a.tinv ? a.K : 0;
+    return (a.tinv && (a.L & 3) == 0 && a.n2 >= 256) ? ((rows + kt + 7) & ~7) + 8 * kSsysWarmBlocks : rows + kt;
+  }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) {
+    // (the list form is the variational system's: launch_ssys_residual records nothing else, and the sampler's parts are not in its code)
+    if (FORM) ssys_residual_body(a.A, a.b, a.bparts, a.nparts, a.S, a.n2, a.r, nullptr, 0, 0, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, (int)blockIdx.x);
+    else ssys_residual_body(a.A, a.b, a.bparts, a.nparts, a.S, a.n2, a.r, a.cands, a.it, a.key0, a.key1, a.tinv, a.K, a.L, a.tau, a.own8, a.recT, a.Tn, (int)blockIdx.x);
+  }
+};
 void launch_ssys_residual(const float* A, float* b, const float* bparts, int nparts, const float* S, int n2, float* r, hipStream_t st, float* cands, uint32_t it, uint32_t key0, uint32_t key1,
                           float* tinv, int K, int L, const float* tau, float* own8, float* recT, float* Tn) {
-  if (g_recorder) {
-    if (cands || tinv || own8 || recT || Tn) { record_missing("ssys_residual (the sampler's form)"); return; }
-    SSysResidualPack p; memset(&p, 0, sizeof(p));
-    p.A = A; p.b = b; p.bparts = bparts; p.S = S; p.r = r; p.nparts = nparts; p.n2 = n2;
-    record_launch((const void*)ssys_residual_many, dim3((n2 + 3) / 4), dim3(256), 0, p, true);
-    return;
-  }
-  hipLaunchKernelGGL(ssys_residual_kernel, dim3((tinv && (L & 3) == 0 && n2 >= 256) ? (((n2 + 3) / 4 + K + 7) & ~7) + 8 * kSsysWarmBlocks : (n2 + 3) / 4 + (tinv ? K : 0)), dim3(256), 0, st, A, b, bparts, nparts, S, n2, r, reinterpret_cast<float4*>(cands), it, key0, key1, tinv, K, L, tau,
-                     reinterpret_cast<float4*>(own8), reinterpret_cast<float4*>(recT), Tn);
+  if ((cands || tinv || own8 || recT || Tn) && record_missing("ssys_residual (the sampler's form)")) return;
+  SSysResidual::Args a; memset(&a, 0, sizeof(a));
+  a.A = A; a.b = b; a.bparts = bparts; a.S = S; a.r = r; a.tau = tau;
+  a.cands = reinterpret_cast<float4*>(cands); a.tinv = tinv; a.own8 = reinterpret_cast<float4*>(own8); a.recT = reinterpret_cast<float4*>(recT); a.Tn = Tn;
+  a.nparts = nparts; a.n2 = n2; a.K = K; a.L = L; a.it = it; a.key0 = key0; a.key1 = key1;
+  launch_forms<SSysResidual>(a, st);
 }
 
 #ifdef BNMTF_EXPERIMENTS   // the chain as rounds 2-4 walked it, entry by entry: for same-box comparisons (make EXPERIMENTS=1, BNMTF_SCHAIN=seq)
@@ -774,7 +765,7 @@ __global__ __launch_bounds__(512) void ssys_chain_seq_kernel(SSysChainArgs a) {
       const float thr = pre.live ? -kTnA0 * pre.tpirt : __builtin_inff();    // a dead entry always leaves through the slow branch
 #pragma unroll
       for (int c = 0; c < NH; ++c) {
-        const float4 cd = a.cands[e * NH + c];                      // {-log u1, z, u2, -}: made by ssys_residual_kernel, off this kernel's critical path
+        const float4 cd = a.cands[e * NH + c];                      // {-log u1, z, u2, -}: made by SSysResidual, off this kernel's critical path
         recA[e * NH + c] = make_float4(cd.y * pre.irt, pre.rcp, thr, pre.irt);
         recB[e * NH + c] = make_float2(cd.x, cd.z);
       }
@@ -981,7 +972,7 @@ __global__ __launch_bounds__(512) void ssys_chain_seq_kernel(SSysChainArgs a) {
 // and c_l = base_l / tau_p,l + z_l sigma_l (the entry's first candidate), the sequential steps are
 //     x_l = c_l - sum_{l'' < l} N_ll'' x_l'' ,   N_ll'' = B_l''l / B_ll        <=>        (I + N) x = c        <=>        x = Ti c ,
 // as long as every entry is in the normal regime and accepts its first candidate.  Ti = (I + N)^-1 depends on A only: K small
-// triangular inversions, made in fp64 by blocks that ride behind ssys_residual_kernel.  So the chain wave does NOT walk the
+// triangular inversions, made in fp64 by blocks that ride behind SSysResidual.  So the chain wave does NOT walk the
 // entries: it forms c (one FMA per lane), multiplies by Ti (16 FMAs per lane, the two halves of the wave take half of the
 // sum each) and TESTS the row in one go -- lane l is fine when x_l is a non-negative finite number and mu_l = x_l - z_l sigma_l
 // lies in the normal regime.  The first lane f that is not fine has a VALID conditional mean (it depends on the lanes before
@@ -997,7 +988,7 @@ __global__ __launch_bounds__(512) void ssys_chain_seq_kernel(SSysChainArgs a) {
 // a = -mu sqrt(tau_p), d = 2 / (sqrt(a^2 + 4) + a), lam = a + d) is stated with 1 / lam = d (Robert's rate: lam d = 1):
 //     rc = 1 / (sqrt(a^2 + 4) + a),  t = e - d = (2 nl - 2) rc,  x = (2 nl sigma) rc,  accepted iff |t| <= sqrt(-2 ln u2)
 // -- the same events and values up to rounding, one reciprocal and no exponential on the chain; (2 nl - 2), 2 nl sigma and the
-// square root are per-candidate constants made by ssys_residual_kernel beside its dot products.
+// square root are per-candidate constants made by SSysResidual beside its dot products.
 // Rounding: Ti c sums the same products as the forward substitution in another order (both fp32; against the fp64 oracle they
 // are equally far, tests/test_bnmtf_gibbs_gpu.py); the chain is deterministic and the same on 1 and N GPUs (Ti is made from the
 // summed A).
@@ -1126,7 +1117,7 @@ __global__ __launch_bounds__(512) void ssys_chain_kernel(SSysChainArgs a) {
       }
     }
   };
-  // ---- prologue: every array the chain reads is a straight copy of what ssys_residual_kernel left in global memory -- LDS-DMA
+  // ---- prologue: every array the chain reads is a straight copy of what SSysResidual left in global memory -- LDS-DMA
   // through buffer descriptors (1 KiB per wave instruction, no registers, past the end: zeros), ONE memory round trip.  The
   // background waves' first loads go out around it.
   {

@@ -12,7 +12,7 @@
 //    SIMDs): each wave posts (mu, tau) of its two units to LDS, wave 0 evaluates the units of the block one per
 //    lane, writes mu/tau/E/Var/S2 of column k to global memory and posts E back.  Two block barriers per column;
 //  * the ELBO / exp_square_diff pieces (more fp64 erfc/log) do not feed the recurrence: the sweep stores
-//    sum_miss S2 and sum_miss E^2 per (unit, column) and vb_pieces_kernel evaluates them afterwards, all units in parallel.
+//    sum_miss S2 and sum_miss E^2 per (unit, column) and VbPieces evaluates them afterwards, all units in parallel.
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -434,7 +434,7 @@ void launch_sweep_vb(const SweepArgs& a, const FastArgs& f, hipStream_t st, int 
 // ELBO / exp_square_diff pieces of one sweep (bnmf_vb_optimised.py:163-177, 185-187), one wave per unit, lane = column:
 //   [0] sum_k tau/2 (Var + (E - mu)^2)   [1] sum_k log(1/2 erfc(-mu sqrt(tau/2)))   [2] sum_k log tau   [3] sum_k lambda E
 //   [4] sum_k S2self sum_miss S2other    [5] sum_k E^2 sum_miss Eother^2
-// out: one row of 8 per BLOCK of four units (vb_finish_kernel only needs the totals).
+// out: one row of 8 per BLOCK of four units (VbFinish only needs the totals).
 __device__ __forceinline__ void vb_pieces_body(int n, int n0, int KP, int K, const float* mu, const float* tauq, const float* ex,
                                                const float* var, const float* lambda, const float* asq, const float* vsq, double* out) {
   const int lane = threadIdx.x & 63, u = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -461,16 +461,13 @@ __device__ __forceinline__ void vb_pieces_body(int n, int n0, int KP, int K, con
   sync_with_dma();
   if (threadIdx.x < 6) out[(size_t)blockIdx.x * 8 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
-__global__ __launch_bounds__(256) void vb_pieces_kernel(int n, int n0, int KP, int K, const float* mu, const float* tauq, const float* ex,
-                                                         const float* var, const float* lambda, const float* asq, const float* vsq, double* out) {
-  vb_pieces_body(n, n0, KP, K, mu, tauq, ex, var, lambda, asq, vsq, out);
-}
-struct VbPiecesPack { int n, n0, KP, K; const float *mu, *tauq, *ex, *var, *lambda, *asq, *vsq; double* out; };
-__global__ __launch_bounds__(256) void vb_pieces_many(const VbPiecesPack* list, int) {      // list form (many.h): blockIdx.z = model
-  const VbPiecesPack p = load_pack(list, blockIdx.z);
-  if ((int)blockIdx.x >= (p.n + 3) / 4) return;
-  vb_pieces_body(p.n, p.n0, p.KP, p.K, p.mu, p.tauq, p.ex, p.var, p.lambda, p.asq, p.vsq, p.out);
-}
+struct VbPieces {      // (both forms: many.h)
+  struct Args { int n, n0, KP, K; const float *mu, *tauq, *ex, *var, *lambda, *asq, *vsq; double* out; };
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& a) { return (a.n + 3) / 4; }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) { vb_pieces_body(a.n, a.n0, a.KP, a.K, a.mu, a.tauq, a.ex, a.var, a.lambda, a.asq, a.vsq, a.out); }
+};
 
 // the same with sum_miss S2other / sum_miss Eother^2 taken from the slabs of kernel_maskgemm.hip ([msplit][n_pad][2 KP], local
 // unit rows), added in slab order as the sweep adds them
@@ -511,13 +508,9 @@ void launch_vb_pieces_slabs(int n, int n0, int KP, int K, const float* mu, const
 void launch_vb_pieces(int n, int n0, int KP, int K, const float* mu, const float* tauq, const float* ex, const float* var,
                       const float* lambda, const float* asq, const float* vsq, double* out, hipStream_t st) {
   if (n <= 0) return;
-  if (g_recorder) {
-    VbPiecesPack p; memset(&p, 0, sizeof(p));
-    p.n = n; p.n0 = n0; p.KP = KP; p.K = K; p.mu = mu; p.tauq = tauq; p.ex = ex; p.var = var; p.lambda = lambda; p.asq = asq; p.vsq = vsq; p.out = out;
-    record_launch((const void*)vb_pieces_many, dim3((n + 3) / 4), dim3(256), 0, p, true);
-    return;
-  }
-  hipLaunchKernelGGL(vb_pieces_kernel, dim3((n + 3) / 4), dim3(256), 0, st, n, n0, KP, K, mu, tauq, ex, var, lambda, asq, vsq, out);
+  VbPieces::Args a; memset(&a, 0, sizeof(a));
+  a.n = n; a.n0 = n0; a.KP = KP; a.K = K; a.mu = mu; a.tauq = tauq; a.ex = ex; a.var = var; a.lambda = lambda; a.asq = asq; a.vsq = vsq; a.out = out;
+  launch_forms<VbPieces>(a, st);
 }
 
 }  // namespace bnmtf

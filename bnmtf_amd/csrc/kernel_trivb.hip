@@ -6,7 +6,7 @@
 //     mvG_il = sum_j M_ij varG_jl,  FS_il = sum_k' E[F_ik'] E[S_k'l]  -- per unit an L-vector, kept current as the unit's
 //     columns change (kernel_sweep.hip takes it as SweepArgs::cov_*).  G likewise with the roles swapped (:265-273).
 //   * the S entries are coordinate steps on the dense system of kernel_ssys.hip built from second moments, walked in
-//     the (shuffled) order the host hands over: ssys_chain_vb_kernel.
+//     the (shuffled) order the host hands over: SSysChainVb.
 //   * exp_square_diff (:235-239) = four masked bilinear sums, evaluated directly in fp64 by metric_kernel on factor
 //     matrices tri_factors_kernel lays out.
 #include <algorithm>
@@ -23,88 +23,77 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // mean and second moment of the effective factor:  Xe[r][c] = sum_t X[r][t] S(t,c),
 // S2e[r][c] = sum_t (varX + X^2)[r][t] (varS + S^2)(t,c) - sum_t X^2[r][t] S^2(t,c) + Xe^2     (S(t,c) = S[t][c] or S[c][t])
-// (block of a grid of nblocks: the single-model kernel and its list form share the body)
-// (LIST: the list form's own instantiation -- a body shared by two kernels is inlined differently into each, and the single-model
-// kernel keeps the code it had)
-template <int LIST>
-__device__ __forceinline__ void small_product_vb_body(SmallProductVbArgs a, unsigned block, unsigned nblocks) {
-  // S(t, c) at [t][c] in LDS whichever way it is read: consecutive lanes (c) on consecutive banks (round 6: the transposed read
-  // c L + t was a 32-way bank conflict -- 16.8 us for the F side against 5 us for the G side)
-  __shared__ float Ss[32 * 32], Vs[32 * 32];
-  for (int t = threadIdx.x; t < a.K * a.L; t += 256) {
-    const int k = t / a.L, l = t % a.L;
-    const int at = a.transposeS ? l * 32 + k : k * 32 + l;
-    Ss[at] = a.S[t]; Vs[at] = a.varS[t];
+// (a model among others strides by its OWN grid nb, so that every element is formed by the thread that forms it in the model's own
+// launch)
+struct SmallProductVb {
+  typedef SmallProductVbArgs Args;
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& a) {
+    const int outw = a.transposeS ? a.K : a.L;
+    const size_t need = ((size_t)a.rows * outw + 255) / 256;
+    return (int)(need < 2048 ? need : 2048);
   }
-  __syncthreads();
-  const int inner = a.transposeS ? a.L : a.K, outw = a.transposeS ? a.K : a.L;
-  for (size_t e = (size_t)block * 256 + threadIdx.x; e < (size_t)a.rows * outw; e += (size_t)nblocks * 256) {
-    const int r = (int)(e / outw), c = (int)(e % outw);
-    const float* x = a.X + (size_t)r * 32;
-    const float* vx = a.varX + (size_t)r * 32;
-    float m = 0.f, s2 = 0.f, sq = 0.f;
-    for (int t = 0; t < inner; ++t) {
-      const int si = t * 32 + c;
-      const float xs = x[t], ss = Ss[si];
-      m = fmaf(xs, ss, m);
-      s2 = fmaf(vx[t] + xs * xs, Vs[si] + ss * ss, s2);
-      sq = fmaf(xs * xs, ss * ss, sq);
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int nb, int) {
+    const unsigned block = blockIdx.x, nblocks = (unsigned)nb;
+    // S(t, c) at [t][c] in LDS whichever way it is read: consecutive lanes (c) on consecutive banks (round 6: the transposed read
+    // c L + t was a 32-way bank conflict -- 16.8 us for the F side against 5 us for the G side)
+    __shared__ float Ss[32 * 32], Vs[32 * 32];
+    for (int t = threadIdx.x; t < a.K * a.L; t += 256) {
+      const int k = t / a.L, l = t % a.L;
+      const int at = a.transposeS ? l * 32 + k : k * 32 + l;
+      Ss[at] = a.S[t]; Vs[at] = a.varS[t];
     }
-    a.out[(size_t)r * 32 + c] = m;
-    a.outS2[(size_t)r * 32 + c] = (s2 - sq) + m * m;
+    __syncthreads();
+    const int inner = a.transposeS ? a.L : a.K, outw = a.transposeS ? a.K : a.L;
+    for (size_t e = (size_t)block * 256 + threadIdx.x; e < (size_t)a.rows * outw; e += (size_t)nblocks * 256) {
+      const int r = (int)(e / outw), c = (int)(e % outw);
+      const float* x = a.X + (size_t)r * 32;
+      const float* vx = a.varX + (size_t)r * 32;
+      float m = 0.f, s2 = 0.f, sq = 0.f;
+      for (int t = 0; t < inner; ++t) {
+        const int si = t * 32 + c;
+        const float xs = x[t], ss = Ss[si];
+        m = fmaf(xs, ss, m);
+        s2 = fmaf(vx[t] + xs * xs, Vs[si] + ss * ss, s2);
+        sq = fmaf(xs * xs, ss * ss, sq);
+      }
+      a.out[(size_t)r * 32 + c] = m;
+      a.outS2[(size_t)r * 32 + c] = (s2 - sq) + m * m;
+    }
   }
-}
-__global__ __launch_bounds__(256) void small_product_vb_kernel(SmallProductVbArgs a) { small_product_vb_body<0>(a, blockIdx.x, gridDim.x); }
-__host__ __device__ inline int small_product_vb_blocks(const SmallProductVbArgs& a) {
-  const int outw = a.transposeS ? a.K : a.L;
-  const size_t need = ((size_t)a.rows * outw + 255) / 256;
-  return (int)(need < 2048 ? need : 2048);
-}
-// List forms (many.h): blockIdx.z = model; a model whose own grid is smaller than the launch's leaves with the surplus blocks --
-// and strides by its OWN grid, so that every element is formed by the thread that forms it in the model's own launch.
-__global__ __launch_bounds__(256) void small_product_vb_many(const SmallProductVbArgs* list, int) {
-  const SmallProductVbArgs a = load_pack(list, blockIdx.z);
-  const int nb = small_product_vb_blocks(a);
-  if ((int)blockIdx.x >= nb) return;
-  small_product_vb_body<1>(a, blockIdx.x, (unsigned)nb);
-}
-void launch_small_product_vb(const SmallProductVbArgs& a, hipStream_t st) {
-  const int blocks = small_product_vb_blocks(a);
-  if (record_launch((const void*)small_product_vb_many, dim3(blocks), dim3(256), 0, a, true)) return;
-  hipLaunchKernelGGL(small_product_vb_kernel, dim3(blocks), dim3(256), 0, st, a);
-}
+};
+void launch_small_product_vb(const SmallProductVbArgs& a, hipStream_t st) { launch_forms<SmallProductVb>(a, st); }
 
 // mv[u][c] = sum over the unit's OBSERVED inner indices of V[.][c] = colsum_c - sum_{e in miss(u)} V[idx_e][c]:
 // one wave per unit, a 32-lane half takes one missing entry per trip (a coalesced 128-byte row of V), eight in flight
-template <int LIST>
-__device__ __forceinline__ void masked_colsum_body(MaskedColsumArgs a, int block) {
-  const int lane = threadIdx.x & 63, half = lane >> 5, c = lane & 31;
-  const int u = block * 4 + (threadIdx.x >> 6);
-  if (u >= a.n) return;
-  const uint32_t s0 = a.slot_ptr[u], s1 = a.slot_ptr[u + 1];
-  float acc = 0.f;
-  for (uint32_t e0 = s0; e0 < s1; e0 += 16) {
-    uint32_t ii[8]; float v[8];
+struct MaskedColsum {
+  typedef MaskedColsumArgs Args;
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& a) { return (a.n + 3) / 4; }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) {
+    const int lane = threadIdx.x & 63, half = lane >> 5, c = lane & 31;
+    const int u = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= a.n) return;
+    const uint32_t s0 = a.slot_ptr[u], s1 = a.slot_ptr[u + 1];
+    float acc = 0.f;
+    for (uint32_t e0 = s0; e0 < s1; e0 += 16) {
+      uint32_t ii[8]; float v[8];
 #pragma unroll
-    for (int t = 0; t < 8; ++t) ii[t] = a.idx[e0 + 2u * t + half];       // padding slots point at the zero row
+      for (int t = 0; t < 8; ++t) ii[t] = a.idx[e0 + 2u * t + half];       // padding slots point at the zero row
 #pragma unroll
-    for (int t = 0; t < 8; ++t) v[t] = a.V[(size_t)ii[t] * 32 + c];
+      for (int t = 0; t < 8; ++t) v[t] = a.V[(size_t)ii[t] * 32 + c];
 #pragma unroll
-    for (int t = 0; t < 8; ++t) acc += v[t];
+      for (int t = 0; t < 8; ++t) acc += v[t];
+    }
+    acc += __shfl_xor(acc, 32, 64);
+    if (half == 0) a.out[(size_t)u * 32 + c] = (float)(a.colsum2[c] - a.C64[(size_t)c * 32 + c]) - acc;   // sum var = sum S2 - sum E^2
   }
-  acc += __shfl_xor(acc, 32, 64);
-  if (half == 0) a.out[(size_t)u * 32 + c] = (float)(a.colsum2[c] - a.C64[(size_t)c * 32 + c]) - acc;   // sum var = sum S2 - sum E^2
-}
-__global__ __launch_bounds__(256) void masked_colsum_kernel(MaskedColsumArgs a) { masked_colsum_body<0>(a, (int)blockIdx.x); }
-__global__ __launch_bounds__(256) void masked_colsum_many(const MaskedColsumArgs* list, int) {
-  const MaskedColsumArgs a = load_pack(list, blockIdx.z);
-  if ((int)blockIdx.x >= (a.n + 3) / 4) return;
-  masked_colsum_body<1>(a, (int)blockIdx.x);
-}
+};
 void launch_masked_colsum(const MaskedColsumArgs& a, hipStream_t st) {
   if (a.n <= 0) return;
-  if (record_launch((const void*)masked_colsum_many, dim3((a.n + 3) / 4), dim3(256), 0, a, true)) return;
-  hipLaunchKernelGGL(masked_colsum_kernel, dim3((a.n + 3) / 4), dim3(256), 0, st, a);
+  launch_forms<MaskedColsum>(a, st);
 }
 
 
@@ -119,92 +108,96 @@ void launch_masked_colsum(const MaskedColsumArgs& a, hipStream_t st) {
 // evaluated behind the last step by every thread for its own entry, from the (mu, tau) the step stored; the barrier of a step
 // waits for LDS traffic only, so the rows of A~ prefetched for later steps stay in flight.
 // only_params: write mu/tau of the ordered entries, leave the moments alone (update_S without update_exp_S).
-// (LIST: the list form's own instantiation -- a body shared by two kernels is inlined differently into each, and the single-model
-// kernel keeps the code it had)
-template <int LIST>
-__device__ __forceinline__ void ssys_chain_vb_body(SSysChainVbArgs a) {
-  constexpr int PF = 12;                                           // rows of A~ prefetched ahead of their step
-  __shared__ float dl[2];
-  __shared__ int ordl[1024 + PF], posl[1024];
-  const int n2 = a.K * a.L, t = threadIdx.x, n_order = a.n_order;
-  const float tau = *a.tau;
-  const bool mine = t < n2;
-  posl[t] = -1;
-  __syncthreads();
-  for (int i = t; i < n_order + PF; i += 1024) {
-    const int ai = i < n_order ? a.order[i] : 0;
-    ordl[i] = ai;
-    if (i < n_order) posl[ai] = i;
+// The arguments of the chain and of the permutation hold the order of the run's FIRST iteration; iteration `it`'s is
+// it * order_step entries behind it (the orders of a run_many call lie iteration by iteration: bnmtf_vb_run's layout).
+struct SSysChainVbForms {     // what the two chains share
+  struct Args { SSysChainVbArgs a; int order_step, pad; };
+  static constexpr int kThreads = 1024;
+  static __host__ __device__ int blocks(const Args&) { return 1; }
+  static __device__ __forceinline__ SSysChainVbArgs at(const Args& p, int it) {
+    SSysChainVbArgs a = p.a;
+    a.order += (size_t)it * p.order_step;
+    return a;
   }
-  __syncthreads();
-  const int mypos = posl[t];                                       // the step that updates this thread's entry (-1: none)
-  float r = mine ? a.r0[t] : 0.f;
-  float e = mine ? a.E[t] : 0.f;
-  const float aaa = mine ? a.A[(size_t)t * n2 + t] : 1.f;       // A~[t][t]
-  const float tau_p = tau * aaa, inv_tp = 1.0f / tau_p;
-  const float sig = __builtin_amdgcn_rsqf(tau_p), xs = tau_p * sig;   // (as tn_moments_f32 forms them)
-  const float lam = mine ? a.lambdaS[t] : 0.f;
-  float mu_t = 0.f;
-  // (unconditional loads -- ordl is padded with PF zeros, a thread beyond the system reads its last column: a predicated load
-  // is merged into its register behind a vmcnt(0), i.e. every step waited for a trip to L2: 0.58 us a step, round 6)
-  const uint32_t tcol = (uint32_t)(mine ? t : n2 - 1);
-  float pf[PF];
+};
+struct SSysChainVb : SSysChainVbForms {
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& args, int, int it) {
+    const SSysChainVbArgs a = at(args, it);
+    constexpr int PF = 12;                                           // rows of A~ prefetched ahead of their step
+    __shared__ float dl[2];
+    __shared__ int ordl[1024 + PF], posl[1024];
+    const int n2 = a.K * a.L, t = threadIdx.x, n_order = a.n_order;
+    const float tau = *a.tau;
+    const bool mine = t < n2;
+    posl[t] = -1;
+    __syncthreads();
+    for (int i = t; i < n_order + PF; i += 1024) {
+      const int ai = i < n_order ? a.order[i] : 0;
+      ordl[i] = ai;
+      if (i < n_order) posl[ai] = i;
+    }
+    __syncthreads();
+    const int mypos = posl[t];                                       // the step that updates this thread's entry (-1: none)
+    float r = mine ? a.r0[t] : 0.f;
+    float e = mine ? a.E[t] : 0.f;
+    const float aaa = mine ? a.A[(size_t)t * n2 + t] : 1.f;       // A~[t][t]
+    const float tau_p = tau * aaa, inv_tp = 1.0f / tau_p;
+    const float sig = __builtin_amdgcn_rsqf(tau_p), xs = tau_p * sig;   // (as tn_moments_f32 forms them)
+    const float lam = mine ? a.lambdaS[t] : 0.f;
+    float mu_t = 0.f;
+    // (unconditional loads -- ordl is padded with PF zeros, a thread beyond the system reads its last column: a predicated load
+    // is merged into its register behind a vmcnt(0), i.e. every step waited for a trip to L2: 0.58 us a step, round 6)
+    const uint32_t tcol = (uint32_t)(mine ? t : n2 - 1);
+    float pf[PF];
 #pragma unroll
-  for (int q = 0; q < PF; ++q) pf[q] = a.A[(uint32_t)ordl[q] * (uint32_t)n2 + tcol];
-  auto step = [&](int i, float arow) {
-    if (i == mypos) {
-      const float numer = fmaf(tau, fmaf(aaa, e, r), -lam);
-      mu_t = numer * inv_tp;
-      float enew = e;
-      if (!a.only_params) {
-        // x = -mu sqrt(tau) <= -6: the routine's lambda term is below half an ulp of |x| and its result is sig |x|, bit for bit
-        // -- the common case of an entry of S away from zero (its mean many standard deviations above it)
-        const float x = -mu_t * xs;
-        if (x <= -6.0f) {
-          const float ef = sig * (-x);
-          enew = isfinite(ef) ? ef : 0.f;
-        } else {
-          float vf;
-          tn_moments_f32(mu_t, tau_p, &enew, &vf);                  // (the variance's part of the routine is dead code here)
+    for (int q = 0; q < PF; ++q) pf[q] = a.A[(uint32_t)ordl[q] * (uint32_t)n2 + tcol];
+    auto step = [&](int i, float arow) {
+      if (i == mypos) {
+        const float numer = fmaf(tau, fmaf(aaa, e, r), -lam);
+        mu_t = numer * inv_tp;
+        float enew = e;
+        if (!a.only_params) {
+          // x = -mu sqrt(tau) <= -6: the routine's lambda term is below half an ulp of |x| and its result is sig |x|, bit for bit
+          // -- the common case of an entry of S away from zero (its mean many standard deviations above it)
+          const float x = -mu_t * xs;
+          if (x <= -6.0f) {
+            const float ef = sig * (-x);
+            enew = isfinite(ef) ? ef : 0.f;
+          } else {
+            float vf;
+            tn_moments_f32(mu_t, tau_p, &enew, &vf);                  // (the variance's part of the routine is dead code here)
+          }
         }
+        dl[i & 1] = enew - e;
+        e = enew;
       }
-      dl[i & 1] = enew - e;
-      e = enew;
-    }
-    // (LDS traffic only: __syncthreads would also wait for the row loads in flight -- a trip to L2 on every step)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    r = fmaf(-dl[i & 1], arow, r);
-  };
-  // whole groups of PF steps: straight-line code, every register of the ring reloaded right behind its use; then the rest
-  int i0 = 0;
-  for (; i0 + PF <= n_order; i0 += PF) {
+      // (LDS traffic only: __syncthreads would also wait for the row loads in flight -- a trip to L2 on every step)
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      r = fmaf(-dl[i & 1], arow, r);
+    };
+    // whole groups of PF steps: straight-line code, every register of the ring reloaded right behind its use; then the rest
+    int i0 = 0;
+    for (; i0 + PF <= n_order; i0 += PF) {
 #pragma unroll
-    for (int q = 0; q < PF; ++q) {
-      step(i0 + q, pf[q]);
-      pf[q] = a.A[(uint32_t)ordl[i0 + q + PF] * (uint32_t)n2 + tcol];      // (behind its use: the reload lands in the same register, no copies -- and no drain -- at the loop's end)
+      for (int q = 0; q < PF; ++q) {
+        step(i0 + q, pf[q]);
+        pf[q] = a.A[(uint32_t)ordl[i0 + q + PF] * (uint32_t)n2 + tcol];      // (behind its use: the reload lands in the same register, no copies -- and no drain -- at the loop's end)
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < PF; ++q)
+      if (i0 + q < n_order) step(i0 + q, pf[q]);
+    if (mypos >= 0) {
+      a.mu[t] = mu_t; a.tauq[t] = tau_p;
+      if (!a.only_params) {
+        float ef, vf;
+        tn_moments_f32(mu_t, tau_p, &ef, &vf);
+        a.E[t] = e; a.var[t] = vf;
+      }
     }
   }
-#pragma unroll
-  for (int q = 0; q < PF; ++q)
-    if (i0 + q < n_order) step(i0 + q, pf[q]);
-  if (mypos >= 0) {
-    a.mu[t] = mu_t; a.tauq[t] = tau_p;
-    if (!a.only_params) {
-      float ef, vf;
-      tn_moments_f32(mu_t, tau_p, &ef, &vf);
-      a.E[t] = e; a.var[t] = vf;
-    }
-  }
-}
-__global__ __launch_bounds__(1024) void ssys_chain_vb_kernel(SSysChainVbArgs a) { ssys_chain_vb_body<0>(a); }
-// list forms of the chain and the permutation: a recorded pack holds the order of the run's FIRST iteration; iteration `it`'s is
-// it * order_step entries behind it (the orders of a run_many call lie iteration by iteration: bnmtf_vb_run's layout)
-struct SSysChainVbPack { SSysChainVbArgs a; int order_step; int pad_; };
-__global__ __launch_bounds__(1024) void ssys_chain_vb_many(const SSysChainVbPack* list, int it) {
-  SSysChainVbPack p = load_pack(list, blockIdx.z);
-  p.a.order += (size_t)it * p.order_step;
-  ssys_chain_vb_body<1>(p.a);
-}
+};
 
 // The same chain for a whole pass (every step with its moments), walked in BLOCKS of 64 steps (round 6).  The kernel above pays a
 // block barrier and two LDS round trips per step (0.28 us a step, 285 us for 1 024 entries at K = L = 32: 40 % of an iteration
@@ -226,203 +219,188 @@ __global__ __launch_bounds__(1024) void ssys_chain_vb_many(const SSysChainVbPack
 // step): out of A~ itself those were 64-lane gathers inside 4 KiB rows -- ~28 cache lines a load instruction, 27 000 line requests
 // per block of the chain from ONE compute unit, which is what its hand-overs waited for (round 6: 10 000 cycles each) -- here all
 // 256 units share the gathers once and the chain's loads are contiguous.
-template <int LIST>
 __device__ __forceinline__ void ssys_permute_body(const float* __restrict__ A, const int* __restrict__ order, int n, float* __restrict__ out, int s) {
   const float* row = A + (size_t)order[s] * n;
   for (int p = threadIdx.x; p < n; p += 256) out[(size_t)s * n + p] = row[order[p]];
 }
-__global__ __launch_bounds__(256) void ssys_permute_kernel(const float* __restrict__ A, const int* __restrict__ order, int n, float* __restrict__ out) {
-  ssys_permute_body<0>(A, order, n, out, (int)blockIdx.x);
-}
-struct SSysPermutePack { const float* A; const int* order; float* out; int n, order_step; };
-__global__ __launch_bounds__(256) void ssys_permute_many(const SSysPermutePack* list, int it) {
-  const SSysPermutePack p = load_pack(list, blockIdx.z);
-  if ((int)blockIdx.x >= p.n) return;
-  ssys_permute_body<1>(p.A, p.order + (size_t)it * p.order_step, p.n, p.out, (int)blockIdx.x);
-}
+struct SSysPermute {
+  struct Args { const float* A; const int* order; float* out; int n, order_step; };
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& a) { return a.n; }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int it) { ssys_permute_body(a.A, a.order + (size_t)it * a.order_step, a.n, a.out, (int)blockIdx.x); }
+};
 void launch_ssys_permute(const float* A, const int* order, int n, float* out, hipStream_t st, int order_step) {
-  if (g_recorder) {
-    SSysPermutePack p; memset(&p, 0, sizeof(p));
-    p.A = A; p.order = order; p.out = out; p.n = n; p.order_step = order_step;
-    record_launch((const void*)ssys_permute_many, dim3(n), dim3(256), 0, p, true);
-    return;
-  }
-  hipLaunchKernelGGL(ssys_permute_kernel, dim3(n), dim3(256), 0, st, A, order, n, out);
+  SSysPermute::Args a; memset(&a, 0, sizeof(a));
+  a.A = A; a.order = order; a.out = out; a.n = n; a.order_step = order_step;
+  launch_forms<SSysPermute>(a, st);
 }
 
-template <int LIST>
-__device__ __forceinline__ void ssys_chain_vb_blocked_body(SSysChainVbArgs a) {
-  __shared__ __align__(16) float dlt[1024];
-  __shared__ float diag[3 * 64 * 64 + 8 * 64];
-  const int n2 = a.K * a.L, p = threadIdx.x, lane = p & 63, n_order = a.n_order;      // (n_order == n2: a whole pass)
-  const int w = __builtin_amdgcn_readfirstlane(p >> 6);
-  const int nblk = (n_order + 63) / 64;
-  const bool on = p < n_order;
-  dlt[p] = 0.f;
-  const uint32_t ent = (uint32_t)a.order[on ? p : n_order - 1];
-  const float tau = *a.tau;
-  float r = a.r0[ent];
-  const float e_old = a.E[ent];
-  const float aaa = a.A[(size_t)ent * n2 + ent];
-  const float tau_p = tau * aaa, inv_tp = 1.0f / tau_p;
-  const float sig = __builtin_amdgcn_rsqf(tau_p), xs = tau_p * sig;      // (as tn_moments_f32 forms them)
-  const float c = fmaf(tau * aaa, e_old, -a.lambdaS[ent]);                // numer = tau (r + A~_aa E) - lambda = tau r + c
-  const float hh = inv_tp * xs;                                           // -x = numer hh
-  const float g = hh * sig;                                               // E_new = sig (-x) = numer g
-  const float thr = hh > 0.f ? 6.0f / hh : __builtin_inff();              // -x >= 6  <=>  numer >= thr
-  const float q1 = -hh * kTnMeanInvW;                                     // (x - x0) / width = numer q1 - x0 / width
-  const float tc0 = kTnMeanTab[lane][0], tc1 = kTnMeanTab[lane][1], tc2 = kTnMeanTab[lane][2],
-              tc3 = kTnMeanTab[lane][3], tc4 = kTnMeanTab[lane][4], tc5 = kTnMeanTab[lane][5];      // segment `lane` of the mean's table
-  auto rl = [](float v, int k) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k)); };
-  __syncthreads();
-  float ab[64];
-  // rows of A~ of block b's steps, this thread's column
-  // rows of the permuted system (a.Aperm): descriptor + the row's byte offset in an SGPR + the lane's column in ONE VGPR
-  const __amdgpu_buffer_rsrc_t rsA = panel_rsrc(a.Aperm, (size_t)n2 * n2 * 4);
-  const int col_b = p * 4;
-  auto load_rows = [&](int b) {
+struct SSysChainVbBlocked : SSysChainVbForms {
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& args, int, int it) {
+    const SSysChainVbArgs a = at(args, it);
+    __shared__ __align__(16) float dlt[1024];
+    __shared__ float diag[3 * 64 * 64 + 8 * 64];
+    const int n2 = a.K * a.L, p = threadIdx.x, lane = p & 63, n_order = a.n_order;      // (n_order == n2: a whole pass)
+    const int w = __builtin_amdgcn_readfirstlane(p >> 6);
+    const int nblk = (n_order + 63) / 64;
+    const bool on = p < n_order;
+    dlt[p] = 0.f;
+    const uint32_t ent = (uint32_t)a.order[on ? p : n_order - 1];
+    const float tau = *a.tau;
+    float r = a.r0[ent];
+    const float e_old = a.E[ent];
+    const float aaa = a.A[(size_t)ent * n2 + ent];
+    const float tau_p = tau * aaa, inv_tp = 1.0f / tau_p;
+    const float sig = __builtin_amdgcn_rsqf(tau_p), xs = tau_p * sig;      // (as tn_moments_f32 forms them)
+    const float c = fmaf(tau * aaa, e_old, -a.lambdaS[ent]);                // numer = tau (r + A~_aa E) - lambda = tau r + c
+    const float hh = inv_tp * xs;                                           // -x = numer hh
+    const float g = hh * sig;                                               // E_new = sig (-x) = numer g
+    const float thr = hh > 0.f ? 6.0f / hh : __builtin_inff();              // -x >= 6  <=>  numer >= thr
+    const float q1 = -hh * kTnMeanInvW;                                     // (x - x0) / width = numer q1 - x0 / width
+    const float tc0 = kTnMeanTab[lane][0], tc1 = kTnMeanTab[lane][1], tc2 = kTnMeanTab[lane][2],
+                tc3 = kTnMeanTab[lane][3], tc4 = kTnMeanTab[lane][4], tc5 = kTnMeanTab[lane][5];      // segment `lane` of the mean's table
+    auto rl = [](float v, int k) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k)); };
+    __syncthreads();
+    float ab[64];
+    // rows of A~ of block b's steps, this thread's column
+    // rows of the permuted system (a.Aperm): descriptor + the row's byte offset in an SGPR + the lane's column in ONE VGPR
+    const __amdgpu_buffer_rsrc_t rsA = panel_rsrc(a.Aperm, (size_t)n2 * n2 * 4);
+    const int col_b = p * 4;
+    auto load_rows = [&](int b) {
 #pragma unroll
-    for (int j = 0; j < 64; ++j)                   // (rows past the last step: the descriptor returns 0, the delta is 0)
-      ab[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsA, col_b, (b * 64 + j) * n2 * 4, 0));
-  };
-  auto stage_diag = [&]() {                        // this wave's own block, strictly upper triangle
-    load_rows(w);
-    const int reg = (w % 3) * 4096 + lane;         // (indexed off the LDS array itself: a float* picked out of three turns into 64-bit flat arithmetic)
-    int ln = on ? lane : -1;
-    asm volatile("" : "+v"(ln));                   // opaque: the 64 lane masks are made here, not hoisted out of the block loop into 128 scalar registers
-#pragma unroll
-    for (int j = 0; j < 64; ++j) diag[reg + j * 64] = ln > j ? ab[j] : 0.f;
-  };
-  if (w < 3 && w < nblk) stage_diag();
-  // (three phases per wave, not one loop over the blocks with the roles inside: there the 64 row registers stayed live through
-  // the active block's code -- 135 spilled)
-#ifdef CHAIN_CLOCK
-  __shared__ unsigned long long cks[16][4];
-  const unsigned long long ck0 = __builtin_amdgcn_s_memtime();
-  unsigned long long ck_fold = 0;
-  int n_slow = 0, n_far = 0;
-#endif
-  for (int blk = 0; blk < w; ++blk) {              // ---- the blocks ahead of mine: their rows, their deltas into my residual
-    load_rows(blk);                                // on their way while the block runs
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // (LDS traffic only: the rows stay in flight)
-#ifdef CHAIN_CLOCK
-    const unsigned long long ckf = __builtin_amdgcn_s_memtime();
-#endif
-    int dbase = 64 * blk;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const float4 d4 = *reinterpret_cast<const float4*>(&dlt[dbase + 4 * j]);
-      r = fmaf(-d4.x, ab[4 * j], r); r = fmaf(-d4.y, ab[4 * j + 1], r);
-      r = fmaf(-d4.z, ab[4 * j + 2], r); r = fmaf(-d4.w, ab[4 * j + 3], r);
-      // (16 deltas in flight at a time -- the next group's address "depends" on this group's sum: all 64 read ahead are 64 more live registers)
-      if ((j & 3) == 3) asm volatile("" : "+v"(dbase), "+v"(r));
-    }
-#ifdef CHAIN_CLOCK
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if (blk == w - 1) ck_fold = __builtin_amdgcn_s_memtime() - ckf;
-#endif
-    __builtin_amdgcn_sched_barrier(0);             // (the fold's FMAs are not interleaved with the next 64 loads: that is 128 live registers)
-    if (w == blk + 2 && w >= 3) stage_diag();      // its region: free since the barrier behind block w - 3
-  }
-  {                                                // ---- my block
-    const int blk = w;
-    // (rows read four steps ahead through ONE running index and immediate offsets; 8 spare rows behind the regions keep the last reads inside the array)
-    int reg = (w % 3) * 4096 + lane;
-    const int cnt = min(64, n_order - 64 * blk);
-    float a0 = diag[reg], a1 = diag[reg + 64], a2 = diag[reg + 128], a3 = diag[reg + 192];
-    auto one = [&](int i, float arow) {
-      const float nm = fmaf(tau, r, c);
-      float d = fmaf(nm, g, -e_old);
-      const unsigned long long ok = __ballot(nm >= thr);                  // (a NaN fails the test: the routine's guards see it)
-      if (__builtin_expect(!((ok >> i) & 1ull), 0)) {
-        // -6 < x < 26: the segment table (tn_mean_table.h) -- lane i's segment number into a scalar register, that segment's six
-        // coefficients out of their lanes by v_readlane, Horner in t = frac: ~20 instructions where the routine is ~50
-        const float xq = fmaxf(fmaf(nm, q1, -kTnMeanX0 * kTnMeanInvW), -1.0f);      // ((x - x0) / width; a NaN becomes -1)
-        const int kseg = __builtin_amdgcn_readlane((int)__builtin_floorf(xq), i);
-        float en;
-        if (__builtin_expect((unsigned)kseg < (unsigned)kTnMeanSeg, 1)) {
-          const float t = __builtin_amdgcn_fractf(xq);
-          float pz = rl(tc5, kseg);
-          pz = fmaf(pz, t, rl(tc4, kseg)); pz = fmaf(pz, t, rl(tc3, kseg)); pz = fmaf(pz, t, rl(tc2, kseg));
-          pz = fmaf(pz, t, rl(tc1, kseg)); pz = fmaf(pz, t, rl(tc0, kseg));
-          en = sig * pz;
-        } else {
-          // x >= 26 (an entry pinned at zero) or not a number: the routine, in the regime of lane i's x (its sign is the numerator's)
-          const unsigned long long xneg = __ballot(nm > 0.0f);
-          const float mu = nm * inv_tp;
-          en = ((xneg >> i) & 1ull) ? tn_mean_f32_regime<false>(mu, tau_p) : tn_mean_f32_regime<true>(mu, tau_p);
-        }
-        d = en - e_old;
-#ifdef CHAIN_CLOCK
-        ++n_slow;
-#endif
-      }
-      const float delta = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, d), i));
-      r = fmaf(-delta, arow, r);
+      for (int j = 0; j < 64; ++j)                   // (rows past the last step: the descriptor returns 0, the delta is 0)
+        ab[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsA, col_b, (b * 64 + j) * n2 * 4, 0));
     };
+    auto stage_diag = [&]() {                        // this wave's own block, strictly upper triangle
+      load_rows(w);
+      const int reg = (w % 3) * 4096 + lane;         // (indexed off the LDS array itself: a float* picked out of three turns into 64-bit flat arithmetic)
+      int ln = on ? lane : -1;
+      asm volatile("" : "+v"(ln));                   // opaque: the 64 lane masks are made here, not hoisted out of the block loop into 128 scalar registers
+#pragma unroll
+      for (int j = 0; j < 64; ++j) diag[reg + j * 64] = ln > j ? ab[j] : 0.f;
+    };
+    if (w < 3 && w < nblk) stage_diag();
+    // (three phases per wave, not one loop over the blocks with the roles inside: there the 64 row registers stayed live through
+    // the active block's code -- 135 spilled)
 #ifdef CHAIN_CLOCK
-    const unsigned long long ck1 = __builtin_amdgcn_s_memtime();
+    __shared__ unsigned long long cks[16][4];
+    const unsigned long long ck0 = __builtin_amdgcn_s_memtime();
+    unsigned long long ck_fold = 0;
+    int n_slow = 0, n_far = 0;
 #endif
-    int i = 0;
-    for (; i + 4 <= cnt; i += 4) {
-      one(i, a0);     a0 = diag[reg + 256];
-      one(i + 1, a1); a1 = diag[reg + 320];
-      one(i + 2, a2); a2 = diag[reg + 384];
-      one(i + 3, a3); a3 = diag[reg + 448];
-      reg += 256;
+    for (int blk = 0; blk < w; ++blk) {              // ---- the blocks ahead of mine: their rows, their deltas into my residual
+      load_rows(blk);                                // on their way while the block runs
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // (LDS traffic only: the rows stay in flight)
+#ifdef CHAIN_CLOCK
+      const unsigned long long ckf = __builtin_amdgcn_s_memtime();
+#endif
+      int dbase = 64 * blk;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const float4 d4 = *reinterpret_cast<const float4*>(&dlt[dbase + 4 * j]);
+        r = fmaf(-d4.x, ab[4 * j], r); r = fmaf(-d4.y, ab[4 * j + 1], r);
+        r = fmaf(-d4.z, ab[4 * j + 2], r); r = fmaf(-d4.w, ab[4 * j + 3], r);
+        // (16 deltas in flight at a time -- the next group's address "depends" on this group's sum: all 64 read ahead are 64 more live registers)
+        if ((j & 3) == 3) asm volatile("" : "+v"(dbase), "+v"(r));
+      }
+#ifdef CHAIN_CLOCK
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      if (blk == w - 1) ck_fold = __builtin_amdgcn_s_memtime() - ckf;
+#endif
+      __builtin_amdgcn_sched_barrier(0);             // (the fold's FMAs are not interleaved with the next 64 loads: that is 128 live registers)
+      if (w == blk + 2 && w >= 3) stage_diag();      // its region: free since the barrier behind block w - 3
     }
-    if (i < cnt) one(i, a0);
-    if (i + 1 < cnt) one(i + 1, a1);
-    if (i + 2 < cnt) one(i + 2, a2);
+    {                                                // ---- my block
+      const int blk = w;
+      // (rows read four steps ahead through ONE running index and immediate offsets; 8 spare rows behind the regions keep the last reads inside the array)
+      int reg = (w % 3) * 4096 + lane;
+      const int cnt = min(64, n_order - 64 * blk);
+      float a0 = diag[reg], a1 = diag[reg + 64], a2 = diag[reg + 128], a3 = diag[reg + 192];
+      auto one = [&](int i, float arow) {
+        const float nm = fmaf(tau, r, c);
+        float d = fmaf(nm, g, -e_old);
+        const unsigned long long ok = __ballot(nm >= thr);                  // (a NaN fails the test: the routine's guards see it)
+        if (__builtin_expect(!((ok >> i) & 1ull), 0)) {
+          // -6 < x < 26: the segment table (tn_mean_table.h) -- lane i's segment number into a scalar register, that segment's six
+          // coefficients out of their lanes by v_readlane, Horner in t = frac: ~20 instructions where the routine is ~50
+          const float xq = fmaxf(fmaf(nm, q1, -kTnMeanX0 * kTnMeanInvW), -1.0f);      // ((x - x0) / width; a NaN becomes -1)
+          const int kseg = __builtin_amdgcn_readlane((int)__builtin_floorf(xq), i);
+          float en;
+          if (__builtin_expect((unsigned)kseg < (unsigned)kTnMeanSeg, 1)) {
+            const float t = __builtin_amdgcn_fractf(xq);
+            float pz = rl(tc5, kseg);
+            pz = fmaf(pz, t, rl(tc4, kseg)); pz = fmaf(pz, t, rl(tc3, kseg)); pz = fmaf(pz, t, rl(tc2, kseg));
+            pz = fmaf(pz, t, rl(tc1, kseg)); pz = fmaf(pz, t, rl(tc0, kseg));
+            en = sig * pz;
+          } else {
+            // x >= 26 (an entry pinned at zero) or not a number: the routine, in the regime of lane i's x (its sign is the numerator's)
+            const unsigned long long xneg = __ballot(nm > 0.0f);
+            const float mu = nm * inv_tp;
+            en = ((xneg >> i) & 1ull) ? tn_mean_f32_regime<false>(mu, tau_p) : tn_mean_f32_regime<true>(mu, tau_p);
+          }
+          d = en - e_old;
 #ifdef CHAIN_CLOCK
-    const unsigned long long ck2 = __builtin_amdgcn_s_memtime();
-    if (lane == 0) { cks[w][0] = ck1; cks[w][1] = ck_fold; cks[w][2] = ck2; cks[w][3] = (unsigned long long)n_slow | ((unsigned long long)n_far << 32); }
+          ++n_slow;
 #endif
-    // the lane's residual froze at its own step: its mu, E and delta once more, for the other waves and the results
-    // (a lane whose step took the table or the routine: the routine's mean here -- the table's agrees with it to 3e-7)
-    const float nm = fmaf(tau, r, c);
-    const float mu = nm * inv_tp;
-    float ef, vf;
-    tn_moments_f32(mu, tau_p, &ef, &vf);
-    const bool fast = nm >= thr;
-    const float en = fast ? nm * g : ef;
-    dlt[p] = on ? (fast ? fmaf(nm, g, -e_old) : ef - e_old) : 0.f;
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (on) { a.mu[ent] = mu; a.tauq[ent] = tau_p; a.E[ent] = en; a.var[ent] = vf; }      // (behind the barrier: nobody waits for these)
-  }
-  for (int blk = w + 1; blk < nblk; ++blk) asm volatile("s_barrier" ::: "memory");      // ---- the blocks behind mine
+        }
+        const float delta = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, d), i));
+        r = fmaf(-delta, arow, r);
+      };
 #ifdef CHAIN_CLOCK
-  if (w == nblk - 1 && lane == 0) {
-    const unsigned long long ck3 = __builtin_amdgcn_s_memtime();
-    unsigned long long st = 0, fo = 0, gaps = 0; int ns = 0;
-    for (int b = 0; b < nblk; ++b) { st += cks[b][2] - cks[b][0]; fo += cks[b][1]; ns += (int)(cks[b][3] & 0xffffffffu); if (b) gaps += cks[b][0] - cks[b - 1][2]; }
-    printf("chain: %llu cycles from the prologue's end to the last wave's end; steps %llu, critical folds %llu, hand-overs (end of a block's steps -> start of the next one's) %llu, slow steps %d of %d; first block started %llu in, gap 0->1 %llu, 7->8 %llu\n",
-           ck3 - ck0, st, fo, gaps, ns, n_order, cks[0][0] - ck0, cks[1][0] - cks[0][2], cks[8][0] - cks[7][2]);
-  }
+      const unsigned long long ck1 = __builtin_amdgcn_s_memtime();
 #endif
-}
-__global__ __launch_bounds__(1024) void ssys_chain_vb_blocked_kernel(SSysChainVbArgs a) { ssys_chain_vb_blocked_body<0>(a); }
-__global__ __launch_bounds__(1024) void ssys_chain_vb_blocked_many(const SSysChainVbPack* list, int it) {
-  SSysChainVbPack p = load_pack(list, blockIdx.z);
-  p.a.order += (size_t)it * p.order_step;
-  ssys_chain_vb_blocked_body<1>(p.a);
-}
+      int i = 0;
+      for (; i + 4 <= cnt; i += 4) {
+        one(i, a0);     a0 = diag[reg + 256];
+        one(i + 1, a1); a1 = diag[reg + 320];
+        one(i + 2, a2); a2 = diag[reg + 384];
+        one(i + 3, a3); a3 = diag[reg + 448];
+        reg += 256;
+      }
+      if (i < cnt) one(i, a0);
+      if (i + 1 < cnt) one(i + 1, a1);
+      if (i + 2 < cnt) one(i + 2, a2);
+#ifdef CHAIN_CLOCK
+      const unsigned long long ck2 = __builtin_amdgcn_s_memtime();
+      if (lane == 0) { cks[w][0] = ck1; cks[w][1] = ck_fold; cks[w][2] = ck2; cks[w][3] = (unsigned long long)n_slow | ((unsigned long long)n_far << 32); }
+#endif
+      // the lane's residual froze at its own step: its mu, E and delta once more, for the other waves and the results
+      // (a lane whose step took the table or the routine: the routine's mean here -- the table's agrees with it to 3e-7)
+      const float nm = fmaf(tau, r, c);
+      const float mu = nm * inv_tp;
+      float ef, vf;
+      tn_moments_f32(mu, tau_p, &ef, &vf);
+      const bool fast = nm >= thr;
+      const float en = fast ? nm * g : ef;
+      dlt[p] = on ? (fast ? fmaf(nm, g, -e_old) : ef - e_old) : 0.f;
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      if (on) { a.mu[ent] = mu; a.tauq[ent] = tau_p; a.E[ent] = en; a.var[ent] = vf; }      // (behind the barrier: nobody waits for these)
+    }
+    for (int blk = w + 1; blk < nblk; ++blk) asm volatile("s_barrier" ::: "memory");      // ---- the blocks behind mine
+#ifdef CHAIN_CLOCK
+    if (w == nblk - 1 && lane == 0) {
+      const unsigned long long ck3 = __builtin_amdgcn_s_memtime();
+      unsigned long long st = 0, fo = 0, gaps = 0; int ns = 0;
+      for (int b = 0; b < nblk; ++b) { st += cks[b][2] - cks[b][0]; fo += cks[b][1]; ns += (int)(cks[b][3] & 0xffffffffu); if (b) gaps += cks[b][0] - cks[b - 1][2]; }
+      printf("chain: %llu cycles from the prologue's end to the last wave's end; steps %llu, critical folds %llu, hand-overs (end of a block's steps -> start of the next one's) %llu, slow steps %d of %d; first block started %llu in, gap 0->1 %llu, 7->8 %llu\n",
+             ck3 - ck0, st, fo, gaps, ns, n_order, cks[0][0] - ck0, cks[1][0] - cks[0][2], cks[8][0] - cks[7][2]);
+    }
+#endif
+  }
+};
 // BNMTF_VB_CHAIN=steps: the barrier-per-step kernel for whole passes too (A/B switch; no list form)
 static bool vb_chain_steps() { static const bool steps = [] { const char* e = getenv("BNMTF_VB_CHAIN"); return e && !strcmp(e, "steps"); }(); return steps; }
 bool trivb_ab_switch_set() { return vb_chain_steps(); }
 void launch_ssys_chain_vb(const SSysChainVbArgs& a, hipStream_t st, int order_step) {
   const bool steps = vb_chain_steps();
   const bool blocked = !(a.only_params || a.n_order < 64 || a.n_order > 1024 || a.n_order != a.K * a.L || !a.Aperm || steps);
-  const dim3 block(blocked ? ((a.n_order + 63) / 64) * 64 : 1024);
-  if (g_recorder) {
-    if (steps) { record_missing("ssys_chain_vb (BNMTF_VB_CHAIN=steps)"); return; }
-    SSysChainVbPack p; memset(&p, 0, sizeof(p));
-    p.a = a; p.order_step = order_step;
-    record_launch(blocked ? (const void*)ssys_chain_vb_blocked_many : (const void*)ssys_chain_vb_many, dim3(1), block, 0, p);
-    return;
-  }
-  if (!blocked) { hipLaunchKernelGGL(ssys_chain_vb_kernel, dim3(1), block, 0, st, a); return; }
-  hipLaunchKernelGGL(ssys_chain_vb_blocked_kernel, dim3(1), block, 0, st, a);
+  if (steps && record_missing("ssys_chain_vb (BNMTF_VB_CHAIN=steps)")) return;
+  SSysChainVbForms::Args p; memset(&p, 0, sizeof(p));
+  p.a = a; p.order_step = order_step;
+  if (blocked) launch_forms<SSysChainVbBlocked>(p, st, ((a.n_order + 63) / 64) * 64);
+  else launch_forms<SSysChainVb>(p, st);
 }
 
 // fp64 factor matrices of the masked bilinear sums of exp_square_diff (:235-239), for metric_kernel (sum over the mask of
@@ -477,39 +455,37 @@ void launch_tri_factors(const TriFactorArgs& a, hipStream_t st) {
 }
 
 // exp_square_diff's third term, sum_Omega varF . ((E[S] E[G]^T)^2 - E[S]^2 (E[G]^2)^T) (:238), as a sum over (j, k): the masked
-// sums mv[j][k] = sum_{i in Omega_j} varF_ik are what the G step's covariance term has just used (masked_colsum_kernel), the
+// sums mv[j][k] = sum_{i in Omega_j} varF_ik are what the G step's covariance term has just used (MaskedColsum), the
 // bracket is a function of row j of E[G] and row k of E[S].  One thread per (j, k), fp64 partial sum per block.
-template <int LIST>
-__device__ __forceinline__ void tri_third_body(TriThirdArgs a, unsigned block) {
-  __shared__ float Ss[32 * 32];
-  __shared__ double red[4];
-  for (int t = threadIdx.x; t < a.K * a.L; t += 256) Ss[t] = a.S[t];
-  __syncthreads();
-  const int j = block * 8 + (threadIdx.x >> 5), k = threadIdx.x & 31;
-  double v = 0.0;
-  if (j < a.rows && k < a.K) {
-    const float* g = a.G + (size_t)j * 32;
-    float m = 0.f, sq = 0.f;
-    for (int l = 0; l < a.L; ++l) { const float t = g[l] * Ss[k * a.L + l]; m += t; sq = fmaf(t, t, sq); }
-    v = (double)a.mv[(size_t)j * 32 + k] * ((double)m * (double)m - (double)sq);
-  }
+struct TriThird {
+  typedef TriThirdArgs Args;
+  static constexpr int kThreads = 256;
+  static __host__ __device__ int blocks(const Args& a) { return tri_third_blocks(a.rows); }
+  template <int FORM>
+  static __device__ __forceinline__ void body(const Args& a, int, int) {
+    const unsigned block = blockIdx.x;
+    __shared__ float Ss[32 * 32];
+    __shared__ double red[4];
+    for (int t = threadIdx.x; t < a.K * a.L; t += 256) Ss[t] = a.S[t];
+    __syncthreads();
+    const int j = block * 8 + (threadIdx.x >> 5), k = threadIdx.x & 31;
+    double v = 0.0;
+    if (j < a.rows && k < a.K) {
+      const float* g = a.G + (size_t)j * 32;
+      float m = 0.f, sq = 0.f;
+      for (int l = 0; l < a.L; ++l) { const float t = g[l] * Ss[k * a.L + l]; m += t; sq = fmaf(t, t, sq); }
+      v = (double)a.mv[(size_t)j * 32 + k] * ((double)m * (double)m - (double)sq);
+    }
 #pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) a.part[block] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-__global__ __launch_bounds__(256) void tri_third_kernel(TriThirdArgs a) { tri_third_body<0>(a, blockIdx.x); }
-int tri_third_blocks(int rows) { return (rows + 7) / 8; }
-__global__ __launch_bounds__(256) void tri_third_many(const TriThirdArgs* list, int) {
-  const TriThirdArgs a = load_pack(list, blockIdx.z);
-  if ((int)blockIdx.x >= (a.rows + 7) / 8) return;                  // (tri_third_blocks)
-  tri_third_body<1>(a, blockIdx.x);
-}
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) a.part[block] = (red[0] + red[1]) + (red[2] + red[3]);
+  }
+};
 void launch_tri_third(const TriThirdArgs& a, hipStream_t st) {
   if (a.rows <= 0) return;
-  if (record_launch((const void*)tri_third_many, dim3(tri_third_blocks(a.rows)), dim3(256), 0, a, true)) return;
-  hipLaunchKernelGGL(tri_third_kernel, dim3(tri_third_blocks(a.rows)), dim3(256), 0, st, a);
+  launch_forms<TriThird>(a, st);
 }
 
 }  // namespace bnmtf

@@ -128,7 +128,7 @@ struct FastArgs {
   double* stats;               // [blocks][4] partial (sum P.X', sum_miss q, sum_miss q^2) or null
   // VB sweep (kernel_sweep_vb.hip)
   const float* XoS;            // other factor's (E, S2) pair panels [KP][ld2_o][2]
-  float* vb_asq; float* vb_vsq;  // [rows][KP] per (unit, column): sum_miss S2other, sum_miss Eother^2 (for vb_pieces_kernel)
+  float* vb_asq; float* vb_vsq;  // [rows][KP] per (unit, column): sum_miss S2other, sum_miss Eother^2 (for VbPieces)
   // VB on the on-chip kernels (sweep_chip.inc, MODE = kSweepVB): the two masked sums of every (unit, column), from
   // kernel_maskgemm.hip: [msplit][n_pad][2 KP] slabs, columns [0, KP) = sum_miss S2other, [KP, 2 KP) = sum_miss Eother^2
   const float* mslabs; int msplit;
@@ -356,12 +356,12 @@ struct SSysGemmArgs {       // slabs[s][p][r] = sum_{j in range s} Wc[j][p] Gc[j
   const float* Wc; const float* Gc;
   float* slabs;                        // [nsplit][tri_padded(K)][tri_padded(L)]
 };
-inline int ssys_gemm_wave_tiles(int K, int L) { return (tri_padded(K) / 64) * (tri_padded(L) / 64); }
-__host__ __device__ inline int ssys_gemm_range(int n, int nsplit) { return ((n + nsplit - 1) / nsplit + 15) & ~15; }     // columns per range of ssys_gemm_bf16_kernel: a multiple of a step
+__host__ __device__ inline int ssys_gemm_wave_tiles(int K, int L) { return (tri_padded(K) / 64) * (tri_padded(L) / 64); }
+__host__ __device__ inline int ssys_gemm_range(int n, int nsplit) { return ((n + nsplit - 1) / nsplit + 15) & ~15; }     // columns per range of SSysGemmBf16: a multiple of a step
 void launch_ssys_gemm(const SSysGemmArgs& a, hipStream_t st);
 bool ssys_ab_switch_set();          // an A/B switch of kernel_ssys.hip that has no list form is set (BNMTF_SCOL_GRAM=f32, BNMTF_SSYS_GEMM=f32)
 struct SSysBArgs { int n, n0, K, L; const float* slabs; int split, n_pad; const float* G; float* b; };   // b[block][K L]: per 64-column block partials of sum_j Pv_jk G_jl
-inline int ssys_b_blocks(int n) { return (n + 63) / 64 > 0 ? (n + 63) / 64 : 1; }
+__host__ __device__ inline int ssys_b_blocks(int n) { return (n + 63) / 64 > 0 ? (n + 63) / 64 : 1; }
 void launch_ssys_b(const SSysBArgs& a, hipStream_t st);
 void launch_ssys_reduce(const float* slabs, int nsplit, int K, int L, float* A, hipStream_t st);   // sum the slabs on k <= k', mirror
 void launch_ssys_sum_parts(const float* parts, int nparts, size_t n, float* out, hipStream_t st);
@@ -375,10 +375,10 @@ struct SSysChainArgs {
   float min_x;
   const float* A; const float* r0; float* S; const float* lambdaS; const float* tau;
   uint32_t key0, key1, it;
-  const float4* cands;                 // [K L][4] {-log u1, z, u2, -} of iteration `it` (ssys_residual_kernel); draws only
-  const float* Tinv;                   // [K][32][32]: (I + N_k)^-1 of every row's diagonal block (ssys_residual_kernel's extra blocks)
-  const float4* own8; const float4* recT;   // [K L][2] per-entry and [K L][4] per-candidate constants of the draws (ssys_residual_kernel)
-  const float* Tn;                     // [K L]: the row's own old values up to the entry put back (ssys_residual_kernel)
+  const float4* cands;                 // [K L][4] {-log u1, z, u2, -} of iteration `it` (SSysResidual); draws only
+  const float* Tinv;                   // [K][32][32]: (I + N_k)^-1 of every row's diagonal block (SSysResidual's extra blocks)
+  const float4* own8; const float4* recT;   // [K L][2] per-entry and [K L][4] per-candidate constants of the draws (SSysResidual)
+  const float* Tn;                     // [K L]: the row's own old values up to the entry put back (SSysResidual)
   double* numer_out; double* tau_out;
 };
 void launch_ssys_chain(const SSysChainArgs& a, hipStream_t st);
@@ -411,7 +411,7 @@ void launch_tri_factors(const TriFactorArgs& a, hipStream_t st);
 // exp_square_diff's third term (bnmtf_vb_optimised.py:238) from the masked variance sums the G step already holds:
 //   sum_jk mv[j][k] ((sum_l S_kl G_jl)^2 - sum_l S_kl^2 G_jl^2),  mv[j][k] = sum_{i in Omega_j} varF_ik;  one partial sum per block
 struct TriThirdArgs { int rows, K, L; const float* G; const float* S; const float* mv; double* part; };
-int tri_third_blocks(int rows);
+__host__ __device__ inline int tri_third_blocks(int rows) { return (rows + 7) / 8; }   // eight rows per block
 void launch_tri_third(const TriThirdArgs& a, hipStream_t st);
 
 // ---------------------------------------------------------------------------
@@ -514,7 +514,7 @@ void launch_np_sweep(const NpSweepArgs& a, hipStream_t st);
 void launch_np_stats_finish(const double* part, int nb, double* out, hipStream_t st);   // out[8] = column sums of part[nb][8]
 void launch_np_small_product(const float* S, int sc, int sa, const float* in, int A, int C, int n, float* out, hipStream_t st);
 void launch_np_build_p(const float* Rn, const float* Ut, const float* Yt, int I, int J, int K, float* P, hipStream_t st);
-int np_s_blocks(int I);
+__host__ __device__ inline int np_s_blocks(int I) { return I < 1024 ? I : 1024; }   // blocks of a pass of the S step
 void launch_np_s_pass(const NpSPassArgs& a, hipStream_t st);
 void record_np_copy(const float* src, float* dst, int n);   // (many.h: a list-form record only) dst[0 .. n) = src[0 .. n)
 void launch_np_metrics(const float* R, const uint8_t* M, const float* Ut, const float* Yt, int I, int J, int K, double* part, hipStream_t st);
@@ -811,7 +811,7 @@ struct OnpEffArgs {         // out = X . S (transposeS = 0: inner K, width L) or
   float* out; int ldo;               // [n][ldo], the padding columns zero
   float* outT; int ldT;              // [width][ldT]
 };
-struct OnpSPassArgs {       // one pass of NMTF's S step over the row list (np_s_pass_kernel's scheme)
+struct OnpSPassArgs {       // one pass of NMTF's S step over the row list (NpSPass's scheme)
   const uint32_t* ptr; const uint32_t* idx; const float* val; int I;
   const float* F; int ldF;           // [I][ldF]
   const float* GT; int ldGT;         // [L][ldGT]

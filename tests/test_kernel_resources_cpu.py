@@ -24,11 +24,11 @@ LIMITS = [
     ("kernel_sweep_wide.hip", "sweep_chip_kernelILi2ELi0ELi16ELi0ELi1ELi1ELi0EE", 128, 120),   # Gibbs sweep, draws, 16 waves, split sampler (cfg3)
     ("kernel_sweep_wide.hip", "sweep_chip_kernelILi2ELi1ELi16ELi0ELi1ELi1ELi0EE", 128, 120),   # ... mode updates
     # the non-probabilistic half sweep: 1 024-thread blocks under __launch_bounds__(1024), so 128 VGPRs and nothing to spill
-    # (measured 113, 104, 116 and 127; E = 16 is the only instance for rows longer than 8 192)
-    ("kernel_np.hip", "np_sweep_kernelILi2ELi16EE", 128, 0),
-    ("kernel_np.hip", "np_sweep_kernelILi4ELi8EE", 128, 0),
-    ("kernel_np.hip", "np_sweep_kernelILi8ELi4EE", 128, 0),
-    ("kernel_np.hip", "np_sweep_kernelILi16ELi1EE", 128, 0),
+    # (measured 113, 104, 116 and 127; E = 16 is the only instance for rows longer than 8 192); the single form of NpSweep<E, RB>
+    ("kernel_np.hip", "one_formINS_7NpSweepILi2ELi16EE", 128, 0),
+    ("kernel_np.hip", "one_formINS_7NpSweepILi4ELi8EE", 128, 0),
+    ("kernel_np.hip", "one_formINS_7NpSweepILi8ELi4EE", 128, 0),
+    ("kernel_np.hip", "one_formINS_7NpSweepILi16ELi1EE", 128, 0),
     # the observed-entry layout's sweeps (written on obs_common.h's ObsForm) and fold-in: 256-thread blocks meant to run four
     # waves per SIMD, and 512 / 4 = 128 -- the hardware's ceiling, not a measurement; nothing to spill
     ("kernel_obs.hip", "obs_sweep_kernelILi0EE", 128, 0),                         # Gibbs draws (kSweepDraw)

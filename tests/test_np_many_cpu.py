@@ -33,7 +33,7 @@ def test_entry_point_is_declared_exported_and_bound():
 
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="no hipcc")
 def test_list_form_sweeps_keep_the_register_budget():
-    """np_sweep_many<E, RB> runs np_sweep_kernel's body under the same __launch_bounds__(1024): at most 128 VGPRs, no spills
+    """list_form<NpSweep<E, RB>> runs one_form<NpSweep<E, RB>>'s body (csrc/many.h) under the same __launch_bounds__(1024): at most 128 VGPRs, no spills
     (read as tests/test_kernel_resources_cpu.py reads the single-model instances)."""
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
            "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, "kernel_np.hip"), "-o", os.devnull]
@@ -48,13 +48,13 @@ def test_list_form_sweeps_keep_the_register_budget():
         m = re.search(r"remark:\s+(VGPRs Spill|VGPRs): (\d+)", line)
         if m and name:
             found[name][m.group(1)] = int(m.group(2))
-    for sub in ("np_sweep_manyILi2ELi16EE", "np_sweep_manyILi4ELi8EE", "np_sweep_manyILi8ELi4EE", "np_sweep_manyILi16ELi1EE"):
+    for sub in ("list_formINS_7NpSweepILi2ELi16EE", "list_formINS_7NpSweepILi4ELi8EE", "list_formINS_7NpSweepILi8ELi4EE", "list_formINS_7NpSweepILi16ELi1EE"):
         hits = [n for n in found if sub in n]
         assert len(hits) == 1, (sub, sorted(found))
         r = found[hits[0]]
         assert r["VGPRs"] <= 128 and r["VGPRs Spill"] == 0, (hits[0], r)
     # the list forms' names leave the single-model kernels' guard (one hit per substring) alone
-    for sub in ("np_sweep_kernelILi2ELi16EE", "np_sweep_kernelILi4ELi8EE", "np_sweep_kernelILi8ELi4EE", "np_sweep_kernelILi16ELi1EE"):
+    for sub in ("one_formINS_7NpSweepILi2ELi16EE", "one_formINS_7NpSweepILi4ELi8EE", "one_formINS_7NpSweepILi8ELi4EE", "one_formINS_7NpSweepILi16ELi1EE"):
         assert len([n for n in found if sub in n]) == 1, sub
 
 

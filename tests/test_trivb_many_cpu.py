@@ -71,23 +71,30 @@ def _resources(tu):
     return subprocess.Popen(cmd, cwd=CSRC, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
 
 
+# translation unit: the kernels written once as a struct K (csrc/many.h), by K's mangled name -- one_form<K> and list_form<K>
+FORMS = {
+    "kernel_trivb.hip": ["14SmallProductVbE", "12MaskedColsumE", "11SSysChainVbE", "18SSysChainVbBlockedE", "11SSysPermuteE", "8TriThirdE"],
+    "kernel_ssys.hip": ["8SColGramILi1EE", "8SColGramILi0EE", "9GammaPackE", "12SSysGemmBf16E", "10SSysReduceE", "5SSysBE", "12SSysResidualE"],
+    "kernel_bnmtf.hip": ["11SlabProductE"],
+    "kernel_misc.hip": ["8VbFinishE"],
+    "kernel_sweep_vb.hip": ["8VbPiecesE"],
+    "kernel_np.hip": ["7NpSweepILi2ELi16EE", "7NpSweepILi4ELi8EE", "7NpSweepILi8ELi4EE", "7NpSweepILi16ELi1EE", "13NpStatsFinishE", "14NpSmallProductE",
+                      "8NpBuildPE", "7NpSPassE"],
+    # (in the file's unnamed namespace)
+    "kernel_heldout.hip": ["12_GLOBAL__N_1%s" % k for k in ("7HeldoutILi32ELb1EE", "7HeldoutILi64ELb1EE", "7HeldoutILi32ELb0EE", "7HeldoutILi64ELb0EE",
+                                                             "9HeldoutNpILb1EE", "9HeldoutNpILb0EE", "11HeldoutFoldE")],
+}
+# the pairs that are still written by hand: (single-model kernel, its list form)
+# (the 8 + 2-wave shape: a model whose sweeps take the 16-wave one is not batched -- api_many.inc, trivb_batchable)
+PAIRS = {"kernel_sweep_vb.hip": [("sweep_vb_kernelILi1ELi8ELi2ELi1EE", "sweep_vb_manyILi1ELi8ELi2ELi1EE")]}
+
+
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="no hipcc")
 def test_list_forms_keep_the_single_model_kernels_budgets():
     """Every list form runs its single-model kernel's body under the same launch bounds: no more VGPRs than a ceiling with room
-    over the single-model kernel's, and no spills where it has none (read as tests/test_kernel_resources_cpu.py reads them)."""
-    pairs = {   # translation unit: [(single-model kernel, its list form)]
-        "kernel_trivb.hip": [("small_product_vb_kernel", "small_product_vb_many"), ("masked_colsum_kernel", "masked_colsum_many"),
-                             ("ssys_chain_vb_kernel", "ssys_chain_vb_many"), ("ssys_permute_kernel", "ssys_permute_many"),
-                             ("ssys_chain_vb_blocked_kernel", "ssys_chain_vb_blocked_many"), ("tri_third_kernel", "tri_third_many")],
-        "kernel_ssys.hip": [("scol_gram_kernelILi1ELi1EE", "scol_gram_manyILi1EE"), ("scol_gram_kernelILi0ELi1EE", "scol_gram_manyILi0EE"),
-                            ("gamma_pack_kernel", "gamma_pack_many"), ("ssys_gemm_bf16_kernel", "ssys_gemm_bf16_many"),
-                            ("ssys_reduce_kernel", "ssys_reduce_many"), ("ssys_b_kernel", "ssys_b_many"),
-                            ("ssys_residual_kernel", "ssys_residual_many")],
-        "kernel_bnmtf.hip": [("slab_product_kernel", "slab_product_many")],
-        # (the 8 + 2-wave shape: a model whose sweeps take the 16-wave one is not batched -- api_many.inc, trivb_batchable)
-        "kernel_sweep_vb.hip": [("sweep_vb_kernelILi1ELi8ELi2ELi1EE", "sweep_vb_manyILi1ELi8ELi2ELi1EE")],
-    }
-    procs = {tu: _resources(tu) for tu in pairs}
+    over the single-model kernel's, and no spills where it has none (read as tests/test_kernel_resources_cpu.py reads them).  The
+    two forms of a struct K share the body, so they hold the same bytes of LDS, and neither has scratch."""
+    procs = {tu: _resources(tu) for tu in FORMS}
     for tu, p in procs.items():
         out = p.communicate(timeout=900)[0]
         assert p.returncode == 0, out[-2000:]
@@ -97,13 +104,17 @@ def test_list_forms_keep_the_single_model_kernels_budgets():
             if m:
                 name = m.group(1); found[name] = {}
                 continue
-            m = re.search(r"remark:\s+(VGPRs Spill|VGPRs): (\d+)", line)
+            m = re.search(r"remark:\s+(VGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", line)
             if m and name:
                 found[name][m.group(1)] = int(m.group(2))
-        for single, many in pairs[tu]:
+        pairs = [("one_formINS_%s" % k, "list_formINS_%s" % k, True) for k in FORMS[tu]] + [(a, b, False) for a, b in PAIRS.get(tu, [])]
+        for single, many, shared in pairs:
             hs = [n for n in found if single in n]
             hm = [n for n in found if many in n]
             assert len(hs) == 1 and len(hm) == 1, (tu, single, many, sorted(found))
             rs, rm = found[hs[0]], found[hm[0]]
             assert rm["VGPRs"] <= max(rs["VGPRs"] + 16, 32), (hm[0], rm, rs)
             assert rm["VGPRs Spill"] <= rs["VGPRs Spill"] + 8, (hm[0], rm, rs)
+            if shared:
+                assert rm["LDS Size [bytes/block]"] == rs["LDS Size [bytes/block]"], (hm[0], rm, rs)
+                assert rm["ScratchSize [bytes/lane]"] == 0 and rs["ScratchSize [bytes/lane]"] == 0, (hm[0], rm, rs)
