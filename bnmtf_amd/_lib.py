@@ -114,6 +114,7 @@ _SIGS = {
     "bnmtf_np_run_many": ([_P, C.c_int, C.c_int, _P, _P, _P, _P], C.c_int),
     "bnmtf_slot_layout": ([C.c_int, C.c_int, C.c_int, C.c_int] + [_P] * 14, C.c_int),
     "bnmtf_handover_dump": ([_P, C.c_int] + [_P] * 6, C.c_int),
+    "bnmtf_post_dump": ([_P, C.c_int] + [_P] * 11, C.c_int),
     "bnmtf_obs_create": ([C.c_int, C.c_int, C.c_int, C.c_uint64, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_uint64, C.c_int, C.POINTER(_P)], C.c_int),
     "bnmtf_obs_build_lists": ([C.c_int, C.c_int, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "bnmf_obs_set_state": ([_P, _P, _P, C.c_double], C.c_int),

@@ -1206,6 +1206,43 @@ int bnmtf_handover_dump(bnmtf_handle h, int which, int64_t* info, uint32_t* t_in
   return BNMTF_OK;
 } BNMTF_ABI_GUARD
 
+int bnmtf_post_dump(bnmtf_handle h, int which, int64_t* info, float* X, float* S2, float* XT, float* XT2, float* S2T, float* XS,
+                    double* C64, float* C32, double* colsum, double* colsum2) try {
+  if (!h || h->obs || h->np) { set_error("bnmtf_post_dump: the handle has no dense-layout factor buffers (layout='observed' or bnmtf_np_create)"); return BNMTF_ESTATE; }
+  if (!info || which < 0 || which > 1) { set_error("bnmtf_post_dump: null info or which=%d (0 rows, 1 cols)", which); return BNMTF_EINVAL; }
+  if (!h->std_built || (h->small && h->small_cur && !h->std_cur)) {
+    set_error("bnmtf_post_dump: the state lives on the one-launch small path, which has no relayout or Gram buffers");
+    return BNMTF_ESTATE;
+  }
+  const Dir& d = which ? h->cols : h->rows;
+  if (!d.X || !d.XT || !d.XT2 || !d.C64 || !d.C32 || !d.colsum) { set_error("bnmtf_post_dump: the handle has no relayout or Gram buffers"); return BNMTF_ESTATE; }
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (h->tail_stream) HIPCHK(hipStreamSynchronize(h->tail_stream));
+  if (h->xchg_stream) HIPCHK(hipStreamSynchronize(h->xchg_stream));
+  if (d.gram_pending && d.ev_gram_all) HIPCHK(hipEventSynchronize(d.ev_gram_all));      // (what await_gram waits for; the flag stays)
+  // which of its buffers the last variational relayout wrote: enqueue_post's rule
+  const bool vb = (h->vb_ready || h->tri_ready) && d.S2 && d.S2T && d.colsum2;
+  const bool chip = vb && vb_chip_ok(h->rows, h->cols) && vb_chip_ok(h->cols, h->rows);
+  const bool xs = vb && d.XS && !chip, umax = vb && chip && d.xb_umax_posted;
+  const size_t nx = (size_t)d.nglob * d.KP, nt = (size_t)d.KP * d.ldT, nc = (size_t)d.KP * d.KP;
+  const int64_t scalars[BNMTF_POST_INFO_LEN] = {d.nglob, d.KP, d.W, d.ldT, post_blocks(d.nglob), vb, xs, umax, d.n0, d.n,
+                                                 (int64_t)nx, (int64_t)(vb ? nx : 0), (int64_t)nt, (int64_t)nt, (int64_t)(vb ? nt : 0), (int64_t)(xs ? 2 * nt : 0),
+                                                 (int64_t)nc, (int64_t)nc, d.KP, vb ? d.KP : 0};
+  memcpy(info, scalars, sizeof(scalars));
+  if (X) HIPCHK(hipMemcpy(X, d.X, nx * sizeof(float), hipMemcpyDeviceToHost));
+  if (S2 && vb) HIPCHK(hipMemcpy(S2, d.S2, nx * sizeof(float), hipMemcpyDeviceToHost));
+  if (XT) HIPCHK(hipMemcpy(XT, d.XT, nt * sizeof(float), hipMemcpyDeviceToHost));
+  if (XT2) HIPCHK(hipMemcpy(XT2, d.XT2, nt * sizeof(float), hipMemcpyDeviceToHost));
+  if (S2T && vb) HIPCHK(hipMemcpy(S2T, d.S2T, nt * sizeof(float), hipMemcpyDeviceToHost));
+  if (XS && xs) HIPCHK(hipMemcpy(XS, d.XS, 2 * nt * sizeof(float), hipMemcpyDeviceToHost));
+  if (C64) HIPCHK(hipMemcpy(C64, d.C64, nc * sizeof(double), hipMemcpyDeviceToHost));
+  if (C32) HIPCHK(hipMemcpy(C32, d.C32, nc * sizeof(float), hipMemcpyDeviceToHost));
+  if (colsum) HIPCHK(hipMemcpy(colsum, d.colsum, d.KP * sizeof(double), hipMemcpyDeviceToHost));
+  if (colsum2 && vb) HIPCHK(hipMemcpy(colsum2, d.colsum2, d.KP * sizeof(double), hipMemcpyDeviceToHost));
+  return BNMTF_OK;
+} BNMTF_ABI_GUARD
+
 int bnmtf_omega_counts(bnmtf_handle h, uint64_t* total, uint32_t* row, uint32_t* col) try {
   CHK(refuse_obs(h, "bnmtf_omega_counts"));
   if (total) *total = (uint64_t)h->n_obs;

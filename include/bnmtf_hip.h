@@ -119,6 +119,21 @@ BNMTF_API int bnmtf_slot_layout(int n, int m, int KP, int world, const uint32_t*
 BNMTF_API int bnmtf_handover_dump(bnmtf_handle h, int which, int64_t* info, uint32_t* t_in, uint32_t* t_out, uint32_t* pk,
                                   uint32_t* region_ofs, float* region);
 
+/* A TEST HOOK like bnmtf_handover_dump: what the relayout and Gram kernels behind a half sweep or a state upload (post_kernel,
+ * gram_reduce_kernel, gram_cast_kernel; csrc/kernel_post.hip) read and wrote for one direction (which = 0 rows, 1 cols) of a
+ * dense-layout handle, copied to the host so that every output can be restated bit for bit (tests/test_post_exact_gpu.py).
+ * Synchronises the compute stream, the tail stream and the exchange stream, waits for a summed Gram that is still on its way as the
+ * loop would, launches nothing, changes no state; BNMTF_ESTATE for a handle without these buffers (layout='observed',
+ * bnmtf_np_create, a model whose state lives on the one-launch small path).
+ * info [BNMTF_POST_INFO_LEN]: rows (of the whole factor), KP, W, ldT, nblk (blocks of 32 rows), whether the handle is a
+ * variational one, whether its relayout writes XS, whether it posts the column maxima (umax), this rank's first row and row
+ * count, then the element counts of the ten arrays in argument order (0: the handle has none).  An array is copied where its
+ * pointer is not NULL and its count is not 0 (a first call with NULL arrays gives the sizes).  X, S2 [rows][KP] as the kernels
+ * read them; XT, S2T [KP][ldT]; XT2 [KP / 2][ldT][2]; XS [KP][ldT][2]; C64, C32 [KP][KP]; colsum, colsum2 [KP]. */
+#define BNMTF_POST_INFO_LEN 20
+BNMTF_API int bnmtf_post_dump(bnmtf_handle h, int which, int64_t* info, float* X, float* S2, float* XT, float* XT2, float* S2T,
+                              float* XS, double* C64, float* C32, double* colsum, double* colsum2);
+
 /* size_Omega and the per-row / per-column observed counts (bit-exact integers;
  * size_Omega = M.sum(), bnmf_gibbs_optimised.py:65; counts :83-84).
  * row/col may be NULL. */
