@@ -153,6 +153,8 @@ _SIGS = {
     "bnmtf_fold_in": ([C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, _P, _P, C.c_double, _P, _P, C.c_uint64,
                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _P, _P, _P, _P], C.c_int),
     "bnmtf_fold_in_times": ([C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
+    "bnmtf_predictive_moments": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "bnmtf_predictive_moments_times": ([C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -1,4 +1,4 @@
-"""What the calls on a fitted model share (posterior_predictive, top_entries, fold_in; DESIGN.md sections 2.8 - 2.10): which kind
+"""What the calls on a fitted model share (posterior_predictive, variational_predictive, top_entries, fold_in; DESIGN.md sections 2.8 - 2.10): which kind
 of class a model is, the factors its predict() multiplies, the checks of stored samples, of factor shapes and of entry lists, and
 the finish of the shifted moments.  Everything here runs on the host and refuses with a BnmtfError '<who>: <why>'."""
 import numpy as np

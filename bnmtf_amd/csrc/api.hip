@@ -148,7 +148,7 @@ struct DevBuf {
   int alloc(size_t count, bool zero = false) { return dalloc(&p, count, zero); }
   ~DevBuf() { dfree(p); }
 };
-// the stream and the three events of one call that takes no handle (api_predictive.inc, api_top.inc, api_foldin.inc): event 0
+// the stream and the three events of one call that takes no handle (api_predictive.inc, api_top.inc, api_foldin.inc, api_predictive_q.inc): event 0
 // before an upload, 1 behind it, 2 behind the kernel; released on every return path
 struct CallScope {
   hipStream_t s = nullptr;
@@ -172,8 +172,8 @@ struct CallScope {
     if (s) (void)hipStreamDestroy(s);
   }
 };
-// upload and kernel time of this host thread's last call of each of the three, from the events (bnmtf_*_times)
-enum CallKind { kCallPredictive, kCallTop, kCallFoldIn, kCallKinds };
+// upload and kernel time of this host thread's last call of each of the four, from the events (bnmtf_*_times)
+enum CallKind { kCallPredictive, kCallTop, kCallFoldIn, kCallPredictiveQ, kCallKinds };
 static thread_local double g_call_ms[kCallKinds][2] = {};
 static int call_times(const char* who, CallKind kind, double* upload_ms, double* kernel_ms) {
   if (!upload_ms || !kernel_ms) { set_error("%s: null argument", who); return BNMTF_EINVAL; }
@@ -1793,4 +1793,5 @@ int bnmtf_gamma_sample(double alpha, double beta, uint64_t seed, uint64_t it, in
 #include "api_many.inc"
 #include "api_top.inc"
 #include "api_foldin.inc"
+#include "api_predictive_q.inc"
 #include "api_predictive.inc"

@@ -636,6 +636,25 @@ struct PredictiveArgs {
 };
 void launch_predictive(const PredictiveArgs& a, hipStream_t st);
 
+// Closed-form predictive mean and variance under a mean-field q over a row-sorted entry list (kernel_predictive_q.hip;
+// bnmtf_predictive_moments): the factors' means and variances in fp64, one launch (two for the
+// tri-factorisation: the column table H = G S^T first)
+constexpr int kPredictiveQRows = kHeldoutRowsPerBlock;  // a wave per row, heldout_blocks(I) blocks
+constexpr int kPredictiveQStep = 64;                     // entries of a row per wave step: a lane each
+constexpr int kPredictiveQStaged = 4;                    // staged arrays per wave: 4 x 256 doubles, 32 KiB per block
+struct PredictiveQArgs {
+  const uint32_t* rowptr;            // [I + 1] the entries of row i are [rowptr[i], rowptr[i + 1])
+  const uint32_t* col;               // [n] their columns
+  const double* EA; const double* VA;   // [I][K] mean and variance of U, or F; unpadded.  VA null: a = 0
+  const double* ES; const double* VS;   // [K][L], or null (L = 0).  VS null: b = 0
+  const double* EB; const double* VB;   // [J][W], W = L ? L : K: V, or G.  VB null: c = 0
+  double* H;                         // [J][hstride] (G S^T)_jk, the pad column zero; written by the table pass (L > 0), else null
+  int I, J, K, L;                    // K, L <= kObsMaxRank
+  int hstride;                       // K rounded up to 2 doubles: a row of H begins on a 16-byte boundary
+  double* mean; double* var;         // [n] in list order
+};
+void launch_predictive_q(const PredictiveQArgs& a, hipStream_t st);   // predictive_q_table_kernel (L > 0), then the entry pass
+
 // The n best columns of every selected row under a total order (kernel_top.hip; bnmtf_top_entries): a wave
 // per (row, column segment) pair, its sorted list in LDS, and a merge of a row's segment lists
 constexpr int kTopRows = kHeldoutRowsPerBlock;           // waves per block: a (row, segment) pair each

@@ -668,6 +668,29 @@ BNMTF_API int bnmtf_fold_in(int device, int n_units, int m, int W, const double*
  * BNMTF_OK; zeros before one did (tools/fold_in_rates.py) */
 BNMTF_API int bnmtf_fold_in_times(double* upload_ms, double* kernel_ms);
 
+/* ---- closed-form predictive mean and variance under a mean-field q over an entry list (bnmtf_amd.variational_predictive;
+ * DESIGN.md section 2.8a) -------------------------------------------------------------------------------------------------------
+ * No handle: the call makes its own stream and buffers on `device` and frees all of them on every path.  The means E* and
+ * variances V* of q, fp64, contiguous: EA, VA [I][K]; L = 0: ES and VS null, EB, VB [J][K]; L >= 1: ES, VS [K][L], EB, VB [J][L];
+ * 1 <= K <= BNMTF_PREDICTIVE_Q_MAX_RANK, 0 <= L <= BNMTF_PREDICTIVE_Q_MAX_RANK.  Any of VA, VS, VB may be null: that factor is
+ * fixed, its variance zero.  Every mean is finite, every variance finite and >= 0.  Per entry e = (rows[e], cols[e]) -- any
+ * order, an entry may occur more than once, 1 <= n < 2^31 -- with f, a = EA[i], VA[i]; s, b = ES, VS; g, c = EB[j], VB[j]:
+ *   L = 0   mean_out[e] = sum_k f_k g_k          var_out[e] = sum_k [ a_k g_k^2 + c_k (f_k^2 + a_k) ]
+ *   L >= 1  mean_out[e] = sum_l (f S)_l g_l      var_out[e] = sum_k a_k (S g)_k^2 + sum_l [ c_l ((f S)_l^2 + u_l) + (g_l^2 + c_l) w_l ]
+ *           u_l = sum_k a_k s_kl^2,  w_l = sum_k b_kl (f_k^2 + a_k)
+ * the variance of the product under q, whose entries are independent; the noise of an observation is not in it.  All fp64, every
+ * sum an fma chain over its index ascending from 0.0: an entry's two numbers depend on that entry and the moments alone, not on the
+ * list's order or on what else is in it.  Device memory is O((I + J)(K + L) + K L + n).  Everything is checked before the first
+ * device call. */
+#define BNMTF_PREDICTIVE_Q_MAX_RANK 256
+BNMTF_API int bnmtf_predictive_moments(int device, int I, int J, int K, int L, uint64_t n,
+    const int32_t* rows, const int32_t* cols,
+    const double* EA, const double* VA, const double* ES, const double* VS, const double* EB, const double* VB,
+    double* mean_out, double* var_out);
+/* upload and kernel time (ms, from events on the call's stream) of the calling host thread's last bnmtf_predictive_moments that
+ * returned BNMTF_OK; zeros before one did (tools/predictive_q_rates.py) */
+BNMTF_API int bnmtf_predictive_moments_times(double* upload_ms, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
