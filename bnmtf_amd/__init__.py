@@ -20,5 +20,6 @@ from .predictive import posterior_predictive
 from .top_entries import top_entries
 from .fold_in import fold_in
 from .predictive_q import variational_predictive
+from .log_predictive import log_predictive
 
-__all__ = ["bnmf_gibbs_optimised", "bnmf_gibbs", "bnmtf_gibbs_optimised", "bnmtf_gibbs", "bnmf_vb_optimised", "bnmf_vb", "bnmf_vb_observed", "bnmtf_vb_optimised", "bnmtf_vb", "bnmtf_vb_observed", "nmf_icm", "nmtf_icm", "NMF", "NMTF", "run_many", "Entries", "posterior_predictive", "top_entries", "fold_in", "variational_predictive", "device_count", "BnmtfError", "lib", "LIB_PATH", "EXPORTS"]
+__all__ = ["bnmf_gibbs_optimised", "bnmf_gibbs", "bnmtf_gibbs_optimised", "bnmtf_gibbs", "bnmf_vb_optimised", "bnmf_vb", "bnmf_vb_observed", "bnmtf_vb_optimised", "bnmtf_vb", "bnmtf_vb_observed", "nmf_icm", "nmtf_icm", "NMF", "NMTF", "run_many", "Entries", "posterior_predictive", "top_entries", "fold_in", "variational_predictive", "log_predictive", "device_count", "BnmtfError", "lib", "LIB_PATH", "EXPORTS"]

@@ -155,6 +155,9 @@ _SIGS = {
     "bnmtf_fold_in_times": ([C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
     "bnmtf_predictive_moments": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "bnmtf_predictive_moments_times": ([C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
+    "bnmtf_log_predictive_samples": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64,
+                                      C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "bnmtf_log_predictive_times": ([C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 

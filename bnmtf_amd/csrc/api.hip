@@ -148,7 +148,7 @@ struct DevBuf {
   int alloc(size_t count, bool zero = false) { return dalloc(&p, count, zero); }
   ~DevBuf() { dfree(p); }
 };
-// the stream and the three events of one call that takes no handle (api_predictive.inc, api_top.inc, api_foldin.inc, api_predictive_q.inc): event 0
+// the stream and the three events of one call that takes no handle (api_predictive.inc, api_log_predictive.inc, api_top.inc, api_foldin.inc, api_predictive_q.inc): event 0
 // before an upload, 1 behind it, 2 behind the kernel; released on every return path
 struct CallScope {
   hipStream_t s = nullptr;
@@ -172,12 +172,45 @@ struct CallScope {
     if (s) (void)hipStreamDestroy(s);
   }
 };
-// upload and kernel time of this host thread's last call of each of the four, from the events (bnmtf_*_times)
-enum CallKind { kCallPredictive, kCallTop, kCallFoldIn, kCallPredictiveQ, kCallKinds };
+// upload and kernel time of this host thread's last call of each of the five, from the events (bnmtf_*_times)
+enum CallKind { kCallPredictive, kCallTop, kCallFoldIn, kCallPredictiveQ, kCallLogPredictive, kCallKinds };
 static thread_local double g_call_ms[kCallKinds][2] = {};
 static int call_times(const char* who, CallKind kind, double* upload_ms, double* kernel_ms) {
   if (!upload_ms || !kernel_ms) { set_error("%s: null argument", who); return BNMTF_EINVAL; }
   *upload_ms = g_call_ms[kind][0]; *kernel_ms = g_call_ms[kind][1];
+  return BNMTF_OK;
+}
+
+// What the calls over an entry list and the host's stored samples share (api_predictive.inc, api_log_predictive.inc; the sort also
+// api_predictive_q.inc).
+// The list by row, in the given order within a row: a stable counting sort.  rowptr [I + 1], col [n] the columns in list order,
+// perm [n] the given position of list position q: the outputs are scattered back through it.
+static void sort_entries_by_row(int I, uint64_t n, const int32_t* rows, const int32_t* cols, std::vector<uint32_t>& rowptr,
+                                std::vector<uint32_t>& col, std::vector<uint32_t>& perm) {
+  rowptr.assign((size_t)I + 1, 0u); col.resize(n); perm.resize(n);
+  for (uint64_t e = 0; e < n; ++e) rowptr[(size_t)rows[e] + 1]++;
+  for (int i = 0; i < I; ++i) rowptr[(size_t)i + 1] += rowptr[i];
+  std::vector<uint32_t> at(rowptr.begin(), rowptr.end() - 1);
+  for (uint64_t e = 0; e < n; ++e) { const uint32_t q = at[rows[e]]++; col[q] = (uint32_t)cols[e]; perm[q] = (uint32_t)e; }
+}
+constexpr size_t kSampleStageBytes = (size_t)256 << 20;          // chunk_samples = 0: as many samples as fit this, at least one
+// samples per upload and launch: chunk_samples, or with 0 what fits the staging size; at most T
+static int sample_chunk(int chunk_samples, int T, size_t floats_per_sample) {
+  int chunk = chunk_samples;
+  if (chunk == 0) {
+    const size_t fit = kSampleStageBytes / (floats_per_sample * sizeof(float));
+    chunk = fit < 1 ? 1 : fit > (size_t)T ? T : (int)fit;
+  }
+  return chunk > T ? T : chunk;
+}
+// samples [t0, t0 + c) of the call, array indices first + t * step, `per` floats each, onto dst
+static int upload_samples(float* dst, const float* src, size_t per, uint64_t first, uint64_t step, int t0, int c, hipStream_t st) {
+  if (step == 1) {
+    HIPCHK(hipMemcpyAsync(dst, src + (first + (uint64_t)t0) * per, (size_t)c * per * sizeof(float), hipMemcpyHostToDevice, st));
+    return BNMTF_OK;
+  }
+  for (int s = 0; s < c; ++s)
+    HIPCHK(hipMemcpyAsync(dst + (size_t)s * per, src + (first + (uint64_t)(t0 + s) * step) * per, per * sizeof(float), hipMemcpyHostToDevice, st));
   return BNMTF_OK;
 }
 
@@ -1794,4 +1827,5 @@ int bnmtf_gamma_sample(double alpha, double beta, uint64_t seed, uint64_t it, in
 #include "api_top.inc"
 #include "api_foldin.inc"
 #include "api_predictive_q.inc"
+#include "api_log_predictive.inc"
 #include "api_predictive.inc"

@@ -6,24 +6,8 @@
 // the device, and walks the samples in chunks: upload of the chunk (one copy per factor when step = 1, else one per sample), one
 // launch of predictive_kernel (kernel_predictive.hip), which read-modify-writes the accumulators.  Everything is owned by objects
 // of this function: whichever way it leaves, nothing stays.  One stream: the upload of a chunk follows the kernel of the one
-// before (DESIGN.md section 2.8 has the measured split that decided against a second stream).
-
-namespace bnmtf {
-
-constexpr size_t kPredictiveStageBytes = (size_t)256 << 20;      // chunk_samples = 0: as many samples as fit this, at least one
-
-// samples [t0, t0 + c) of the call, array indices first + t * step, `per` floats each, onto dst
-static int predictive_upload(float* dst, const float* src, size_t per, uint64_t first, uint64_t step, int t0, int c, hipStream_t st) {
-  if (step == 1) {
-    HIPCHK(hipMemcpyAsync(dst, src + (first + (uint64_t)t0) * per, (size_t)c * per * sizeof(float), hipMemcpyHostToDevice, st));
-    return BNMTF_OK;
-  }
-  for (int s = 0; s < c; ++s)
-    HIPCHK(hipMemcpyAsync(dst + (size_t)s * per, src + (first + (uint64_t)(t0 + s) * step) * per, per * sizeof(float), hipMemcpyHostToDevice, st));
-  return BNMTF_OK;
-}
-
-}  // namespace bnmtf
+// before (DESIGN.md section 2.8 has the measured split that decided against a second stream).  The row sort, the chunk size and
+// the upload of a chunk are api.hip's (sort_entries_by_row, sample_chunk, upload_samples): api_log_predictive.inc walks the same way.
 
 extern "C" {
 
@@ -48,22 +32,12 @@ int bnmtf_predictive_samples(int device, int I, int J, int K, int L, uint64_t n,
     }
 
   // ---- the list by row, in the given order within a row
-  std::vector<uint32_t> rowptr((size_t)I + 1, 0u), col(n), perm(n);
-  for (uint64_t e = 0; e < n; ++e) rowptr[(size_t)rows[e] + 1]++;
-  for (int i = 0; i < I; ++i) rowptr[(size_t)i + 1] += rowptr[i];
-  {
-    std::vector<uint32_t> at(rowptr.begin(), rowptr.end() - 1);
-    for (uint64_t e = 0; e < n; ++e) { const uint32_t q = at[rows[e]]++; col[q] = (uint32_t)cols[e]; perm[q] = (uint32_t)e; }
-  }
+  std::vector<uint32_t> rowptr, col, perm;
+  sort_entries_by_row(I, n, rows, cols, rowptr, col, perm);
 
   const int W = L > 0 ? L : K;
   const size_t perA = (size_t)I * K, perS = (size_t)K * L, perB = (size_t)J * W;
-  int chunk = chunk_samples;
-  if (chunk == 0) {
-    const size_t fit = kPredictiveStageBytes / ((perA + perS + perB) * sizeof(float));
-    chunk = fit < 1 ? 1 : fit > (size_t)T ? T : (int)fit;
-  }
-  if (chunk > T) chunk = T;
+  const int chunk = sample_chunk(chunk_samples, T, perA + perS + perB);
 
   // ---- the device's side: all of it owned here
   CallScope cs;
@@ -87,9 +61,9 @@ int bnmtf_predictive_samples(int device, int I, int J, int K, int L, uint64_t n,
   for (int t0 = 0; t0 < T; t0 += chunk) {
     const int c = T - t0 < chunk ? T - t0 : chunk;
     CHK(cs.mark(0));
-    CHK(predictive_upload(dA.p, A, perA, first, step, t0, c, cs.s));
-    if (L > 0) CHK(predictive_upload(dS.p, S, perS, first, step, t0, c, cs.s));
-    CHK(predictive_upload(dB.p, B, perB, first, step, t0, c, cs.s));
+    CHK(upload_samples(dA.p, A, perA, first, step, t0, c, cs.s));
+    if (L > 0) CHK(upload_samples(dS.p, S, perS, first, step, t0, c, cs.s));
+    CHK(upload_samples(dB.p, B, perB, first, step, t0, c, cs.s));
     CHK(cs.mark(1));
     a.C = c; a.first = t0 == 0 ? 1 : 0;
     launch_predictive(a, cs.s);

@@ -57,13 +57,8 @@ int bnmtf_predictive_moments(int device, int I, int J, int K, int L, uint64_t n,
   }
 
   // ---- the list by row, in the given order within a row
-  std::vector<uint32_t> rowptr((size_t)I + 1, 0u), col(n), perm(n);
-  for (uint64_t e = 0; e < n; ++e) rowptr[(size_t)rows[e] + 1]++;
-  for (int i = 0; i < I; ++i) rowptr[(size_t)i + 1] += rowptr[i];
-  {
-    std::vector<uint32_t> at(rowptr.begin(), rowptr.end() - 1);
-    for (uint64_t e = 0; e < n; ++e) { const uint32_t q = at[rows[e]]++; col[q] = (uint32_t)cols[e]; perm[q] = (uint32_t)e; }
-  }
+  std::vector<uint32_t> rowptr, col, perm;
+  sort_entries_by_row(I, n, rows, cols, rowptr, col, perm);
 
   // ---- the device's side: all of it owned here
   CallScope cs;

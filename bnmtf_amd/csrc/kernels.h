@@ -636,6 +636,26 @@ struct PredictiveArgs {
 };
 void launch_predictive(const PredictiveArgs& a, hipStream_t st);
 
+// Log predictive density of known values under stored samples over a row-sorted entry list (kernel_log_predictive.hip;
+// bnmtf_log_predictive_samples): predictive_kernel's gather, and per entry and sample the Gaussian
+// log-likelihood l_t = fma(-(h_t d), d, c_t), d = r - p_t, into five accumulators: the shifted moments of l and a running-maximum
+// log-sum-exp.  One launch per chunk of samples, the accumulators read-modify-written in sample order
+struct LogPredictiveArgs {
+  const uint32_t* rowptr;            // [I + 1] the entries of row i are [rowptr[i], rowptr[i + 1])
+  const uint32_t* col;               // [n] their columns
+  const double* val;                 // [n] their values r, in list order
+  const float* A;                    // [C][I][K] the chunk's samples of U, or F; unpadded
+  const float* S;                    // [C][K][L], or null (L = 0)
+  const float* B;                    // [C][J][K] V, or [C][J][L] G
+  const double* c; const double* h;  // [C] the chunk's c_t = (log tau_t - log 2 pi) / 2 and h_t = tau_t / 2, from the host
+  int I, J, K, L;                    // K, L <= kObsMaxRank
+  int C;                             // samples in the chunk
+  int first;                         // the chunk begins with the call's first sample: it sets l_first, l_max and sum_exp = 1
+  double* l_first; double* sum_d; double* sum_d2;   // [n] in list order; the sums zero before the first chunk
+  double* l_max; double* sum_exp;                   // [n]: max_t l_t so far and sum_t exp(l_t - l_max)
+};
+void launch_log_predictive(const LogPredictiveArgs& a, hipStream_t st);
+
 // Closed-form predictive mean and variance under a mean-field q over a row-sorted entry list (kernel_predictive_q.hip;
 // bnmtf_predictive_moments): the factors' means and variances in fp64, one launch (two for the
 // tri-factorisation: the column table H = G S^T first)

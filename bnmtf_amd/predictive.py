@@ -56,7 +56,9 @@ def _progression(who, indices, stored):
     return first, step, int(idx.size)
 
 
-def _compute(who, factors, taus, shape, rows, cols, indices, device, chunk_samples):
+def _operands(who, factors, taus, shape, rows, cols, indices, chunk_samples):
+    """What bnmtf_predictive_samples and bnmtf_log_predictive_samples are handed, checked: (I, J, K, L, rows, cols, A, S, B, first,
+    step, T, the selected taus in fp64)"""
     if len(factors) not in (2, 3):
         refuse(who, "factors is (all_A, all_B) or (all_A, all_S, all_B), not %d arrays" % len(factors))
     I, J = int(shape[0]), int(shape[1])
@@ -90,12 +92,16 @@ def _compute(who, factors, taus, shape, rows, cols, indices, device, chunk_sampl
     taus = np.asarray(taus, dtype=np.float64)
     if taus.ndim != 1 or len(taus) < stop:
         refuse(who, "taus holds a value per stored sample, not %s" % (taus.shape,))
-    noise = float(np.mean(1.0 / taus[first:stop:step]))
+    return I, J, int(K), int(L), rows, cols, A, S, B, c_first, c_step, int(T), taus[first:stop:step]
 
+
+def _compute(who, factors, taus, shape, rows, cols, indices, device, chunk_samples):
+    I, J, K, L, rows, cols, A, S, B, c_first, c_step, T, taus = _operands(who, factors, taus, shape, rows, cols, indices, chunk_samples)
+    noise = float(np.mean(1.0 / taus))
     n = len(rows)
     p_first, sum_d, sum_d2 = np.zeros(n), np.zeros(n), np.zeros(n)
-    _lib.check(_lib.lib().bnmtf_predictive_samples(int(device), I, J, int(K), int(L), C.c_uint64(n), _lib.ptr(rows), _lib.ptr(cols),
-                                                   _lib.ptr(A), _lib.ptr(S), _lib.ptr(B), C.c_uint64(c_first), C.c_uint64(c_step), int(T),
+    _lib.check(_lib.lib().bnmtf_predictive_samples(int(device), I, J, K, L, C.c_uint64(n), _lib.ptr(rows), _lib.ptr(cols),
+                                                   _lib.ptr(A), _lib.ptr(S), _lib.ptr(B), C.c_uint64(c_first), C.c_uint64(c_step), T,
                                                    int(chunk_samples), _lib.ptr(p_first), _lib.ptr(sum_d), _lib.ptr(sum_d2)))
     mean, variance = shifted_moments(p_first, sum_d, sum_d2, T)
     return Predictive(rows, cols, mean, variance, noise, T)

@@ -691,6 +691,26 @@ BNMTF_API int bnmtf_predictive_moments(int device, int I, int J, int K, int L, u
  * returned BNMTF_OK; zeros before one did (tools/predictive_q_rates.py) */
 BNMTF_API int bnmtf_predictive_moments_times(double* upload_ms, double* kernel_ms);
 
+/* ---- log predictive density of known values under stored samples over an entry list (bnmtf_amd.log_predictive; DESIGN.md
+ * section 2.8b) -----------------------------------------------------------------------------------------------------------------
+ * bnmtf_predictive_samples' arguments, checks and walk, and with them values [n], fp64 and finite: the known value r_e of entry e;
+ * c, h [T], per selected sample s = 0 .. T - 1: c_s = (log tau_s - log 2 pi) / 2, finite, and h_s = tau_s / 2, finite and > 0,
+ * formed by the caller (the device takes no logarithm).  Per entry and sample, with p_s as bnmtf_predictive_samples forms it, the
+ * Gaussian log-likelihood l_s = fma(-(h_s d), d, c_s), d = r_e - p_s, in fp64.  Outputs [n] in the given order: l_first = l_0,
+ * sum_d = sum_s (l_s - l_0), sum_d2 = sum_s (l_s - l_0)^2 (fma), l_max = max_s l_s and sum_exp = sum_s exp(l_s - l_max), kept as a
+ * running maximum: from l_max = l_0, sum_exp = 1, in ascending s, l_s > l_max: sum_exp = fma(sum_exp, exp(l_max - l_s), 1), l_max =
+ * l_s; else sum_exp += exp(l_s - l_max).  The caller finishes lpd_e = l_max + log(sum_exp) - log(T), the mean l_first + sum_d / T
+ * and the variance (sum_d2 - sum_d^2 / T) / (T - 1).  An entry's five numbers depend on that entry, its value and the samples
+ * alone -- not on chunk_samples, not on the list's order or on what else is in it.  Everything is checked before the first device
+ * call. */
+BNMTF_API int bnmtf_log_predictive_samples(int device, int I, int J, int K, int L, uint64_t n,
+    const int32_t* rows, const int32_t* cols, const double* values, const float* A, const float* S, const float* B,
+    uint64_t first, uint64_t step, int T, int chunk_samples, const double* c, const double* h,
+    double* l_first, double* sum_d, double* sum_d2, double* l_max, double* sum_exp);
+/* upload and kernel time (ms, from events on the call's stream, summed over its chunks) of the calling host thread's last
+ * bnmtf_log_predictive_samples that returned BNMTF_OK; zeros before one did (tools/log_predictive_rates.py) */
+BNMTF_API int bnmtf_log_predictive_times(double* upload_ms, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
